@@ -232,6 +232,37 @@ def comm_kind_name():
     return " / ".join(names.get(k, str(k)) for k in kinds) or "none"
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, walkers, scalars, world, rank):
+    """``--dump-outputs DIR``: the timed path's results as ``DIR/<name>.npy`` (float64).  ``walkers``: the per-walker arrays
+    of this rank's shard (gathered over the ranks in rank order); ``scalars``: the replicated adaptation state.  Beyond
+    DUMP_MAX_BYTES the per-walker arrays keep a fixed, seeded sample of their rows, half the cap's worth (listed in
+    ``rows.npy``)."""
+    import torch.distributed as dist
+    walkers = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in walkers.items()}
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, walkers)
+        walkers = {k: np.concatenate([p[k] for p in parts]) for k in walkers}
+    if rank != 0:
+        return
+    arrays = dict(walkers)
+    n_rows = len(arrays["u"])
+    row_bytes = sum(v[:1].nbytes for v in walkers.values())
+    if n_rows * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, DUMP_MAX_BYTES // (2 * row_bytes), replace=False))
+        arrays = {k: v[rows] for k, v in walkers.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k, v in scalars.items():
+        if v is not None:
+            arrays[k] = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
 
 
 def main():
@@ -288,7 +319,13 @@ def main():
                          "inverse sweep multiplies everything left of the diagonal tile with 16-bit operands and float32 accumulation "
                          "(Flow(inverse_precision=...); the dependent chain stays float32) -- opt-in precision, tolerance stated in "
                          "tests/test_gpu_config.py")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last step (walker state u, x, logdetj, logl, logp; "
+                         "proposal_scale, accept, mu) as DIR/<name>.npy, float64, at most 64 MB; the inputs depend on the "
+                         "arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
@@ -622,6 +659,12 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dt_local = dt
+    if args.dump_outputs:
+        # what a preconditioned_pcn call of the K timed steps returns (pocomc_amd/mcmc.py::_run), taken before the passes
+        # below step the walkers on
+        ad_t = ad_l if leng is not None else ad
+        dump_outputs(args.dump_outputs, (leng if leng is not None else eng).download(),
+                     dict(proposal_scale=ad_t.sigma, accept=ad_t.mean_alpha, mu=ad_t.mu), world, rank)
     # the host clocks of the K timed steps, taken HERE: the steady-state loop below adds to the same accumulators (round 5
     # divided their sum over K + 200 steps by K: step_call read 11x a step)
     seg_region = dict(t_lseg if leng is not None else t_seg)

@@ -29,6 +29,27 @@ def _free_port():
     return p
 
 
+# GPU nodes shared between users cap the processes that hold one device open; this suite keeps to PROCS_PER_GPU per
+# device.  The kernel-call tests place their ranks on the devices round robin (_rank_device: all on device 0 of a one-GPU
+# node), so device 0 holds the test process and ceil(world / GPUs) ranks.
+PROCS_PER_GPU = 6
+
+
+def _rank_device(rank):
+    import torch
+    torch.cuda.set_device(rank % torch.cuda.device_count())
+
+
+def skip_unless_gpus_for(world):
+    import torch
+    n = max(torch.cuda.device_count(), 1)
+    on_device0 = -(-world // n) + 1
+    if on_device0 > PROCS_PER_GPU:
+        need = -(-world // (PROCS_PER_GPU - 1))
+        pytest.skip(f"needs {need} GPUs, found {n}: {world} ranks would put {on_device0} processes on one GPU "
+                    f"(at most {PROCS_PER_GPU})")
+
+
 def _worker(rank, world, port, out, fit_parallel="auto"):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -172,6 +193,7 @@ def _kernel_worker(rank, world, port, out, lanes):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    _rank_device(rank)
     lo, hi = rank * 640 // world, (rank + 1) * 640 // world
     r = _kernel_call(lo, hi, lanes, dict(group=None, shard_offset=lo))
     np.savez(out % rank, u=r["u"], logl=r["logl"], sigma=r["proposal_scale"], accept=r["accept"], steps=r["steps"])
@@ -181,9 +203,10 @@ def _kernel_worker(rank, world, port, out, lanes):
 
 @pytest.mark.parametrize("world,lanes", [(2, 1), (2, 2), (4, 2), (8, 2)])
 def test_sharded_pipelined_kernel_call_equals_one_rank(tmp_path, world, lanes):
-    """Walkers sharded over 2, 4 and 8 ranks (one GPU shared by the processes: the rank plumbing, not the links), adaptation
-    on the device (lane sums -> exchange -> sigma / mu update, the next pre-step enqueued behind it): the same trajectory
-    as the whole set on one rank, up to the order in which the sums are added."""
+    """Walkers sharded over 2, 4 and 8 ranks (on a one-GPU node the processes share it: the rank plumbing, not the
+    links), adaptation on the device (lane sums -> exchange -> sigma / mu update, the next pre-step enqueued behind it):
+    the same trajectory as the whole set on one rank, up to the order in which the sums are added."""
+    skip_unless_gpus_for(world)
     import torch.multiprocessing as mp
     out = str(tmp_path / "k%d.npz")
     mp.spawn(_kernel_worker, args=(world, _free_port(), out, lanes), nprocs=world, join=True)
@@ -204,6 +227,7 @@ def _comm_worker(rank, world, port, out, c_allreduce, mailbox, Dk=6):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       PMC_C_ALLREDUCE=c_allreduce, PMC_COMM_MAILBOX=mailbox)
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    _rank_device(rank)
     from pocomc_amd import mcmc as pmcmc
     lo, hi = rank * 640 // world, (rank + 1) * 640 // world
     r = _kernel_call(lo, hi, 2, dict(group=None, shard_offset=lo), Dk)
@@ -218,7 +242,7 @@ def _comm_worker(rank, world, port, out, c_allreduce, mailbox, Dk=6):
 
 
 @pytest.mark.parametrize("world,mailbox,Dk", [(2, "device", 6), (2, "host", 6), (4, "device", 6), (4, "host", 6),
-                                              (8, "device", 6), (8, "host", 6), (8, "device", 32), (8, "host", 128)])
+                                              (4, "device", 32), (4, "host", 128), (8, "device", 6), (8, "host", 6), (8, "device", 32), (8, "host", 128)])
 def test_the_sharded_step_behind_the_c_abi_equals_the_torch_distributed_path(tmp_path, world, mailbox, Dk):
     """2, 4 and 8 ranks, walkers sharded (D = 6, 32, 128: the two-wave sweep, the headline's, and the lane sweep of config 5's
     width): the step runs behind ``pmc_pipeline_*`` with the library's own exchange between the last accept and the
@@ -228,8 +252,9 @@ def test_the_sharded_step_behind_the_c_abi_equals_the_torch_distributed_path(tmp
     processes share one GPU here and map LOCAL memory; on a node every handle is a peer's).  ``mailbox="host"``: the
     mailboxes in pinned host memory (POSIX shared memory registered with every rank's runtime) -- every system-scope
     store, sequence word and acquire-poll of the protocol crosses PCIe to memory no device caches: the stand-in for a
-    remote target on a one-GPU box.  No link between two GPUs is crossed by this test: what it rehearses is the 4- and
+    remote target on a one-GPU box.  On a one-GPU node no link between two GPUs is crossed by this test: what it rehearses is the 4- and
     8-way handle exchange, the mailbox indexing and the rank-ordered sums."""
+    skip_unless_gpus_for(world)
     import torch.multiprocessing as mp
     res = {}
     for flag in ("1", "0"):
