@@ -119,9 +119,12 @@ def _take(a, k, xp):
     return a.gather(-1, k[..., None])[..., 0]
 
 
-def rqs_forward(x, phi, K=8, xp=np):
-    """``y, ladj`` of the spline at ``x`` (..., ) with parameters ``phi`` (..., 3K-1)."""
+def rqs_forward(x, phi, K=8, xp=np, tables=None):
+    """``y, ladj`` of the spline at ``x`` (..., ) with parameters ``phi`` (..., 3K-1).  ``tables``: a function applied to the
+    knots ``(xk, yk, dk)`` before use (the sensitivity envelope of tests/flow_regimes.py perturbs them)."""
     xk, yk, dk = _rqs_knots(phi, K, xp)
+    if tables is not None:
+        xk, yk, dk = tables(xk, yk, dk)
     k = (xk < x[..., None]).sum(-1) - 1                  # searchsorted(knots, x) - 1
     mask = (k >= 0) & (k < K)
     kc = k.clip(0, K - 1) if xp is np else k.clamp(0, K - 1)
@@ -138,9 +141,11 @@ def rqs_forward(x, phi, K=8, xp=np):
     return xp.where(mask, y, x), xp.where(mask, ladj, xp.zeros_like(ladj))
 
 
-def rqs_inverse(y, phi, K=8, xp=np):
+def rqs_inverse(y, phi, K=8, xp=np, tables=None):
     """``x, ladj_forward(x)`` with ``rqs_forward(x) = y``."""
     xk, yk, dk = _rqs_knots(phi, K, xp)
+    if tables is not None:
+        xk, yk, dk = tables(xk, yk, dk)
     k = (yk < y[..., None]).sum(-1) - 1
     mask = (k >= 0) & (k < K)
     kc = k.clip(0, K - 1) if xp is np else k.clamp(0, K - 1)
@@ -168,6 +173,7 @@ class OracleMAF:
         for two float32 evaluations (this file's, a kernel's) of an ill-conditioned map such as the spline."""
         self.spec = spec
         self.F = F = np.dtype(dtype).type
+        self.tables = None                   # optional hook on the spline's knots (rqs_forward / rqs_inverse)
         self.flat = np.asarray(flat, dtype=F32)
         assert self.flat.shape == (spec.n_params,)
         self._mats = []
@@ -203,7 +209,7 @@ class OracleMAF:
         if self.spec.univariate == "affine":
             ls = soft_log_scale(phi[..., 1])
             return (x * np.exp(ls) + phi[..., 0]).astype(self.F), ls
-        y, l = rqs_forward(x, phi, self.spec.bins)
+        y, l = rqs_forward(x, phi, self.spec.bins, tables=self.tables)
         return y.astype(self.F), l.astype(self.F)
 
     def _inv(self, t, xcur, y):
@@ -212,7 +218,7 @@ class OracleMAF:
         if self.spec.univariate == "affine":
             ls = soft_log_scale(phi[..., 1])
             return ((y - phi[..., 0]) / np.exp(ls)).astype(self.F), ls
-        x, l = rqs_inverse(y, phi, self.spec.bins)
+        x, l = rqs_inverse(y, phi, self.spec.bins, tables=self.tables)
         return x.astype(self.F), l.astype(self.F)
 
     def forward(self, x):

@@ -1,0 +1,192 @@
+"""The criterion of ``tests/flow_regimes.py`` without a GPU: float32 evaluations of the flow (the numpy oracle, the torch
+twin) meet it on trained and output-gain flows and at the spline's edges, a deliberate one-ulp defect fails it, and the
+edge inputs lie exactly where the helper says.
+
+What the envelope must contain was measured here.  Perturbing only the inputs and the parameters (the literal recipe,
+``knots=False``) misses the float32 rounding of the spline's knots: cumulative sums near +-5 carry ~ulp(5) of absolute
+error whatever the bin's width, so the float32 oracle's median ``err/e`` on a trained nsf6 inverse is ~5.  With the computed
+knots and interior derivatives jittered as well, every float32 evaluation passes -- except the spline flow with its output
+layer x16 (bins at the 1e-3 floor, derivatives 3e-3 .. 3e2), where the inverse's x of the float32 oracle itself falls
+outside ``C e_i`` on a few rows, and so do the torch twin's log-density on a row with every coordinate on a knot and the
+inverse's log-determinant (there and already at x4): those are beyond float32 and are asserted to be so (``BEYOND_F32``)."""
+import numpy as np
+import pytest
+import torch
+
+import flow_regimes as fr
+from oracle.maf import OracleMAF, _rqs_knots, soft_log_scale, torch_log_prob
+from pocomc_amd.maf_spec import MAFSpec
+
+
+def fixture(name):
+    if name.endswith("trained"):
+        return fr.twin_trained(name.split("-")[0])
+    kind, g = name.split("-g")
+    spec = MAFSpec(10, 3) if kind == "maf3" else MAFSpec(10, 6, univariate="rqs")
+    return spec, fr.gain_params(spec, float(g))
+
+
+FIXTURES = ["maf3-trained", "nsf6-trained", "maf3-g4", "maf3-g16", "nsf6-g4", "nsf6-g16"]
+# quantities no float32 evaluation meets the criterion on (measured here): asserted to FAIL, so that the table stays true
+BEYOND_F32 = {"nsf6-g4": ("inverse ladj",),
+              "nsf6-g16": ("inverse x", "inverse ladj", "twin log_prob")}
+
+
+def forward_inputs(spec, flat, n=192, seed=1):
+    x = fr.two_modes(spec.n_dim, n, seed) * np.float32(1.3)
+    parts = [x]     # (tails: a coordinate of 1e3 or more rounds its neighbours' hidden activations at its own scale, which the
+                    #  envelope does not model: they go to the identity / non-finite tests of tests/test_gpu_flow_regimes.py)
+    if spec.univariate == "rqs":
+        parts += [fr.knot_rows(spec, flat, x)[0], fr.all_knot_rows(spec, flat, x[:16])[0], fr.box_rows(spec, flat, x)[0]]
+    return np.concatenate(parts).astype(np.float32)
+
+
+def inverse_inputs(spec, flat, n=96, seed=2):
+    z = (np.random.default_rng(seed).normal(size=(n, spec.n_dim)) * 1.2).astype(np.float32)
+    parts = [z]             # (latent tails: the float32 D-pass overflows in its early passes where float64 does not)
+    if spec.univariate == "rqs":
+        parts += [fr.knot_rows(spec, flat, z, inverse=True)[0], fr.box_rows(spec, flat, z, inverse=True)[0]]
+    return np.concatenate(parts).astype(np.float32)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_float32_evaluations_meet_the_criterion(name):
+    spec, flat = fixture(name)
+    o = OracleMAF(spec, flat)
+    beyond = BEYOND_F32.get(name, ())
+    x = forward_inputs(spec, flat)
+    R = fr.Reference(spec, flat, x, "forward")
+    z, l = o.forward(x)
+    got = {"z": z, "ladj": l, "log_prob": o.log_prob(x)}
+    for q, v in got.items():
+        if f"forward {q}" in beyond:
+            assert not R.passes(q, v), f"{name} {q}: the float32 oracle meets the criterion (update BEYOND_F32)"
+        else:
+            R.check(q, v, f"cpu oracle32 forward, {name}")
+    lt = torch_log_prob(spec, torch.from_numpy(flat), torch.from_numpy(x)).numpy()
+    if "twin log_prob" in beyond:
+        assert not R.passes("log_prob", lt), f"{name}: the float32 twin meets the criterion (update BEYOND_F32)"
+    else:
+        R.check("log_prob", lt, f"cpu twin32 log_prob, {name}")
+    zz = inverse_inputs(spec, flat)
+    R = fr.Reference(spec, flat, zz, "inverse")
+    xi, li = o.inverse(zz)
+    for q, v in (("x", xi), ("ladj", li)):
+        if f"inverse {q}" in beyond:
+            assert not R.passes(q, v), f"{name} {q}: the float32 oracle meets the criterion (update BEYOND_F32)"
+        else:
+            R.check(q, v, f"cpu oracle32 inverse, {name}")
+
+
+def test_the_envelope_needs_the_knots_of_the_spline():
+    """Inputs and parameters alone (``knots=False``) do not bound the float32 oracle's error on a trained spline flow: the
+    knot rounding is a float32 evaluation's own, and the envelope has to carry it."""
+    spec, flat = fixture("nsf6-trained")
+    zz = (np.random.default_rng(2).normal(size=(96, spec.n_dim)) * 1.2).astype(np.float32)
+    xi, _ = OracleMAF(spec, flat).inverse(zz)
+    assert not fr.Reference(spec, flat, zz, "inverse", knots=False).passes("x", xi)
+    assert fr.Reference(spec, flat, zz, "inverse").passes("x", xi)
+
+
+class BiasedExp(OracleMAF):
+    """The float32 oracle with ``exp`` of the affine map's log-scale one ulp high (what a biased hardware exponential
+    would do): a defect well inside the suite's fixed 1e-5 bound."""
+    UP = np.float32(1.0 + 2.0 ** -23)
+
+    def _fwd(self, t, x):
+        phi = self._phi(t, x)
+        ls = soft_log_scale(phi[..., 1])
+        return (x * (np.exp(ls) * self.UP).astype(np.float32) + phi[..., 0]).astype(self.F), ls
+
+    def _inv(self, t, xcur, y):
+        phi = self._phi(t, xcur)
+        ls = soft_log_scale(phi[..., 1])
+        return ((y - phi[..., 0]) / (np.exp(ls) * self.UP).astype(np.float32)).astype(self.F), ls
+
+
+def test_a_one_ulp_biased_exp_fails_the_criterion():
+    """On the trained affine flow the bias moves the median ``err/e`` of z / log_prob past ``MEDIAN_BOUND`` (measured 2.7 /
+    2.9; the float32 oracle: 0.8 / 0.7)."""
+    spec, flat = fixture("maf3-trained")
+    x = forward_inputs(spec, flat)
+    R = fr.Reference(spec, flat, x, "forward")
+    o = BiasedExp(spec, flat)
+    z, _ = o.forward(x)
+    assert not (R.passes("z", z) and R.passes("log_prob", o.log_prob(x)))
+    assert fr.row_err(z, R.ref["z"])[R.ok].max() < 1e-5          # (the fixed bound alone lets it through)
+    z32, _ = OracleMAF(spec, flat).forward(x)
+    assert R.passes("z", z32)
+
+
+def test_the_fixtures_reach_their_regimes():
+    x = fr.two_modes(10, 256, 1) * np.float32(1.3)
+    s = fr.regime_stats(*fixture("maf3-g16"), x)
+    assert s["big_log_scale_share"] > 0.2                          # log-scales near the clip's +-6.9
+    s = fr.regime_stats(*fixture("nsf6-g16"), x)
+    assert s["small_bin_share"] > 0.03 and s["deriv_min"] < 1e-2 and s["deriv_max"] > 1e2
+    s = fr.regime_stats(*fixture("nsf6-g4"), x)
+    assert s["deriv_min"] < 0.1 and s["deriv_max"] > 10
+    # a trained flow is not its initialisation: the float32 oracle's distance to the float64 one grows
+    spec, flat = fixture("nsf6-trained")
+    zz = (np.random.default_rng(2).normal(size=(96, 10)) * 1.2).astype(np.float32)
+    R = fr.Reference(spec, flat, zz, "inverse")
+    R0 = fr.Reference(spec, spec.init_params(0), zz, "inverse")
+    e = fr.row_err(OracleMAF(spec, flat).inverse(zz)[0], R.ref["x"]).max()
+    e0 = fr.row_err(OracleMAF(spec, spec.init_params(0)).inverse(zz)[0], R0.ref["x"]).max()
+    assert e > 2 * e0
+
+
+def test_edge_inputs_lie_where_the_helper_says():
+    spec, flat = fixture("nsf6-trained")
+    K = spec.bins
+    base = fr.two_modes(10, 32, 3)
+    o = OracleMAF(spec, flat)
+    for inverse in (False, True):
+        t = spec.n_transforms - 1 if inverse else 0
+        f = fr.first_feature(spec, t)
+        rows, where = fr.knot_rows(spec, flat, base, inverse)
+        xk, yk = fr.constant_knots(spec, flat, t)
+        kn = yk if inverse else xk
+        cur = np.zeros((len(rows), spec.n_dim), np.float32) if inverse else rows
+        phi = o._phi(t, cur)[:, f]                                 # (rank 0: constant over the rows)
+        assert (phi == phi[:1]).all()
+        for r, (j, d) in zip(rows, where):
+            v = r[f]
+            if d == 0:
+                assert v == kn[j]
+            else:
+                assert v == np.nextafter(kn[j], np.float32(d * np.inf), dtype=np.float32)
+            k = int((kn < v).sum()) - 1                             # the oracle's bin: searchsorted - 1
+            assert k == (j - 1 if d <= 0 else j)
+        rows, band = fr.box_rows(spec, flat, base, inverse)
+        end = kn[-1]
+        vals = rows[:, f]
+        assert set(vals[~band][[2, 7]]) == {np.float32(-5.0), np.float32(5.0)}
+        assert ((vals[band] >= min(end, 5.0)) & (vals[band] <= max(end, 5.0))).all() and band.sum() >= 1
+    x, pick = fr.all_knot_rows(spec, flat, base[:12])
+    for r in range(spec.n_dim):
+        xk, _, _ = _rqs_knots(o._phi(0, x)[:, r], K, np)
+        assert (x[:, r] == xk[np.arange(len(x)), pick[:, r]]).all()
+    assert (pick == 0).any() and (pick == K).any()
+    x, out = fr.outside_rows(spec, base)
+    assert (np.abs(x[out]) >= 5.0001).all() and out[:4].all() and (~out).any()
+    bad, rows = fr.with_nonfinite(base)
+    assert rows == [0, 15, 16, 17, 31]
+    assert (~np.isfinite(bad)).sum(axis=1)[rows].tolist() == [1] * 5 and np.isfinite(np.delete(bad, rows, 0)).all()
+    assert np.isnan(bad).any() and np.isposinf(bad).any() and np.isneginf(bad).any()
+
+
+def test_the_kernels_spline_formulas_carry_a_larger_median_than_numpy():
+    """``KernelSplineOracle`` (the kernels' spline formulas in float32, hardware transcendentals taken as correctly rounded)
+    on the trained nsf6 inverse: median ``err/e`` on x ~1.9 against the numpy oracle's ~1.5 -- the kernels measure 1.94-2.02
+    on a trained nsf6 flow, so that figure is the formulas', not a device defect.  The GPU tests take this evaluation's
+    median into the median bound (``Reference.check(f32=...)``); its rows still meet the row criterion."""
+    spec, flat = fixture("nsf6-trained")
+    zz = (np.random.default_rng(2).normal(size=(192, spec.n_dim)) * 1.2).astype(np.float32)
+    R = fr.Reference(spec, flat, zz, "inverse")
+    s_np = R.check("x", OracleMAF(spec, flat).inverse(zz)[0], "cpu numpy32 inverse", raise_=False)
+    s_k = R.check("x", fr.KernelSplineOracle(spec, flat).inverse(zz)[0], "cpu kernel-model32 inverse", raise_=False)
+    assert s_k["failing"] == 0 and s_np["failing"] == 0
+    assert s_k["median_ratio"] > 1.15 * s_np["median_ratio"]
+    x = fr.two_modes(10, 128, 1)
+    np.testing.assert_allclose(fr.KernelSplineOracle(spec, flat).forward(x)[0], OracleMAF(spec, flat).forward(x)[0], rtol=0, atol=1e-4)
