@@ -35,7 +35,7 @@ struct ChainFrags {
     float4 wt1, wt2;               // the diagonal tile's fragments, rows transposed (chain_vo_T); component c = K chunk c
     float4 wo[2];                  // output rows (shift, raw) of the tile's groups 0, 1 / 2, 3
     float4 w0o[4];                 // [group].jt: W0[row q of quad jt of this tile][the rank the group produces]
-    // right-looking mode (ABL & 2, the two-wave sweep): what this tile adds to the NEXT tile's pre-activations
+    // CHAIN_RIGHT_LOOKING (the two-wave sweep): what this tile adds to the NEXT tile's pre-activations
     float4 wn1, wn2;               // block (Tt + 1, Tt) of layers 1 / 2, transposed
     float4 woN[2];                 // (shift, raw) rows of the next tile's groups
     float4 w0N[4];                 // [group].jt: W0[row q of quad jt of the next tile][the rank the group produces]
@@ -105,11 +105,18 @@ __device__ __forceinline__ void chain_tile_begin(ChainRot<MAXO>& s, const ChainF
     s.pend_ls = 0.0f;
 }
 
-// (ABL: timing-only switches of scripts/abl_tri5.sh above 0xff -- results are wrong with them)
-// ABL & 2: right-looking mode -- every group also adds its share to the next tile's pre-activations (accN1, accN2, outN, a0N)
-// ABL & 1: no right-looking output updates -- the caller supplies the output partials of the previous tiles itself (the
-// two-wave sweep: its burst wave adds them once per tile from the h2 tile this function then stores in H2[tile parity]).
-//
+// Modes of chain_group_rot (bits; 0 = the lone-wave sweep, tri4):
+//   CHAIN_OWN_OUTPUT: no right-looking output updates -- the caller supplies the output partials of the previous tiles
+//     itself (the two-wave sweep: its burst wave adds them once per tile from the h2 tile this function then stores in
+//     H2[tile parity]);
+//   CHAIN_RIGHT_LOOKING: every group also adds its share to the next tile's pre-activations (accN1, accN2, outN, a0N);
+//   CHAIN_HALF: one output accumulator whose rows differ between the two halves of the wavefront (hop 3 below).
+// The two-wave sweep (tri5) runs all three: CHAIN_TWO_WAVE.
+constexpr int CHAIN_OWN_OUTPUT = 1;
+constexpr int CHAIN_RIGHT_LOOKING = 2;
+constexpr int CHAIN_HALF = 4;
+constexpr int CHAIN_TWO_WAVE = CHAIN_OWN_OUTPUT | CHAIN_RIGHT_LOOKING | CHAIN_HALF;
+
 // Groups I .. END-1 of the tile, one after the other, as STRAIGHT-LINE code: a conditional update of an
 // accumulator array costs a register copy per element on every path (SSA phi), so padding groups
 // (degree >= D: zero weights, zero activations) run through the same instructions and only their
@@ -117,7 +124,7 @@ __device__ __forceinline__ void chain_tile_begin(ChainRot<MAXO>& s, const ChainF
 // fragments of output tiles whose ranks are all below g are exact zeros).
 // `extra(group, hop, groups of the tile)`: caller's work for the shadow of hop 0..2 of a group (the next tile's fragment requests).
 // The last group's side effects stay pending: chain_flush() after the last call of a tile.
-template <int PAT, int I, int END, int MAXO, int ABL = 0, class EX = ChainNoExtra>
+template <int PAT, int I, int END, int MAXO, int MODE = 0, class EX = ChainNoExtra>
 __device__ __forceinline__ void chain_group_rot(ChainRot<MAXO>& s, const ChainFrags<MAXO>& f, float* H0, float* H1, float* X, int Tt,
                                                 int D, int nOT, int q, int p, float& ladj, float* H2 = nullptr, const EX& extra = EX{}) {
     constexpr int NG = pat_ngroups(PAT);
@@ -137,11 +144,11 @@ __device__ __forceinline__ void chain_group_rot(ChainRot<MAXO>& s, const ChainFr
         CHAIN_FENCE();
         chain_flush(s, ladj);
         if constexpr (I == NG - 1) {                   // (the tile's quads are 16 consecutive bytes per lane)
-            if (!(ABL & 0x400)) *reinterpret_cast<float4*>(H0 + hw) = make_float4(s.h0s[0], s.h0s[1], s.h0s[2], s.h0s[3]);
+            *reinterpret_cast<float4*>(H0 + hw) = make_float4(s.h0s[0], s.h0s[1], s.h0s[2], s.h0s[3]);
         }
         extra(gi, std::integral_constant<int, 0>{}, ng);
         CHAIN_FENCE();
-        if constexpr ((ABL & 2) != 0) {
+        if constexpr ((MODE & CHAIN_RIGHT_LOOKING) != 0) {
 #pragma unroll
             for (int c = c0; c <= c1; ++c) s.accN1 = MFMA(comp(f.wn1, c), h0[c], s.accN1);
             CHAIN_FENCE();
@@ -154,11 +161,11 @@ __device__ __forceinline__ void chain_group_rot(ChainRot<MAXO>& s, const ChainFr
         for (int c = c0; c <= c1; ++c) s.acc2 = MFMA(comp(f.wt2, c), h1[c], s.acc2);
         CHAIN_FENCE();
         if constexpr (I == NG - 1) {
-            if (!(ABL & 0x400)) *reinterpret_cast<float4*>(H1 + hw) = make_float4(s.h1s[0], s.h1s[1], s.h1s[2], s.h1s[3]);
+            *reinterpret_cast<float4*>(H1 + hw) = make_float4(s.h1s[0], s.h1s[1], s.h1s[2], s.h1s[3]);
         }
         extra(gi, std::integral_constant<int, 1>{}, ng);
         CHAIN_FENCE();
-        if constexpr ((ABL & 2) != 0) {
+        if constexpr ((MODE & CHAIN_RIGHT_LOOKING) != 0) {
 #pragma unroll
             for (int c = c0; c <= c1; ++c) s.accN2 = MFMA(comp(f.wn2, c), h1[c], s.accN2);
             CHAIN_FENCE();
@@ -167,16 +174,16 @@ __device__ __forceinline__ void chain_group_rot(ChainRot<MAXO>& s, const ChainFr
         for (int c = c0; c <= c1; ++c) { h2[c] = fmaxf((s.acc2[c] + s.p2[c]) + h1[c], 0.0f); s.h2s[c] = h2[c]; }
         CHAIN_FENCE();
         // ---------------------------------------------------------------- hop 3: output rows of this group
-        // (ABL & 8, "half" mode of the two-wave sweep: ONE output accumulator whose rows differ between the two halves of
+        // (CHAIN_HALF, the two-wave sweep: ONE output accumulator whose rows differ between the two halves of
         //  the wavefront -- lanes q < 2 receive the (shift, raw) pairs of groups 0, 1, lanes q >= 2 those of groups 2, 3 --
         //  so a group costs one output MFMA instead of two, and its x crosses to the other half with v_permlane32_swap)
-        constexpr bool HALF = (ABL & 8) != 0;
+        constexpr bool HALF = (MODE & CHAIN_HALF) != 0;
         constexpr int slot = HALF ? 0 : (I >> 1);
 #pragma unroll
         for (int c = c0; c <= c1; ++c) s.outR[slot] = MFMA(comp(f.wo[slot], c), h2[c], s.outR[slot]);
         CHAIN_FENCE();
         if constexpr (I == NG - 1) {                   // (two tiles deep; the lone-wave sweep uses h2 from registers only)
-            if ((ABL & 1) && !(ABL & 0x400))
+            if constexpr ((MODE & CHAIN_OWN_OUTPUT) != 0)
                 *reinterpret_cast<float4*>(H2 + ((Tt & 1) << 8) + (q << 6) + (p << 2)) = make_float4(s.h2s[0], s.h2s[1], s.h2s[2], s.h2s[3]);
         }
         extra(gi, std::integral_constant<int, 2>{}, ng);
@@ -202,7 +209,7 @@ __device__ __forceinline__ void chain_group_rot(ChainRot<MAXO>& s, const ChainFr
         s.pend_ls = live ? ls : 0.0f;
         s.pend_a = s.xa[I];
         CHAIN_FENCE();
-        if constexpr ((ABL & 2) != 0) {
+        if constexpr ((MODE & CHAIN_RIGHT_LOOKING) != 0) {
             s.a0N[0] = fmaf(f.w0N[I].x, xg, s.a0N[0]); s.a0N[1] = fmaf(f.w0N[I].y, xg, s.a0N[1]);
             s.a0N[2] = fmaf(f.w0N[I].z, xg, s.a0N[2]); s.a0N[3] = fmaf(f.w0N[I].w, xg, s.a0N[3]);
 #pragma unroll
@@ -219,14 +226,14 @@ __device__ __forceinline__ void chain_group_rot(ChainRot<MAXO>& s, const ChainFr
             for (int c = c0; c <= c1; ++c) s.outR[1] = MFMA(comp(f.wo[1], c), h2[c], s.outR[1]);
             CHAIN_FENCE();
         }
-        if (!(ABL & 1)) {
+        if constexpr ((MODE & CHAIN_OWN_OUTPUT) == 0) {
 #pragma unroll
             for (int O = 0; O < MAXO; ++O)
 #pragma unroll
                 for (int c = c0; c <= c1; ++c) s.oN[O] = MFMA(comp(f.f3n[O], c), h2[c], s.oN[O]);
             CHAIN_FENCE();
         }
-        chain_group_rot<PAT, I + 1, END, MAXO, ABL, EX>(s, f, H0, H1, X, Tt, D, nOT, q, p, ladj, H2, extra);
+        chain_group_rot<PAT, I + 1, END, MAXO, MODE, EX>(s, f, H0, H1, X, Tt, D, nOT, q, p, ladj, H2, extra);
     }
 }
 

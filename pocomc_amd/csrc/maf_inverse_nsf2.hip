@@ -2,7 +2,7 @@
 // flow.py:116-132 with flow = nsf3 | nsf6 | nsf12): the spline counterpart of maf_inverse_tri5_kernel.
 //
 // The lone-wave spline sweep (maf_inverse_tri_nsf.hip) spends its time where the affine one did before it was split --
-// 272 us for 7008 walkers of nsf3 @ D = 32, of which (timing-only builds, scripts/abl_nsf.sh) ~100 us are the rank's
+// 272 us for 7008 walkers of nsf3 @ D = 32, of which (timing-only builds, docs/LAB_NOTEBOOK.md) ~100 us are the rank's
 // left-looking output product (23 parameters = two 16-row tiles against every final h2 tile: 8 (Tt + 1) MFMAs per
 // rank), ~65 us the hidden chain with its left-looking bursts, ~53 us the spline solves, ~55 us everything else.  As
 // in the affine sweep the work is cut by WHEN its inputs exist:
@@ -16,19 +16,13 @@
 //     output tiles against h2 tiles <= Tt-2 (into a staged partial the chain's accumulators start from: both waves hold
 //     a 16 x 16 product in the same lane layout, so staging is one 16-byte write and read per lane at the same address).
 //     Round 4: the output partials of the last two live tiles start at steps 2 - 4 (eager partials, NSF2_EAGER_OK): the two
-//     wavefronts are within 10 % of each other at every barrier (scripts/profile_nsf2_tiles.py).
+//     wavefronts are within 10 % of each other at every barrier (barrier stamps: docs/LAB_NOTEBOOK.md).
 // One LDS-only barrier per tile: E(Tt) = "tile Tt is final, the staging of tile Tt+1 is complete".
 #include <stdlib.h>
 #include "maf_chain_rot.h"
 #include "rqs.h"
 #include "propose_body.h"
 
-#ifndef NSF2_ABL
-#define NSF2_ABL 0                 // timing experiments only (scripts/abl_nsf.sh): results are wrong when != 0
-#endif
-#if NSF2_ABL != 0
-extern "C" int pmc_ablation_nsf2(void) { return NSF2_ABL; }      // (see pmc_ablation_tri6)
-#endif                             // 1 no spline solve, 2 no output MFMAs on the chain, 4 burst: no output partials, 8 nor their loads, 16 chain: no output fragment requests, 32 burst: no hidden products, 64 no eager partials (results stay right)
 #define NSF2_PK 10                 // K tiles of the hidden bursts held in registers; the static burst tile covers flows of <= NSF2_PK + 1 live tiles
 #define NSF2_PX 4                  // x tiles of the layer-0 product held in registers (D <= 64)
 #define NSF2_OOB 0x40000000        // a lane offset beyond every image: the bounds-checked load returns zeros
@@ -39,8 +33,8 @@ extern "C" int pmc_ablation_nsf2(void) { return NSF2_ABL; }      // (see pmc_abl
 #define NSF2_LDS_BASE_FLOATS(m) (3 * (m)->Dp * 16 + 3 * (m)->Hp * 16 + 2 * NSF2_STAGE_FLOATS + 2 * NSF2_PART_FLOATS + 16 * 32 + \
                                  ((NSF2_TT_WORDS(m) + (m)->Dp + NSF2_YT_WORDS(m) + 3) & ~3))
 // EAGER PARTIALS (round 4).  The burst wave's work for tile T1 grows with T1 (40 (T1 - 1) MFMAs at 32 cycles each against a
-// chain that takes ~9 k cycles per tile whatever the tile): from the seventh tile on the chain waited for it (scripts/
-// profile_nsf2_tiles.py: 0.5 / 2.1 / 3.1 k cycles at tiles 5 - 7 of a nine-tile flow) while on tiles 1 - 4 the burst wave waited
+// chain that takes ~9 k cycles per tile whatever the tile): from the seventh tile on the chain waited for it (barrier
+// stamps, docs/LAB_NOTEBOOK.md: 0.5 / 2.1 / 3.1 k cycles at tiles 5 - 7 of a nine-tile flow) while on tiles 1 - 4 the burst wave waited
 // 2 - 4 k cycles for the chain.  The output partials of the LAST TWO live tiles therefore start early: their ranks' products
 // against h2 tiles 0, 1, 2 (last tile) and 0, 1 (the one before) are formed at steps 2, 3, 4 -- in the burst wave's idle
 // time -- into two more partial buffers in LDS that only the burst wave touches; the two tiles' own steps start from those
@@ -170,15 +164,13 @@ __device__ __forceinline__ void nsf_group(NsfChain& s, const NsfHid& f, NsfOut (
             CHAIN_FENCE();
             NSF_STAMP(2)
             // ---------------------------------------------------------------- hop 3: the group's own quads
-            if (!(NSF2_ABL & 2)) {
 #pragma unroll
-                for (int c = c0; c <= c1; ++c) s.o0 = MFMA(comp(o.fc0, c), h2[c], s.o0);
-                CHAIN_FENCE();
-                if constexpr (I > 0) { rqs_ladj_2(s.pend); NSF_PIN(s.pend.jac) }
-                CHAIN_FENCE();
+            for (int c = c0; c <= c1; ++c) s.o0 = MFMA(comp(o.fc0, c), h2[c], s.o0);
+            CHAIN_FENCE();
+            if constexpr (I > 0) { rqs_ladj_2(s.pend); NSF_PIN(s.pend.jac) }
+            CHAIN_FENCE();
 #pragma unroll
-                for (int c = c0; c <= c1; ++c) s.o1 = MFMA(comp(o.fc1, c), h2[c], s.o1);
-            }
+            for (int c = c0; c <= c1; ++c) s.o1 = MFMA(comp(o.fc1, c), h2[c], s.o1);
             CHAIN_FENCE();
             NSF_STAMP(3)
             // ---------------------------------------------------------------- this rank's spline solve; in its slots the
@@ -194,9 +186,9 @@ __device__ __forceinline__ void nsf_group(NsfChain& s, const NsfHid& f, NsfOut (
                 constexpr int K = decltype(k_)::value;
                 if constexpr (K < 8) {
                     constexpr int j = K >> 1;
-                    if constexpr ((K & 1) == 0) { if (!(NSF2_ABL & 2)) n0 = MFMA(comp(on.fp0, j), hB[j], n0); }
+                    if constexpr ((K & 1) == 0) n0 = MFMA(comp(on.fp0, j), hB[j], n0);
                     else {
-                        if (!(NSF2_ABL & 2)) n1 = MFMA(comp(on.fp1, j), hB[j], n1);
+                        n1 = MFMA(comp(on.fp1, j), hB[j], n1);
                         if constexpr (!(LAST && (NG & 1))) ahead(gn, std::integral_constant<int, j>{}, ngc);
                         else if constexpr (K == 7) {                        // (the requests' target is the buffer the MFMAs read)
                             ob[0].fc0 = ob[1].fc0; ob[0].fc1 = ob[1].fc1;
@@ -205,24 +197,12 @@ __device__ __forceinline__ void nsf_group(NsfChain& s, const NsfHid& f, NsfOut (
                     }
                 } else if constexpr (K < NM) {
                     constexpr int c = (K - 8) >> 1;
-                    if (!(NSF2_ABL & 2)) {
-                        if constexpr ((K & 1) == 0) n0 = MFMA(comp(on.fc0, c), s.h2s[c], n0);
-                        else n1 = MFMA(comp(on.fc1, c), s.h2s[c], n1);
-                    }
+                    if constexpr ((K & 1) == 0) n0 = MFMA(comp(on.fc0, c), s.h2s[c], n0);
+                    else n1 = MFMA(comp(on.fc1, c), s.h2s[c], n1);
                 }
                 if constexpr (K == 5 && I > 0) { ladj -= rqs_ladj_3(s.pend); NSF_PIN(ladj) }          // (inside the exchange's LDS wait)
             };
-            if (NSF2_ABL & 1) {
-                float* pr = PAR + (p << 5) + (q << 2);
-                *reinterpret_cast<float4*>(pr) = make_float4(s.o0[0], s.o0[1], s.o0[2], s.o0[3]);
-                *reinterpret_cast<float4*>(pr + 16) = make_float4(s.o1[0], s.o1[1], s.o1[2], s.o1[3]);
-                WAVE_LDS_FENCE();
-                xg = yv + PAR[(p << 5)] + PAR[(p << 5) + 22];
-                pn.s = 1.0f; pn.e = 0.0f; pn.z = PAR[(p << 5) + 8]; pn.d0 = pn.d1 = 1.0f; pn.inside = true;
-                static_for<RQS_NSLOTS>(shadow);
-            } else {
-                rqs_inverse_split_sh(s.o0, s.o1, PAR + (p << 5), q, yv, xg, pn, shadow);
-            }
+            rqs_inverse_split_sh(s.o0, s.o1, PAR + (p << 5), q, yv, xg, pn, shadow);
             CHAIN_FENCE();
             NSF_STAMP(4)
             // ---------------------------------------------------------------- what the next hop waits for: the rank-1 update of the
@@ -264,7 +244,7 @@ struct NsfBurstCtx {
     const float *X, *H0, *H1, *H2;
     float *stg, *part;
     int g[4], gnx[4], ksn;         // the ranks of this tile's groups; of the next tile's groups, and the first K step of its own products
-    long long* ts;                 // (measurement only, NSF2_TILE_STAMPS: where this tile's section stamps go, or null)
+    long long* ts;                 // where this tile's section stamps go: always null, kept because removing the stamps changes the compiled kernels
     int eag;                       // eager partials on: eg[0] / ea[0]: the ranks / the partial buffer of the last live tile, [1]: of the one before
     int eg[2][4];
     float* ea[2];
@@ -390,35 +370,27 @@ __device__ __forceinline__ void nsf_burst_tile(const NsfBurstCtx& c, NsfBurstCar
         const float4 b = bnx;
         if constexpr (i + 1 < NK) bnx = *reinterpret_cast<const float4*>(c.H2 + ((i + 1) << 8) + (lane << 2));
         auto ld = [&](const int k) {
-            if constexpr (j + 2 < SH) { if (!(NSF2_ABL & 8)) S[nxt][k] = bload4(c.rs, fvo_[k], fb_[k] + (i + 2) * 1024); }
+            if constexpr (j + 2 < SH) S[nxt][k] = bload4(c.rs, fvo_[k], fb_[k] + (i + 2) * 1024);
         };
         auto xs = [&](const int part) {                                // this step's share of the other requests, in four parts
 #pragma unroll
             for (int l = 0; l < XPS; ++l) if ((l & 3) == part) xload(j * XPS + l);
         };
-        if (!(NSF2_ABL & 4)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].x, b.x, o0[r]);
-            o1c[0] = MFMA(S[cur][4].x, b.x, o1c[0]); o1c[1] = MFMA(S[cur][5].x, b.x, o1c[1]);
-        }
+        for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].x, b.x, o0[r]);
+        o1c[0] = MFMA(S[cur][4].x, b.x, o1c[0]); o1c[1] = MFMA(S[cur][5].x, b.x, o1c[1]);
         ld(0); ld(1); xs(0);
-        if (!(NSF2_ABL & 4)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].y, b.y, o0[r]);
-            o1c[0] = MFMA(S[cur][4].y, b.y, o1c[0]); o1c[1] = MFMA(S[cur][5].y, b.y, o1c[1]);
-        }
+        for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].y, b.y, o0[r]);
+        o1c[0] = MFMA(S[cur][4].y, b.y, o1c[0]); o1c[1] = MFMA(S[cur][5].y, b.y, o1c[1]);
         ld(2); ld(3); xs(1);
-        if (!(NSF2_ABL & 4)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].z, b.z, o0[r]);
-            o1c[0] = MFMA(S[cur][4].z, b.z, o1c[0]); o1c[1] = MFMA(S[cur][5].z, b.z, o1c[1]);
-        }
+        for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].z, b.z, o0[r]);
+        o1c[0] = MFMA(S[cur][4].z, b.z, o1c[0]); o1c[1] = MFMA(S[cur][5].z, b.z, o1c[1]);
         ld(4); ld(5); xs(2);
-        if (!(NSF2_ABL & 4)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].w, b.w, o0[r]);
-            o1c[0] = MFMA(S[cur][4].w, b.w, o1c[0]); o1c[1] = MFMA(S[cur][5].w, b.w, o1c[1]);
-        }
+        for (int r = 0; r < 4; ++r) o0[r] = MFMA(S[cur][r].w, b.w, o0[r]);
+        o1c[0] = MFMA(S[cur][4].w, b.w, o1c[0]); o1c[1] = MFMA(S[cur][5].w, b.w, o1c[1]);
         xs(3);
         CHAIN_FENCE();
     });
@@ -447,7 +419,6 @@ __device__ __forceinline__ void nsf_burst_tile(const NsfBurstCtx& c, NsfBurstCar
         nvo_[k] = k < 4 ? ovo(g) : (k == 4 ? npv0 : npv1);
     }
     auto cload = [&](const int k) {                                    // request k of NCL of the carry
-        if (NSF2_ABL & 8) return;
         if (k < 6 * NCS) carry.f[k / 6][k % 6] = bload4(c.rs, nvo_[k % 6], nb_[k % 6] + (k / 6) * 1024);
         else if (k < NCL) carry.b[k - 6 * NCS] = bias(c.tb, c.gnx, nbv0, nbv1, k - 6 * NCS);
     };
@@ -461,16 +432,12 @@ __device__ __forceinline__ void nsf_burst_tile(const NsfBurstCtx& c, NsfBurstCar
             b1n = *reinterpret_cast<const float4*>(c.H0 + ((i + 1) << 8) + (lane << 2));
             b2n = *reinterpret_cast<const float4*>(c.H1 + ((i + 1) << 8) + (lane << 2));
         }
-        if (!(NSF2_ABL & 32)) {
-            a1 = MFMA(hp1[i].x, b1.x, a1); a2 = MFMA(hp2[i].x, b2.x, a2);
-            a1 = MFMA(hp1[i].y, b1.y, a1); a2 = MFMA(hp2[i].y, b2.y, a2);
-        }
+        a1 = MFMA(hp1[i].x, b1.x, a1); a2 = MFMA(hp2[i].x, b2.x, a2);
+        a1 = MFMA(hp1[i].y, b1.y, a1); a2 = MFMA(hp2[i].y, b2.y, a2);
 #pragma unroll
         for (int l = 0; l < CPS; ++l) if ((l & 1) == 0) cload(i * CPS + l);
-        if (!(NSF2_ABL & 32)) {
-            a1 = MFMA(hp1[i].z, b1.z, a1); a2 = MFMA(hp2[i].z, b2.z, a2);
-            a1 = MFMA(hp1[i].w, b1.w, a1); a2 = MFMA(hp2[i].w, b2.w, a2);
-        }
+        a1 = MFMA(hp1[i].z, b1.z, a1); a2 = MFMA(hp2[i].z, b2.z, a2);
+        a1 = MFMA(hp1[i].w, b1.w, a1); a2 = MFMA(hp2[i].w, b2.w, a2);
 #pragma unroll
         for (int l = 0; l < CPS; ++l) if ((l & 1) == 1) cload(i * CPS + l);
         CHAIN_FENCE();
@@ -585,11 +552,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
     const int nTl = __builtin_amdgcn_readfirstlane(m.meta[7]);
     // (measurement only, FM == -1: cycles of the chain wave of workgroup 0 by section, summed over the sweep)
     long long pfv[16];
-#ifdef NSF2_TILE_STAMPS
-    long long* pf = nullptr;
-#else
     long long* pf = (FM == -1 && prof && blockIdx.x == 0) ? pfv : nullptr;
-#endif
     if (FM == -1) for (int i = 0; i < 16; ++i) pfv[i] = 0;
     const int64_t row0 = (int64_t)blockIdx.x * 16;
     float* Y = smem;
@@ -630,20 +593,6 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
     const int vo_T = chain_vo_T(lane);
     const int vo_q = q << 4;
     auto lds_bar = []() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    // (measurement only, a library built with -DNSF2_TILE_STAMPS, FM == -1: when the two wavefronts of workgroup 0 reach and
-    //  leave every barrier -- prof[16 + 4 * barrier + {0, 1} chain, {2, 3} burst]; scripts/profile_nsf2_tiles.py)
-#ifdef NSF2_TILE_STAMPS
-    long long* ts = (FM == -1 && prof && blockIdx.x == 0) ? prof + 16 : nullptr;
-    int bar_no = 0;
-    auto lds_bar_t = [&]() {
-        if (ts && lane == 0) ts[4 * bar_no + 2 * wv] = clock64();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (ts && lane == 0) ts[4 * bar_no + 2 * wv + 1] = clock64();
-        ++bar_no;
-    };
-#else
-    auto lds_bar_t = lds_bar;
-#endif
 
     // per hidden tile 8 words (two rows of "no groups" behind the last tile): the ranks its groups produce (word 0 also
     // the quad pattern << 16), the byte offsets of those ranks' x / y word (walker 0)
@@ -758,7 +707,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
         bc.nT = nT; bc.nXT = nXT; bc.D = D; bc.lane = lane; bc.vo_lane = vo_lane; bc.vo_T = vo_T; bc.vo_q = vo_q;
         bc.H0 = H0; bc.H1 = H1; bc.H2 = H2; bc.ts = nullptr;
         // eager partials of the last two live tiles (NSF2_EAGER_OK)
-        bc.eag = (NSF2_EAGER_OK(&m) && static_tiles && nTl >= 8 && !(NSF2_ABL & 64) && !(m.reserved & 1)) ? 1 : 0;   // (reserved bit 0: launch_nsf2, PMC_NSF2_EAGER=0)
+        bc.eag = (NSF2_EAGER_OK(&m) && static_tiles && nTl >= 8 && !(m.reserved & 1)) ? 1 : 0;   // (reserved bit 0: launch_nsf2, PMC_NSF2_EAGER=0)
         const int eT1 = bc.eag ? nTl - 1 : -1, eT2 = bc.eag ? nTl - 2 : -1;
         bc.ea[0] = EAG; bc.ea[1] = EAG + NSF2_PART_FLOATS;
         {
@@ -838,7 +787,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
                 const int g2_ = __builtin_amdgcn_readfirstlane(tg_.z), g3_ = __builtin_amdgcn_readfirstlane(tg_.w); \
                 NB_FETCH(tb, T1 + 1, N1, N2, NXF, Nz0, Nz1, Nz2)                                                  \
                 f32x4 a0 = as_acc(Bz0), a1 = as_acc(Bz1), a2 = as_acc(Bz2);                                       \
-                if (!(NSF2_ABL & 32)) NB_K(nK, P1, P2, a1, a2)                                                                          \
+                NB_K(nK, P1, P2, a1, a2)                                                                          \
                 nsf_stream2(a1, a2, rs, vo_T, tb + oF1 + T1 * nT * 1024, tb + oF2 + T1 * nT * 1024, NSF2_PK, nK, H0, H1, lane);  /* flows wider than NSF2_PK + 2 tiles */ \
                 _Pragma("unroll") for (int i_ = 0; i_ < NSF2_PX; ++i_) {                                          \
                     if (i_ < nXT) {                                                                               \
@@ -860,16 +809,13 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
                 lds_bar();                                                /* E(T1 - 1) */                         \
             }
             if (static_tiles) {
-                lds_bar_t();                                              // E(-1): the chain solved rank 0
+                lds_bar();                                                // E(-1): the chain solved rank 0
                 bc.tb = tb; bc.X = X;
                 for (int T1 = 1; T1 < nTl; ++T1) {
                     bc.g[0] = bc.gnx[0]; bc.g[1] = bc.gnx[1]; bc.g[2] = bc.gnx[2]; bc.g[3] = bc.gnx[3];      // (the previous tile's "next")
                     set_next(T1 + 1);
                     bc.stg = STG + ((T1 + spar) & 1) * NSF2_STAGE_FLOATS;
                     bc.part = PART + ((T1 + spar) & 1) * NSF2_PART_FLOATS;
-#ifdef NSF2_TILE_STAMPS
-                    bc.ts = ts ? ts + 4 * T * (nTl + 1) + 4 * bar_no : nullptr;       // (behind the barrier stamps: four section stamps per tile)
-#endif
                     switch (T1) {
 #define CASE(K) case K: nsf_burst_tile<K>(bc, carry); break;
 #define CASE_E(K) case K: if (T1 == eT1) nsf_burst_tile<K, 3>(bc, carry); else if (T1 == eT2) nsf_burst_tile<K, 2>(bc, carry); \
@@ -881,7 +827,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
 #undef CASE
                         default: break;
                     }
-                    lds_bar_t();                                          // E(T1 - 1)
+                    lds_bar();                                            // E(T1 - 1)
                 }
                 if (t > 0) first_tile(t - 1, xsel ? XB : XA, spar + nTl);     // (the next transform's x array and parity)
             } else {
@@ -893,7 +839,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
                 const int tbn = (t > 0 ? t - 1 : 0) * blk_bytes;      // the next transform's first operands: on their way before this one ends
                 NB_FETCH(tbn, 0, sA.p1, sA.p2, sA.xf, sA.b0, sA.b1, sA.b2)
             }
-            if (static_tiles) lds_bar_t(); else lds_bar();                // E(nTl - 1)
+            if (static_tiles) lds_bar(); else lds_bar();                  // E(nTl - 1) (two call sites: merged, the compiled kernels change)
             spar = (spar + nTl) & 1;
             if (t == 0) __syncthreads();                                  // (the chain stored the result)
         }
@@ -925,7 +871,6 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
             const int so = tt * blk_bytes + oF3I + (lv ? g : 0) * 2 * nT * 1024;
             const int vp = (lv && Kp >= 0) ? vo_lane : NSF2_OOB, vc = lv ? vo_lane : NSF2_OOB;
             const int kp = Kp >= 0 ? Kp : 0;
-            if (NSF2_ABL & 16) return;
             if constexpr (K == 0) O.fp0 = bload4(rs, vp, so + kp * 1024);
             else if constexpr (K == 1) O.fp1 = bload4(rs, vp, so + (nT + kp) * 1024);
             else if constexpr (K == 2) O.fc0 = bload4(rs, vc, so + Kc * 1024);
@@ -970,7 +915,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
             s.accN1 = s.accN2 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < 4; ++j) s.h2s[j] = 0.0f;
-            lds_bar_t();                                                  // E(-1): the first tile's staging is complete
+            lds_bar();                                                    // E(-1): the first tile's staging is complete
 
             for (int Tt_ = 0; Tt_ < nTl; ++Tt_) {
                 const int Tt = __builtin_amdgcn_readfirstlane(Tt_);
@@ -1036,7 +981,7 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
                     *reinterpret_cast<float4*>(H2 + hw) = make_float4(s.h2s[0], s.h2s[1], s.h2s[2], s.h2s[3]);
                 }
                 NSF_STAMP(8)
-                lds_bar_t();                                 // E(Tt): this tile is final
+                lds_bar();                                   // E(Tt): this tile is final
                 NSF_STAMP(9)
                 fA = fB;
                 NSF_STAMP(10)

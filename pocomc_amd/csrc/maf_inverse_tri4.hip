@@ -105,9 +105,8 @@ __device__ __forceinline__ void prefetch_tile(float4 (&pf1)[PK4], float4 (&pf2)[
     }
 }
 
-// ABL: timing-only ablations (see maf_chain_rot.h); 4 = no bursts, 8 = no chain, 16 = no next-tile prefetch,
-// 32 = no tile-top fragment loads.  FM: 0 = plain inverse of `in`; 4 / 8 / 16 = fused proposal with D <= 4 FM.
-template <int MAXO, int ABL, int FM = 0>
+// FM: 0 = plain inverse of `in`; 4 / 8 / 16 = fused proposal with D <= 4 FM.
+template <int MAXO, int FM = 0>
 __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const float* __restrict__ in,
                                                               float* __restrict__ out,
                                                               float* __restrict__ ladj_out, int64_t n,
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
         // burst fragments of the NEXT tile (filled while the current tile's chain runs)
         float4 pf0[PX4], pf1[PK4], pf2[PK4], pb0, pb1, pb2;
 #define PREFETCH4(TT)                                                                                          \
-        if (!(ABL & 16)) {                                                                                                      \
+        {                                                                                                      \
             const int TT_ = (TT);                                                                              \
             _Pragma("unroll") for (int i_ = 0; i_ < PX4; ++i_)                                                 \
                 if (i_ < nXT) pf0[i_] = bload4(rs, vo_lane, oF0 + (TT_ * nXT + i_) * 1024);                     \
@@ -233,7 +232,6 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
                 f.g[3] = (ny && nz && nw) ? dg.w : D;
             }
             const int soD1 = oF1 + (Tt * nT + Tt) * 1024, soD2 = oF2 + (Tt * nT + Tt) * 1024;
-            if (!(ABL & 32)) {
             f.wt1 = bload4(rs, vo_T, soD1);
             f.wt2 = bload4(rs, vo_T, soD2);
 #pragma unroll
@@ -260,7 +258,6 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
                         rs, q << 2, oW0 + (gg * Hp + 16 * Tt + 4 * jt) * 4, 0));
                 f.w0o[i] = make_float4(w[0], w[1], w[2], w[3]);
             }
-            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) s.yv[i] = Y[lidx(f.g[i] < D ? f.g[i] : 0, p)];
 
@@ -282,7 +279,6 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
                 const float4 b = *reinterpret_cast<const float4*>(X + (Xt << 8) + (lane << 2));
                 a0 = MFMA(a.x, b.x, a0); a0 = MFMA(a.y, b.y, a0); a0 = MFMA(a.z, b.z, a0); a0 = MFMA(a.w, b.w, a0);
             }
-            if (!(ABL & 4))
             switch (Tt < PK4 ? Tt : PK4) {
                 case 1: burst_tile<1>(a1, a2, pf1, pf2, H0, H1, lane); break;
                 case 2: burst_tile<2>(a1, a2, pf1, pf2, H0, H1, lane); break;
@@ -353,9 +349,8 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
             // first group, then the next tile's burst fragments (loads return in order: issued any earlier
             // they would sit between the chain and its own fragments), then the remaining groups
             chain_tile_begin(s, f, X, S, D, q, p, lane);
-            if (!(ABL & 8))
             switch (pat) {
-#define CASE(P) case P: chain_group_rot<P, 0, 1, MAXO, ABL>(s, f, H0, H1, X, Tt, D, nOT, q, p, ladj); break;
+#define CASE(P) case P: chain_group_rot<P, 0, 1, MAXO>(s, f, H0, H1, X, Tt, D, nOT, q, p, ladj); break;
                 CASE(1) CASE(3) CASE(5) CASE(7) CASE(9) CASE(11) CASE(13) CASE(15)
 #undef CASE
             }
@@ -363,9 +358,8 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
                 PREFETCH4(Tt + 1);
                 dg_next = *reinterpret_cast<const int4*>(DGT + 4 * (Tt + 1));
             }
-            if (!(ABL & 8))
             switch (pat) {
-#define CASE(P) case P: chain_group_rot<P, 1, 4, MAXO, ABL>(s, f, H0, H1, X, Tt, D, nOT, q, p, ladj); break;
+#define CASE(P) case P: chain_group_rot<P, 1, 4, MAXO>(s, f, H0, H1, X, Tt, D, nOT, q, p, ladj); break;
                 CASE(3) CASE(5) CASE(7) CASE(9) CASE(11) CASE(13) CASE(15)
 #undef CASE
                 default: break;
@@ -424,11 +418,11 @@ int pmc_launch_inverse_tri4(const pmc_maf_t* m, const float* z, float* x, float*
 #define LAUNCH(MO)                                                                                               \
     {                                                                                                            \
         if (lds > 48 * 1024) {                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri4_kernel<MO, 0>),        \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri4_kernel<MO>),       \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
             if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri4_kernel)");         \
         }                                                                                                        \
-        hipLaunchKernelGGL((maf_inverse_tri4_kernel<MO, 0>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds,      \
+        hipLaunchKernelGGL((maf_inverse_tri4_kernel<MO>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds,        \
                            stream, *m, z, x, ladj, n, ProposeArgs{});                                            \
     }
     if (maxo == 4) LAUNCH(4) else LAUNCH(8)
@@ -469,11 +463,11 @@ int pmc_launch_propose_inverse_tri4(int kind, const float* cur32, const double* 
 #define LAUNCHF(MO, FMV)                                                                                          \
     {                                                                                                             \
         if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri4_kernel<MO, 0, FMV>),    \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri4_kernel<MO, FMV>),   \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
             if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri4_kernel)");          \
         }                                                                                                         \
-        hipLaunchKernelGGL((maf_inverse_tri4_kernel<MO, 0, FMV>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds,  \
+        hipLaunchKernelGGL((maf_inverse_tri4_kernel<MO, FMV>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds,    \
                            stream, *m, (const float*)nullptr, x, ladj, n, pa);                                    \
     }
     if (m->D <= 16) { if (maxo == 4) LAUNCHF(4, 4) else LAUNCHF(8, 4) }
@@ -511,12 +505,6 @@ int pmc_launch_propose_inverse_tri4(int kind, const float* cur32, const double* 
 // splits larger calls into rounds of this kernel (two rounds still beat the lone wave's one: DESIGN.md section 4).
 // ============================================================================================================
 #define TRI5_NC 1                  // chain waves (16-walker sets) per workgroup
-#ifndef TRI5_ABL
-#define TRI5_ABL 0                 // timing experiments only (scripts/abl_tri5.sh): results are wrong when != 0
-#endif
-#if TRI5_ABL != 0
-extern "C" int pmc_ablation_tri5(void) { return TRI5_ABL; }      // (see pmc_ablation_tri6)
-#endif
 #define PXB 4                      // x tiles of the layer-0 product held in registers (D <= 64)
 #define TRI5_STAGE_FLOATS(MO) ((3 + (MO)) * 256)                 // one staging buffer: S0 | S1 | S2 (transposed, [lane][4]) | SO[MO] (natural)
 #define TRI5_SET_FLOATS(Dp, Hp, MO) (2 * (Dp) * 16 + 2 * (Hp) * 16 + 2 * 256 + 2 * TRI5_STAGE_FLOATS(MO))
@@ -921,8 +909,7 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
                     constexpr int LPS = (16 + NSH - 1) / NSH, k0 = (G * 3 + HP) * LPS;
                     auto into = [&](ChainFrags<MAXO>& F, auto k_) { request(F, k_, ntt, nU, gU, gV); };
                     using std::integral_constant;
-                    if constexpr ((TRI5_ABL & 0x100) != 0) {
-                    } else if constexpr (FAST && NG_ == 4) {
+                    if constexpr (FAST && NG_ == 4) {
                         // the common tile: the layer-0 window columns of a group die with the group, so the next tile's go
                         // straight into the CURRENT set once it has run; only what lives to the tile's end is buffered
                         // (and copied over at the boundary: 7 of 13 operands)
@@ -942,11 +929,11 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
                     }
                 };
                 if (pf && lane == 0) pf[1] = clock64();
-                if constexpr (FAST || (TRI5_ABL & 0x200) != 0) {   // four single-quad groups: the common tile
-                    chain_group_rot<15, 0, 4, MAXO, TRI5_ABL | 11>(s, cur, H0, H1, X, Tt, D, nOT, q, p, ladj, H2, ahead);
+                if constexpr (FAST) {   // four single-quad groups: the common tile
+                    chain_group_rot<15, 0, 4, MAXO, CHAIN_TWO_WAVE>(s, cur, H0, H1, X, Tt, D, nOT, q, p, ladj, H2, ahead);
                 } else
                 switch (pat) {
-#define CASE(P) case P: chain_group_rot<P, 0, 4, MAXO, TRI5_ABL | 11>(s, cur, H0, H1, X, Tt, D, nOT, q, p, ladj, H2, ahead); break;
+#define CASE(P) case P: chain_group_rot<P, 0, 4, MAXO, CHAIN_TWO_WAVE>(s, cur, H0, H1, X, Tt, D, nOT, q, p, ladj, H2, ahead); break;
                     CASE(1) CASE(3) CASE(5) CASE(7) CASE(9) CASE(11) CASE(13) CASE(15)
 #undef CASE
                     default: break;
@@ -961,7 +948,7 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
             // Runs of common tiles are a loop of their own: a tile body that joins the other patterns' bodies pays for it
             // with ~45 register copies per join (every register a body updates becomes a conditional assignment), per tile.
             for (int Tt = 0; Tt < nTl;) {
-                while (Tt < nTl && __builtin_amdgcn_readfirstlane(fA.pat) == 15 && !(TRI5_ABL & 0x100)) {
+                while (Tt < nTl && __builtin_amdgcn_readfirstlane(fA.pat) == 15) {
                     tile(fA, fB, Tt, std::true_type{});
                     // (the window columns were requested in place)
                     fA.wt1 = fB.wt1; fA.wt2 = fB.wt2; fA.wn1 = fB.wn1; fA.wn2 = fB.wn2;

@@ -44,14 +44,6 @@
 
 typedef unsigned int u32x2_t6 __attribute__((ext_vector_type(2)));
 
-#ifndef TRI6_ABL
-#define TRI6_ABL 0                 // timing experiments only (scripts/abl_tri6.sh): results are wrong when != 0
-#endif
-#if TRI6_ABL != 0
-// marks a library built with an ablation: pocomc_amd/_lib.py refuses it unless PMC_ALLOW_ABLATION is set
-extern "C" int pmc_ablation_tri6(void) { return TRI6_ABL; }
-#endif
-
 namespace tri6 {
 
 using ::bload4;                    // (maf_common.h)
@@ -160,9 +152,7 @@ template <int HB> struct Ops {
 template <int HB>
 __device__ __forceinline__ void store_quad16(float* H, int T, int c, int p, const f32x4& v) {
     uint2 w;
-    if constexpr ((TRI6_ABL & 2) != 0) {
-        w.x = __float_as_uint(v[0]); w.y = __float_as_uint(v[2]);
-    } else if constexpr (HB == 1) {
+    if constexpr (HB == 1) {
         const b16x2_t6 a = __builtin_convertvector(f32x2_t6{v[0], v[1]}, b16x2_t6), b = __builtin_convertvector(f32x2_t6{v[2], v[3]}, b16x2_t6);
         w.x = *reinterpret_cast<const unsigned*>(&a); w.y = *reinterpret_cast<const unsigned*>(&b);
     } else {
@@ -193,7 +183,7 @@ __device__ __forceinline__ void publish(int* flags, int which, int value) {
 // LDS instruction in front of every DS operation of the chain (measured: chain tile 4.3 k -> 5.3 k cycles)
 template <bool NAP = false>
 __device__ __forceinline__ void wait_for(const int* flags, int which, int value) {
-    while (peek(flags, which) < value) { if constexpr (NAP && !(TRI6_ABL & 8)) __builtin_amdgcn_s_sleep(1); }
+    while (peek(flags, which) < value) { if constexpr (NAP) __builtin_amdgcn_s_sleep(1); }
     asm volatile("" ::: "memory");
 }
 
@@ -214,7 +204,7 @@ struct ChainState {
 template <int HB>
 __device__ __forceinline__ void store_x(float* A, float* X16, int g, int p, float v) {
     A[lidx(g, p)] = v;
-    if constexpr (HB != 0 && !(TRI6_ABL & 1)) {
+    if constexpr (HB != 0) {
         unsigned short h;
         if constexpr (HB == 1) { const __bf16 b = (__bf16)v; h = *reinterpret_cast<const unsigned short*>(&b); }
         else { const _Float16 b = (_Float16)v; h = *reinterpret_cast<const unsigned short*>(&b); }
@@ -233,25 +223,13 @@ __device__ __forceinline__ void tile_groups(const int4& dg, int D, int (&g)[4]) 
 // Speculative hand-over read: the word and the staged data are read in ONE LDS round trip (DS operations of a wave
 // execute in order and the writer stored the data before the word, so data read after a word that already shows
 // `value` are the staged ones); only if the word is behind does the wave poll and read again.
-#if (TRI6_ABL & 32)
-__device__ unsigned long long g_tri6_wait[2 * F_COUNT];      // measurement build: [word] cycles the chain of workgroup 0 waited, [F_COUNT + word] times
-#endif
 template <class LOAD>
 __device__ __forceinline__ void take(const int* flags, int which, int value, LOAD&& load) {
     const int seen = peek(flags, which);
     load();
     asm volatile("" ::: "memory");
     if (seen < value) {
-#if (TRI6_ABL & 32)
-        const long long t0 = clock64();
-#endif
         wait_for(flags, which, value);
-#if (TRI6_ABL & 32)
-        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
-            atomicAdd(&g_tri6_wait[which], (unsigned long long)(clock64() - t0));
-            atomicAdd(&g_tri6_wait[F_COUNT + which], 1ull);
-        }
-#endif
         load();
     }
 }
@@ -796,7 +774,7 @@ __global__ __launch_bounds__(64 * NW, (FM == 0 && (NS == 1 || (NS == 2 && HB != 
             // the hidden layer 2's: its row is staged when the chain starts the tile, and it idles from there until the tile's h1
             // is final, while the output wavefront (a tile's output partials, then a new output tile's whole row) is the one the
             // chain waits for (measured: 6.5-8.5 k cycles per iteration against the chain's 5.5 k)
-            constexpr int P0W = NW == 5 ? 4 : ((HB && !(TRI6_ABL & 4)) ? 2 : 3);
+            constexpr int P0W = NW == 5 ? 4 : (HB ? 2 : 3);
             if (wv == P0W) {
                 // layer-0 partial of tile 0: bias only (cut = 0)
                 const float4 b0 = bload4(rs, vo_q, oB0);
@@ -1193,15 +1171,6 @@ extern "C" int pmc_maf_pack_lane16(const pmc_maf_t* m, int fmt, uint16_t* image,
     hipLaunchKernelGGL(pack_lane16_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, *m, fmt, image);
     return pmc_check_launch("pack_lane16_kernel");
 }
-
-#if (TRI6_ABL & 32)
-// measurement build only (scripts/abl_tri6.sh 32): out[2 F_COUNT] <- cycles / times the chain wavefront of workgroup 0 waited per word, then reset
-extern "C" int pmc_debug_tri6_waits(unsigned long long* out) {
-    unsigned long long z[2 * tri6::F_COUNT] = {};
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(tri6::g_tri6_wait), sizeof(z)) != hipSuccess) return 1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(tri6::g_tri6_wait), z, sizeof(z)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // whether PMC_INVERSE_AUTO (and with it the MCMC step) takes this sweep for the flow (bench.py names the kernel it times)
 extern "C" int pmc_maf_inverse_auto_is_lane(const pmc_maf_t* m) {

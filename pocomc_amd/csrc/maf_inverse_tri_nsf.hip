@@ -27,13 +27,7 @@
 #define NPX 2     // x tiles prefetched per hidden tile
 #define NPK 8     // K tiles prefetched per hidden tile and layer
 #define NPO 10    // K tiles of the rank's two output tiles prefetched per group
-#ifndef NSF_ABL
-#define NSF_ABL 0 // timing-only builds (scripts/abl_nsf.sh)
-#endif
 
-// ABL (timing experiments only, wrong results): 1 = no spline solve, 2 = no output product, 4 = no hidden chain,
-// 8 = no per-rank output fragment loads
-template <int ABL>
 __global__ __launch_bounds__(64) void maf_inverse_tri_nsf_kernel(pmc_maf_t m, const float* __restrict__ in,
                                                                  float* __restrict__ out,
                                                                  float* __restrict__ ladj_out, int64_t n) {
@@ -73,8 +67,7 @@ __global__ __launch_bounds__(64) void maf_inverse_tri_nsf_kernel(pmc_maf_t m, co
             *reinterpret_cast<float4*>(pr_ + 16) = make_float4(OA1[0], OA1[1], OA1[2], OA1[3]);         \
             WAVE_LDS_FENCE();                                                                           \
             float xv_, l_;                                                                              \
-            if (ABL & 1) { xv_ = Y[lidx((G), p)] + PAR[(p << 5)] + PAR[(p << 5) + 22]; l_ = PAR[(p << 5) + 8]; } \
-            else rqs_inverse_coop(PAR + (p << 5), TAB + p * 24, q, Y[lidx((G), p)], xv_, l_);           \
+            rqs_inverse_coop(PAR + (p << 5), TAB + p * 24, q, Y[lidx((G), p)], xv_, l_);                \
             if (q == 0) { X[lidx((G), p)] = xv_; ladj -= l_; }                                          \
             WAVE_LDS_FENCE();                                                                           \
         }
@@ -166,15 +159,12 @@ __global__ __launch_bounds__(64) void maf_inverse_tri_nsf_kernel(pmc_maf_t m, co
                 // in flight while the hidden chain of the group runs
                 float4 po0[NPO], po1[NPO];
                 const float4* fo_ = w.f3i + ((size_t)g * 2 * nT) * 64 + lane;
-                if (!(ABL & 8)) {
 #pragma unroll
                 for (int i = 0; i < NPO; ++i)
                     if (i <= Tt) { po0[i] = fo_[i * 64]; po1[i] = fo_[(nT + i) * 64]; }
-                }
                 f32x4 o0 = bias4(w.b3i, 32 * g + 4 * q), o1 = bias4(w.b3i, 32 * g + 16 + 4 * q);
 
                 f32x4 h0, h1, h2;
-                if (!(ABL & 4)) {
                 for (int r = 0; r < 4; ++r) h0[r] = fmaxf(a0[r], 0.0f);
                 if (mine) store_rows(H0, Tt, q, p, h0);
                 WAVE_LDS_FENCE();
@@ -186,10 +176,8 @@ __global__ __launch_bounds__(64) void maf_inverse_tri_nsf_kernel(pmc_maf_t m, co
                 for (int r = 0; r < 4; ++r) h2[r] = fmaxf(a2[r] + h1[r], 0.0f);
                 if (mine) store_rows(H2, Tt, q, p, h2);
                 WAVE_LDS_FENCE();
-                }
 
                 // ---- the 23 spline parameters of rank g: left-looking over the final h2 tiles
-                if (!(ABL & 2)) {
                 // (dealing the K < Tt part of this product into the hops of the chain above was measured: the
                 // in-order queue then delays the chain's own dependent MFMAs -- 6 us slower)
 #pragma unroll
@@ -205,7 +193,6 @@ __global__ __launch_bounds__(64) void maf_inverse_tri_nsf_kernel(pmc_maf_t m, co
                 for (int K = NPO; K <= Tt; ++K) {
                     o0 = tile_mac(o0, w.f3i + ((size_t)g * 2 * nT) * 64, H2, K, lane);
                     o1 = tile_mac(o1, w.f3i + ((size_t)g * 2 * nT + nT) * 64, H2, K, lane);
-                }
                 }
                 SOLVE_RANK(g, o0, o1)
                 const float xg = X[lidx(g, p)];
@@ -233,12 +220,12 @@ int pmc_launch_inverse_tri_nsf(const pmc_maf_t* m, const float* z, float* x, flo
     if (lds > 160 * 1024) return pmc_fail("pmc_maf_inverse: flow too wide for one wave's LDS budget (160 KiB)");
     static size_t lds_set = 0;
     if (lds > 48 * 1024 && lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri_nsf_kernel<NSF_ABL>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri_nsf_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri_nsf_kernel)");
         lds_set = lds;
     }
-    hipLaunchKernelGGL(maf_inverse_tri_nsf_kernel<NSF_ABL>, dim3((unsigned)((n + 15) / 16)), dim3(64), lds, stream, *m, z, x,
+    hipLaunchKernelGGL(maf_inverse_tri_nsf_kernel, dim3((unsigned)((n + 15) / 16)), dim3(64), lds, stream, *m, z, x,
                        ladj, n);
     return pmc_check_launch("maf_inverse_tri_nsf_kernel");
 }
