@@ -1,7 +1,12 @@
 """Headline benchmark: flow-preconditioned MCMC steps/s (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` if asked and prints the headline line.
+``--full`` adds what the headline does not need, all of it behind the timed region: the >= 200-step steady state,
+the host-timer and instrumented passes behind the per-kernel roofline and breakdowns, the resample / gather sweeps,
+the config-5 flow sub-metric and the CPU baseline.
 
 Workload (``config.workload``): the tpCN kernel of ``pocomc/mcmc.py:8-183`` on the
 32-D Rosenbrock likelihood (``README.md:53-55``), prior U(-10,10)^32, 10 000 walkers per
@@ -272,8 +277,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--particles", type=int, default=10000, help="walkers per GPU")
     ap.add_argument("--dim", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-flow-bench", action="store_true", help="skip the config-5 flow sub-metric (f32 vs bf16 log_prob)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline after the timed steps: steady state, roofline and host "
+                         "breakdowns, resample / gather sweeps, the config-5 flow sub-metric, the CPU baseline "
+                         "(default: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-flow-bench", action="store_true",
+                    help="with --full: skip the config-5 flow sub-metric (f32 vs bf16 log_prob)")
     ap.add_argument("--host-threads", type=int, default=1, help="host threads evaluating the prior/likelihood")
     ap.add_argument("--host-prefetch", type=int, default=1,
                     help="helper threads that warm the cache with x' for the likelihood (csrc/host_prefetch.hip; they run "
@@ -284,7 +294,7 @@ def main():
     ap.add_argument("--x-order", choices=["C", "F"], default="F",
                     help="memory order of the (n, D) array handed to the host prior/likelihood")
     ap.add_argument("--no-steady-state", action="store_true",
-                    help="skip the second closed region of >= 200 steps (side key steady_state)")
+                    help="with --full: skip the second closed region of >= 200 steps (side key steady_state)")
     ap.add_argument("--event-every", type=int, default=10,
                     help="record the HIP event pair around the flow-inverse launch on every k-th timed step (an event "
                          "pair per step costs ~5 %% of the step rate: it splits the pre-phase's back-to-back launches)")
@@ -668,10 +678,11 @@ def main():
     # the host clocks of the K timed steps, taken HERE: the steady-state loop below adds to the same accumulators (round 5
     # divided their sum over K + 200 steps by K: step_call read 11x a step)
     seg_region = dict(t_lseg if leng is not None else t_seg)
-    # ---- the same closed region once more over >= 200 steps (side key "steady_state": the exposed first pre-step is
-    #      1 / K of the region, 5 % of it at the driver's K = 20 and 0.5 % here)
+    # ---- from here on a plain run does only what its line needs; --full measures the rest, starting with the same
+    #      closed region once more over >= 200 steps (side key "steady_state": the exposed first pre-step is 1 / K of
+    #      the region, 5 % of it at the driver's K = 20 and 0.5 % here)
     roof_eng._step.ev_inv0, roof_eng._step.ev_inv1 = None, None
-    n_ss = 0 if args.no_steady_state else max(200, args.steps)
+    n_ss = max(200, args.steps) if (args.full and not args.no_steady_state) else 0
     dt_ss = None
     if n_ss:
         if step_times is not None:
@@ -703,7 +714,7 @@ def main():
         if os.environ.get("PMC_BENCH_STEP_TIMES"):
             step_times = step_times_k
     gc.enable()
-    if leng is not None and pipelined:
+    if args.full and leng is not None and pipelined:
         leng.resume_pipeline(nu)                                 # (the passes below step on: their first pre-steps)
     if step_times is not None and rank == 0:
         st_ = np.diff(np.array([t0] + step_times)) * 1e6
@@ -720,333 +731,337 @@ def main():
     roof_eng._step.ev_inv0, roof_eng._step.ev_inv1 = None, None
     seg_timed = {k: v / args.steps * 1e6 for k, v in seg_region.items()}
     laned_host = None
-    if leng is not None:                                    # same pipeline again with host timers
-        leng.host_timers = {"wait_device": 0.0, "prior": 0.0, "likelihood": 0.0}
-        for k in t_lseg:
-            t_lseg[k] = 0.0
-        n_lt = max(20, min(args.steps, 100))
-        leng.pipeline_stats(reset=True)
-        for _ in range(n_lt):
-            step_laned()
-        torch.cuda.synchronize()
-        laned_host = {**{k: v / n_lt * 1e6 for k, v in leng.host_timers.items()},
-                      **{k: v / n_lt * 1e6 for k, v in t_lseg.items()}}
-        ps = leng.pipeline_stats(reset=True)
-        if ps is not None:
-            # the lane pipeline behind the C ABI keeps its own clocks: waits (completion words of x' and of the sums) and
-            # the time it spends enqueuing; what is left of a step call is the interpreter
-            laned_host["wait_device"] = (ps["wait_x"] + ps["wait_sums"]) / n_lt * 1e6
-            laned_host["wait_x"] = ps["wait_x"] / n_lt * 1e6
-            laned_host["wait_sums"] = ps["wait_sums"] / n_lt * 1e6
-            laned_host["enqueue_accept"] = ps["enqueue_accept"] / n_lt * 1e6
-            laned_host["enqueue_next_pre"] = ps["enqueue_next_pre"] / n_lt * 1e6
-            laned_host["pipeline"] = "pmc_pipeline_next (C ABI)"
-        laned_host["python_overhead"] = (laned_host["step_call"] - laned_host["likelihood"] - laned_host["prior"]
-                                         - laned_host["wait_device"] - laned_host.get("enqueue_accept", 0.0)
-                                         - laned_host.get("enqueue_next_pre", 0.0) - laned_host.get("enqueue_adapt", 0.0)
-                                         - laned_host.get("wait_sums", 0.0))
-        leng.host_timers = None
-        if os.environ.get("PMC_BENCH_EPI_STAMPS") and rank == 0 and not hasattr(lib, "pmc_debug_set_epilogue_stamps"):
-            print("[epilogue stamps] this library was built without the measurement hooks: make -C pocomc_amd/csrc clean all DEBUG_HOOKS=1",
-                  file=sys.stderr)
-        elif os.environ.get("PMC_BENCH_EPI_STAMPS") and rank == 0:
-            # measurement only: where the fused launch of lane 0 spends its epilogue (100 MHz stamps per workgroup)
-            import ctypes
-            nb = (leng.lanes[0].n + 15) // 16
-            stamps = torch.zeros(nb, 8, dtype=torch.int64, device="cuda")
-            fn = lib.pmc_debug_set_epilogue_stamps
-            fn.restype, fn.argtypes = None, [ctypes.c_void_p, ctypes.c_int64]
-            fn(stamps.data_ptr(), leng.lanes[0].n)
-            for _ in range(3):
+    if args.full:
+        if leng is not None:                                    # same pipeline again with host timers
+            leng.host_timers = {"wait_device": 0.0, "prior": 0.0, "likelihood": 0.0}
+            for k in t_lseg:
+                t_lseg[k] = 0.0
+            n_lt = max(20, min(args.steps, 100))
+            leng.pipeline_stats(reset=True)
+            for _ in range(n_lt):
                 step_laned()
             torch.cuda.synchronize()
-            fn(None, 0)
-            st = stamps.cpu().numpy()
-            t0_ = st[:, 6].min()
-            us_ = lambda a: (a - t0_) / 100.0
-            names = ["epilogue entry", "elements done", "rows entry", "before x' stores", "x' stores issued",
-                     "fence passed", "kernel entry"]
-            for sel, nm in ((slice(0, nb), "blocks"),):
-                for i in (6, 0, 1, 2, 3, 4, 5):
-                    v = us_(st[sel, i])
-                    print(f"[epilogue stamps] {nm:12s} {names[i]:42s} min {v.min():7.1f} median {np.median(v):7.1f} p90 {np.percentile(v, 90):7.1f} max {v.max():7.1f} us", file=sys.stderr)
-            cu = st[:, 7] & 0xffffffff
-            xcc = (st[:, 7] >> 32) & 0xf
-            key = (xcc << 16) | ((cu >> 8) & 0xff) | (((cu >> 13) & 7) << 8)       # (xcc, se, sh+cu)
-            uniq, cnt = np.unique(key, return_counts=True)
-            late = us_(st[:, 0])
-            per = {k: c for k, c in zip(uniq, cnt)}
-            solo = np.array([per[k] == 1 for k in key])
-            print(f"[epilogue stamps] CUs used {len(uniq)}, blocks {nb}; sweep end (epilogue entry) median: blocks alone on their CU "
-                  f"{np.median(late[solo]) if solo.any() else float('nan'):.1f} us, blocks sharing a CU {np.median(late[~solo]) if (~solo).any() else float('nan'):.1f} us",
-                  file=sys.stderr)
-        if pipelined:
-            leng.finish_pipeline()
-    inv_us_live = (float(np.mean([lib.pmc_event_elapsed_ms(a, b) for a, b in ev_used])) * 1e3 if ev_used else None)
-    # the same launch without the scaler epilogue (pmc_step_t.no_fuse bit 1: the scaler as a launch of its own), a few
-    # untimed steps: what the sweep alone takes -- side key of the roofline object
-    inv_us_sweep_only = None
-    scaler_epilogue = int(roof_eng._step.no_fuse) & 3 == 0
-    if scaler_epilogue:
-        roof_eng._step.no_fuse = int(roof_eng._step.no_fuse) | 2
-        extra = [(lib.pmc_event_create(), lib.pmc_event_create()) for _ in range(10)]
-        for pair in extra:
-            roof_eng._step.ev_inv0, roof_eng._step.ev_inv1 = pair
-            timed_step()
+            laned_host = {**{k: v / n_lt * 1e6 for k, v in leng.host_timers.items()},
+                          **{k: v / n_lt * 1e6 for k, v in t_lseg.items()}}
+            ps = leng.pipeline_stats(reset=True)
+            if ps is not None:
+                # the lane pipeline behind the C ABI keeps its own clocks: waits (completion words of x' and of the sums) and
+                # the time it spends enqueuing; what is left of a step call is the interpreter
+                laned_host["wait_device"] = (ps["wait_x"] + ps["wait_sums"]) / n_lt * 1e6
+                laned_host["wait_x"] = ps["wait_x"] / n_lt * 1e6
+                laned_host["wait_sums"] = ps["wait_sums"] / n_lt * 1e6
+                laned_host["enqueue_accept"] = ps["enqueue_accept"] / n_lt * 1e6
+                laned_host["enqueue_next_pre"] = ps["enqueue_next_pre"] / n_lt * 1e6
+                laned_host["pipeline"] = "pmc_pipeline_next (C ABI)"
+            laned_host["python_overhead"] = (laned_host["step_call"] - laned_host["likelihood"] - laned_host["prior"]
+                                             - laned_host["wait_device"] - laned_host.get("enqueue_accept", 0.0)
+                                             - laned_host.get("enqueue_next_pre", 0.0) - laned_host.get("enqueue_adapt", 0.0)
+                                             - laned_host.get("wait_sums", 0.0))
+            leng.host_timers = None
+            if os.environ.get("PMC_BENCH_EPI_STAMPS") and rank == 0 and not hasattr(lib, "pmc_debug_set_epilogue_stamps"):
+                print("[epilogue stamps] this library was built without the measurement hooks: make -C pocomc_amd/csrc clean all DEBUG_HOOKS=1",
+                      file=sys.stderr)
+            elif os.environ.get("PMC_BENCH_EPI_STAMPS") and rank == 0:
+                # measurement only: where the fused launch of lane 0 spends its epilogue (100 MHz stamps per workgroup)
+                import ctypes
+                nb = (leng.lanes[0].n + 15) // 16
+                stamps = torch.zeros(nb, 8, dtype=torch.int64, device="cuda")
+                fn = lib.pmc_debug_set_epilogue_stamps
+                fn.restype, fn.argtypes = None, [ctypes.c_void_p, ctypes.c_int64]
+                fn(stamps.data_ptr(), leng.lanes[0].n)
+                for _ in range(3):
+                    step_laned()
+                torch.cuda.synchronize()
+                fn(None, 0)
+                st = stamps.cpu().numpy()
+                t0_ = st[:, 6].min()
+                us_ = lambda a: (a - t0_) / 100.0
+                names = ["epilogue entry", "elements done", "rows entry", "before x' stores", "x' stores issued",
+                         "fence passed", "kernel entry"]
+                for sel, nm in ((slice(0, nb), "blocks"),):
+                    for i in (6, 0, 1, 2, 3, 4, 5):
+                        v = us_(st[sel, i])
+                        print(f"[epilogue stamps] {nm:12s} {names[i]:42s} min {v.min():7.1f} median {np.median(v):7.1f} p90 {np.percentile(v, 90):7.1f} max {v.max():7.1f} us", file=sys.stderr)
+                cu = st[:, 7] & 0xffffffff
+                xcc = (st[:, 7] >> 32) & 0xf
+                key = (xcc << 16) | ((cu >> 8) & 0xff) | (((cu >> 13) & 7) << 8)       # (xcc, se, sh+cu)
+                uniq, cnt = np.unique(key, return_counts=True)
+                late = us_(st[:, 0])
+                per = {k: c for k, c in zip(uniq, cnt)}
+                solo = np.array([per[k] == 1 for k in key])
+                print(f"[epilogue stamps] CUs used {len(uniq)}, blocks {nb}; sweep end (epilogue entry) median: blocks alone on their CU "
+                      f"{np.median(late[solo]) if solo.any() else float('nan'):.1f} us, blocks sharing a CU {np.median(late[~solo]) if (~solo).any() else float('nan'):.1f} us",
+                      file=sys.stderr)
+            if pipelined:
+                leng.finish_pipeline()
+        inv_us_live = (float(np.mean([lib.pmc_event_elapsed_ms(a, b) for a, b in ev_used])) * 1e3 if ev_used else None)
+        # the same launch without the scaler epilogue (pmc_step_t.no_fuse bit 1: the scaler as a launch of its own), a few
+        # untimed steps: what the sweep alone takes -- side key of the roofline object
+        inv_us_sweep_only = None
+        scaler_epilogue = int(roof_eng._step.no_fuse) & 3 == 0
+        if scaler_epilogue:
+            roof_eng._step.no_fuse = int(roof_eng._step.no_fuse) | 2
+            extra = [(lib.pmc_event_create(), lib.pmc_event_create()) for _ in range(10)]
+            for pair in extra:
+                roof_eng._step.ev_inv0, roof_eng._step.ev_inv1 = pair
+                timed_step()
+            torch.cuda.synchronize()
+            roof_eng._step.ev_inv0, roof_eng._step.ev_inv1 = None, None
+            roof_eng._step.no_fuse = int(roof_eng._step.no_fuse) & ~2
+            inv_us_sweep_only = float(np.mean([lib.pmc_event_elapsed_ms(a, b) for a, b in extra[2:]])) * 1e3
+            for a, b in extra:
+                lib.pmc_event_destroy(a); lib.pmc_event_destroy(b)
+        # ---- composite path again with host timers only (no HIP events): where the host thread's time goes
+        eng.host_timers = {"wait_device": 0.0, "prior": 0.0, "likelihood": 0.0}
+        for k in t_seg:
+            t_seg[k] = 0.0
+        n_ht = max(20, min(args.steps, 100))
+        for _ in range(n_ht):
+            step()
         torch.cuda.synchronize()
-        roof_eng._step.ev_inv0, roof_eng._step.ev_inv1 = None, None
-        roof_eng._step.no_fuse = int(roof_eng._step.no_fuse) & ~2
-        inv_us_sweep_only = float(np.mean([lib.pmc_event_elapsed_ms(a, b) for a, b in extra[2:]])) * 1e3
-        for a, b in extra:
-            lib.pmc_event_destroy(a); lib.pmc_event_destroy(b)
+        composite_host = {**{k: v / n_ht * 1e6 for k, v in eng.host_timers.items()},
+                          **{k: v / n_ht * 1e6 for k, v in t_seg.items()}}
+        # ---- instrumented pass (same steps, fine-grained entry points + HIP events + host timers):
+        #      per-kernel durations for the roofline object and the host/device breakdown
+        eng.events = []
+        eng.host_timers = {"wait_device": 0.0, "prior": 0.0, "likelihood": 0.0}
+        t_host[0] = 0.0
+        for k in t_seg:
+            t_seg[k] = 0.0
+        n_inst = max(20, min(args.steps, 100))
+        ti0 = time.perf_counter()
+        for _ in range(n_inst):
+            step()
+        torch.cuda.synchronize()
+        dt_inst = time.perf_counter() - ti0
     for a, b in ev_pairs:
         lib.pmc_event_destroy(a); lib.pmc_event_destroy(b)
-    # ---- composite path again with host timers only (no HIP events): where the host thread's time goes
-    eng.host_timers = {"wait_device": 0.0, "prior": 0.0, "likelihood": 0.0}
-    for k in t_seg:
-        t_seg[k] = 0.0
-    n_ht = max(20, min(args.steps, 100))
-    for _ in range(n_ht):
-        step()
-    torch.cuda.synchronize()
-    composite_host = {**{k: v / n_ht * 1e6 for k, v in eng.host_timers.items()},
-                      **{k: v / n_ht * 1e6 for k, v in t_seg.items()}}
-    # ---- instrumented pass (same steps, fine-grained entry points + HIP events + host timers):
-    #      per-kernel durations for the roofline object and the host/device breakdown
-    eng.events = []
-    eng.host_timers = {"wait_device": 0.0, "prior": 0.0, "likelihood": 0.0}
-    t_host[0] = 0.0
-    for k in t_seg:
-        t_seg[k] = 0.0
-    n_inst = max(20, min(args.steps, 100))
-    ti0 = time.perf_counter()
-    for _ in range(n_inst):
-        step()
-    torch.cuda.synchronize()
-    dt_inst = time.perf_counter() - ti0
     blas_limit.restore_original_limits()
     if bufsize0 is not None:
         np.setbufsize(bufsize0)
     if pinned_core is not None:
         os.sched_setaffinity(0, affinity0)
-    per_rank = None
+    spec = flow.spec
     if world > 1:
         tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        # every rank's own clocks, so that a multi-GPU line explains itself: wait_sums is the host's wait for the closing
-        # launch of a step -- at world > 1 that launch holds the exchange (comm_adapt_kernel polls the peers' sequence words),
-        # so a rank that waits longer there than the others waited for a LATE PEER, not for its own device
-        mine = {"rank": rank, "device": torch.cuda.current_device(), "pinned_core": pinned_core, "timed_region_s": dt_local,
-                **{k: (laned_host or {}).get(k) for k in ("wait_x", "wait_sums", "likelihood", "enqueue_accept", "enqueue_next_pre",
-                                                           "python_overhead", "step_call")}}
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
+    per_rank = None
+    if args.full:
+        if world > 1:
+            # every rank's own clocks, so that a multi-GPU line explains itself: wait_sums is the host's wait for the closing
+            # launch of a step -- at world > 1 that launch holds the exchange (comm_adapt_kernel polls the peers' sequence words),
+            # so a rank that waits longer there than the others waited for a LATE PEER, not for its own device
+            mine = {"rank": rank, "device": torch.cuda.current_device(), "pinned_core": pinned_core, "timed_region_s": dt_local,
+                    **{k: (laned_host or {}).get(k) for k in ("wait_x", "wait_sums", "likelihood", "enqueue_accept", "enqueue_next_pre",
+                                                               "python_overhead", "step_call")}}
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
 
-    # ---- per-kernel device times from the HIP events recorded inside the timed region
-    ev = eng.events
-    seg = lambda a, b: float(np.mean([e[a].elapsed_time(e[b]) for e in ev])) * 1e3     # us
-    us = {"propose": seg(0, 1), "maf_inverse": seg(1, 2), "scaler_inverse": seg(2, 3), "d2h_x": seg(3, 4),
-          "accept_reduce": seg(5, 6)}
-    spec = flow.spec
-    n_launch = roof_eng.n                                         # walkers of the launch the event pair brackets
-    algo_flops = n_launch * spec.flops_inverse_naive()            # (D+1)*F_fwd per walker
-    actual_flops = n_launch * 2 * spec.macs_masked()              # what the triangular sweep needs
-    if inv_us_live is None:
-        inv_us_live = us["maf_inverse"]                     # (--steps 1 --no-steady-state: the instrumented pass's figure)
-    us["maf_inverse_timed_region"] = inv_us_live            # HIP events inside the timed region
-    t_inv = inv_us_live * 1e-6
-    lane_auto = args.inverse in ("auto", "triangular") and bool(lib.pmc_maf_inverse_auto_is_lane(ctypes.byref(flow._desc)))
-    nsf2 = spec.univariate == "rqs" and bool(lib.pmc_maf_inverse_auto_is_nsf2(ctypes.byref(flow._desc)))
-    fused = (eng.pre and spec.tri_ok and not lane_auto and args.inverse in ("auto", "triangular")
-             and ((spec.univariate == "affine" and spec.nOT <= 8) or nsf2))
-    duo = bool(lib.pmc_maf_inverse_auto_is_duo(ctypes.byref(flow._desc), n_launch))
-    roof_kernel = ("maf_dense_kernel<1>" if (args.inverse == "naive" or not spec.tri_ok) else
-                   "maf_inverse_nsf2_kernel" if (nsf2 and args.inverse in ("auto", "triangular", "duo")) else
-                   "maf_inverse_tri_nsf_kernel" if spec.univariate == "rqs" else
-                   "maf_inverse_tri6_kernel" if (args.inverse == "lane" or lane_auto or os.environ.get("PMC_INVERSE_LANE", "0") != "0") else
-                   "maf_inverse_tri4_kernel" if args.inverse == "solo" else
-                   "maf_inverse_tri5_kernel" if (args.inverse == "duo" or duo) else "maf_inverse_tri4_kernel")
-    # HBM bytes per launch of the dominant kernel: PMC passes cannot run inside this process; the value is the
-    # committed rocprofv3 measurement of this very command (scripts/collect_profile.sh -> profiles/*_traffic.json),
-    # used only when it was taken on the kernel sources this run was built from (their hash is stored with it) and
-    # for the same kernel / walkers per launch -- otherwise null
-    traffic = None
-    try:
-        src_hash = kernel_source_hash(ROOT)
-        for cand in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")), reverse=True):
-            pm = json.load(open(os.path.join(ROOT, "profiles", cand)))
-            if (pm.get("kernel_source_hash") == src_hash and n == 10000 and D == 32 and args.inverse == "auto"
-                    and args.flow == "maf3" and pm.get("kernel", "").startswith(roof_kernel)
-                    and pm.get("walkers_per_launch") == n_launch):
-                traffic = {"hbm_bytes_per_launch": pm["hbm_bytes_per_launch"], "unit": "B", "source": pm["source"], "file": "profiles/" + cand,
-                           "correction": pm["correction"], "algorithmic_bytes": pm.get("algorithmic_bytes", {}).get("total"),
-                           "kernel_source_hash": src_hash, "note": pm.get("note")}
-                break
-    except (OSError, KeyError, ValueError, ImportError):
-        pass
-    # the roofline fraction is what the kernel EXECUTES (the masked multiply-adds, once) over the f32 MFMA peak; the
-    # SURVEY 8(d) naive-equivalent figure ((D+1) dense passes per transform, which this algorithm does not perform) is
-    # kept as a side key
-    achieved = actual_flops / t_inv / 1e12
-    lane16 = args.precision != "f32" and roof_kernel == "maf_inverse_tri6_kernel" and bool(flow._desc.lane16)
-    peak = PEAK_BF16_MFMA_TFLOPS if lane16 else PEAK_F32_MFMA_TFLOPS
-    roofline = {"bound": "mfma", "kernel": roof_kernel, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                "frac": achieved / peak,
-                "peak_note": ("dense bf16 / f16 MFMA peak: the left-looking products (the bulk of the executed flops) run on "
-                              "v_mfma_f32_16x16x32_bf16 / _f16; the dependent chain (diagonal tiles) stays on v_mfma_f32_4x4x1_16b_f32"
-                              if lane16 else "float32 MFMA peak (= vector peak)"),
-                # HBM bytes per launch come from PMC counters, which cannot be collected inside this process: null here;
-                # the committed rocprofv3 PMC measurement of this very command (same kernel sources, by hash) is kept under
-                # `traffic_committed_profile` for reference
-                "traffic": None,
-                "traffic_committed_profile": traffic,
-                "avg_launch_us": inv_us_live, "launches_timed": len(ev_used),
-                "walkers_per_launch": n_launch,
-                "flops_per_launch": actual_flops,
-                "note": "achieved = executed flops (2 x the unmasked multiply-adds of the flow, each once: the triangular "
-                        "sweep) / launch time, measured with a HIP event pair inside the timed region"
-                        + ("; the launch also proposes theta' for its walkers (fused proposal prologue)" if fused else "")
-                        + ("; and applies the scaler + prior to them and stores x' to pinned host memory over PCIe (fused "
-                           "epilogue, ~1.3 MB per launch at ~40 GB/s): that part of the launch executes no flow flops -- "
-                           "sweep_only is the same launch without it" if (fused and inv_us_sweep_only) else ""),
-                "fused_proposal": bool(fused),
-                "fused_scaler_epilogue": bool(fused and inv_us_sweep_only),
-                "sweep_only": None if not (fused and inv_us_sweep_only) else
-                {"avg_launch_us": inv_us_sweep_only, "achieved": actual_flops / inv_us_sweep_only / 1e6,
-                 "frac": actual_flops / inv_us_sweep_only / 1e6 / PEAK_F32_MFMA_TFLOPS,
-                 "note": "proposal + sweep without the scaler epilogue (10 untimed steps with pmc_step_t.no_fuse = 2)"},
-                "naive_equivalent": {"flops_per_launch": algo_flops, "tflops": algo_flops / t_inv / 1e12,
-                                     "note": "SURVEY 8(d) F_inv = (D+1) F_fwd per walker: zuko's D-pass algorithm, not executed"}}
-    # HBM-nominal sweeps: achieved GB/s against ~8 TB/s.  At this size every array (1.28 MB f32 /
-    # 2.56 MB f64) is cache-resident, so these kernels are launch / latency limited -- reported with that caveat.
-    b_accept = n * 4 * (6 * D + 13)                           # SURVEY figure (fp32 state)
-    b_accept_f64 = n * (8 * (4 * D + 9) + 4 * 2 * D)          # what this build moves: f64 u, x (+theta f32/f64), 9 scalars
-    b_scaler = n * (8 * D + 4)
-    sweeps = {"bound": "hbm", "peak": 8000.0, "unit": "GB/s",
-              "accept_kernel": {"avg_launch_us": us["accept_reduce"], "algorithmic_bytes": b_accept,
-                                "achieved": b_accept / us["accept_reduce"] * 1e-3,
-                                "frac": b_accept / us["accept_reduce"] * 1e-3 / 8000.0,
-                                "bytes_moved_f64_state": b_accept_f64},
-              "scaler_inverse_kernel": {"avg_launch_us": us["scaler_inverse"], "algorithmic_bytes": b_scaler,
-                                        "achieved": b_scaler / us["scaler_inverse"] * 1e-3,
-                                        "frac": b_scaler / us["scaler_inverse"] * 1e-3 / 8000.0},
-              "note": "state is cache-resident at 1e4 x 32: launch/latency bound, not bandwidth bound (SURVEY 8(d) caveat); "
-                      "durations from the instrumented pass (fine-grained launches with device-to-host copies)"}
-    # resample sweep (sampler.py:680-715) on a config-4 sized persistent pool: multinomial indices + gather of 1e4 rows
-    # out of 8e4 pooled particles, f64 state (what this build moves; SURVEY counts 4 B elements)
-    try:
-        P_pool = 8 * n
-        g = torch.Generator(device="cuda").manual_seed(5)
-        pu = torch.randn(P_pool, D, dtype=torch.float64, device="cuda", generator=g)
-        px = torch.randn(P_pool, D, dtype=torch.float64, device="cuda", generator=g)
-        ps = [torch.randn(P_pool, dtype=torch.float64, device="cuda", generator=g) for _ in range(3)]
-        wts = torch.rand(P_pool, dtype=torch.float64, device="cuda", generator=g); wts /= wts.sum()
-        unif = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
-        cdf = torch.empty(P_pool, dtype=torch.float64, device="cuda")
-        ridx = torch.empty(n, dtype=torch.int64, device="cuda")
-        ou, ox = torch.empty(n, D, dtype=torch.float64, device="cuda"), torch.empty(n, D, dtype=torch.float64, device="cuda")
-        os_ = [torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(3)]
-        from pocomc_amd import _lib as _L
-        st_h = _L.stream_handle()
-
-        def resample_once():
-            _L.check(lib.pmc_resample_multinomial(_L.ptr(wts), P_pool, _L.ptr(unif), n, _L.ptr(cdf), _L.ptr(ridx), st_h))
-
-        def gather_once():
-            _L.check(lib.pmc_gather(_L.ptr(ridx), n, D, _L.ptr(pu), _L.ptr(px), _L.ptr(ps[0]), _L.ptr(ps[1]), _L.ptr(ps[2]),
-                                    _L.ptr(ou), _L.ptr(ox), _L.ptr(os_[0]), _L.ptr(os_[1]), _L.ptr(os_[2]), st_h))
-
-        def timed(fn, reps=10):
-            for _ in range(5):
-                fn()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / reps * 1e3
-        t_res, t_gat = timed(resample_once), timed(gather_once)
-        b_gather = n * (2 * D + 3) * 8 * 2 + n * 8                       # rows read + written (f64) + indices
-        sweeps["resample_gather"] = {"pool": P_pool, "rows_out": n, "indices_us": t_res, "gather_us": t_gat,
-                                     "algorithmic_bytes": 4 * n * (3 * D + 3), "bytes_moved_f64_state": b_gather,
-                                     "achieved": b_gather / t_gat * 1e-3, "frac": b_gather / t_gat * 1e-3 / 8000.0,
-                                     "note": "achieved / frac use the f64 bytes this build moves for the gather launch"}
-        del pu, px, ps, ou, ox, os_, cdf
-    except Exception as exc:                                              # (a sub-metric must not take the bench down)
-        sweeps["resample_gather"] = {"error": repr(exc)}
-    # BASELINE configs[4] flow (128-D, 8 transforms, H = 512; "8-layer MAF bf16"): log_prob on 5000 rows per GPU with the
-    # float32 and the bf16 matrix-core kernels -- rows/s and executed-flop fraction of the respective dense MFMA peak
-    flow_cfg5 = None
-    if rank == 0 and not args.no_flow_bench:
+        # ---- per-kernel device times from the HIP events recorded inside the timed region
+        ev = eng.events
+        seg = lambda a, b: float(np.mean([e[a].elapsed_time(e[b]) for e in ev])) * 1e3     # us
+        us = {"propose": seg(0, 1), "maf_inverse": seg(1, 2), "scaler_inverse": seg(2, 3), "d2h_x": seg(3, 4),
+              "accept_reduce": seg(5, 6)}
+        n_launch = roof_eng.n                                         # walkers of the launch the event pair brackets
+        algo_flops = n_launch * spec.flops_inverse_naive()            # (D+1)*F_fwd per walker
+        actual_flops = n_launch * 2 * spec.macs_masked()              # what the triangular sweep needs
+        if inv_us_live is None:
+            inv_us_live = us["maf_inverse"]                     # (--steps 1 --no-steady-state: the instrumented pass's figure)
+        us["maf_inverse_timed_region"] = inv_us_live            # HIP events inside the timed region
+        t_inv = inv_us_live * 1e-6
+        lane_auto = args.inverse in ("auto", "triangular") and bool(lib.pmc_maf_inverse_auto_is_lane(ctypes.byref(flow._desc)))
+        nsf2 = spec.univariate == "rqs" and bool(lib.pmc_maf_inverse_auto_is_nsf2(ctypes.byref(flow._desc)))
+        fused = (eng.pre and spec.tri_ok and not lane_auto and args.inverse in ("auto", "triangular")
+                 and ((spec.univariate == "affine" and spec.nOT <= 8) or nsf2))
+        duo = bool(lib.pmc_maf_inverse_auto_is_duo(ctypes.byref(flow._desc), n_launch))
+        roof_kernel = ("maf_dense_kernel<1>" if (args.inverse == "naive" or not spec.tri_ok) else
+                       "maf_inverse_nsf2_kernel" if (nsf2 and args.inverse in ("auto", "triangular", "duo")) else
+                       "maf_inverse_tri_nsf_kernel" if spec.univariate == "rqs" else
+                       "maf_inverse_tri6_kernel" if (args.inverse == "lane" or lane_auto or os.environ.get("PMC_INVERSE_LANE", "0") != "0") else
+                       "maf_inverse_tri4_kernel" if args.inverse == "solo" else
+                       "maf_inverse_tri5_kernel" if (args.inverse == "duo" or duo) else "maf_inverse_tri4_kernel")
+        # HBM bytes per launch of the dominant kernel: PMC passes cannot run inside this process; the value is the
+        # committed rocprofv3 measurement of this very command (scripts/collect_profile.sh -> profiles/*_traffic.json),
+        # used only when it was taken on the kernel sources this run was built from (their hash is stored with it) and
+        # for the same kernel / walkers per launch -- otherwise null
+        traffic = None
         try:
-            from pocomc_amd.maf_spec import MAFSpec
-            sp5 = MAFSpec(128, 8)
-            x5 = torch.randn(5000, 128, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
-            flow_cfg5 = {"workload": "log_prob of 5000 rows, 128-D MAF, 8 transforms, H=512 (BASELINE configs[4] per-GPU shard)",
-                         "flops_per_row_executed": 2 * sp5.macs_masked(), "flops_per_row_dense": sp5.flops_forward_dense()}
-            for prec, peak in (("f32", PEAK_F32_MFMA_TFLOPS), ("bf16", PEAK_BF16_MFMA_TFLOPS)):
-                f5 = Flow(128, sp5, seed=0, precision=prec)
-                for _ in range(3):
-                    f5.log_prob(x5)
+            src_hash = kernel_source_hash(ROOT)
+            for cand in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")), reverse=True):
+                pm = json.load(open(os.path.join(ROOT, "profiles", cand)))
+                if (pm.get("kernel_source_hash") == src_hash and n == 10000 and D == 32 and args.inverse == "auto"
+                        and args.flow == "maf3" and pm.get("kernel", "").startswith(roof_kernel)
+                        and pm.get("walkers_per_launch") == n_launch):
+                    traffic = {"hbm_bytes_per_launch": pm["hbm_bytes_per_launch"], "unit": "B", "source": pm["source"], "file": "profiles/" + cand,
+                               "correction": pm["correction"], "algorithmic_bytes": pm.get("algorithmic_bytes", {}).get("total"),
+                               "kernel_source_hash": src_hash, "note": pm.get("note")}
+                    break
+        except (OSError, KeyError, ValueError, ImportError):
+            pass
+        # the roofline fraction is what the kernel EXECUTES (the masked multiply-adds, once) over the f32 MFMA peak; the
+        # SURVEY 8(d) naive-equivalent figure ((D+1) dense passes per transform, which this algorithm does not perform) is
+        # kept as a side key
+        achieved = actual_flops / t_inv / 1e12
+        lane16 = args.precision != "f32" and roof_kernel == "maf_inverse_tri6_kernel" and bool(flow._desc.lane16)
+        peak = PEAK_BF16_MFMA_TFLOPS if lane16 else PEAK_F32_MFMA_TFLOPS
+        roofline = {"bound": "mfma", "kernel": roof_kernel, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                    "frac": achieved / peak,
+                    "peak_note": ("dense bf16 / f16 MFMA peak: the left-looking products (the bulk of the executed flops) run on "
+                                  "v_mfma_f32_16x16x32_bf16 / _f16; the dependent chain (diagonal tiles) stays on v_mfma_f32_4x4x1_16b_f32"
+                                  if lane16 else "float32 MFMA peak (= vector peak)"),
+                    # HBM bytes per launch come from PMC counters, which cannot be collected inside this process: null here;
+                    # the committed rocprofv3 PMC measurement of this very command (same kernel sources, by hash) is kept under
+                    # `traffic_committed_profile` for reference
+                    "traffic": None,
+                    "traffic_committed_profile": traffic,
+                    "avg_launch_us": inv_us_live, "launches_timed": len(ev_used),
+                    "walkers_per_launch": n_launch,
+                    "flops_per_launch": actual_flops,
+                    "note": "achieved = executed flops (2 x the unmasked multiply-adds of the flow, each once: the triangular "
+                            "sweep) / launch time, measured with a HIP event pair inside the timed region"
+                            + ("; the launch also proposes theta' for its walkers (fused proposal prologue)" if fused else "")
+                            + ("; and applies the scaler + prior to them and stores x' to pinned host memory over PCIe (fused "
+                               "epilogue, ~1.3 MB per launch at ~40 GB/s): that part of the launch executes no flow flops -- "
+                               "sweep_only is the same launch without it" if (fused and inv_us_sweep_only) else ""),
+                    "fused_proposal": bool(fused),
+                    "fused_scaler_epilogue": bool(fused and inv_us_sweep_only),
+                    "sweep_only": None if not (fused and inv_us_sweep_only) else
+                    {"avg_launch_us": inv_us_sweep_only, "achieved": actual_flops / inv_us_sweep_only / 1e6,
+                     "frac": actual_flops / inv_us_sweep_only / 1e6 / PEAK_F32_MFMA_TFLOPS,
+                     "note": "proposal + sweep without the scaler epilogue (10 untimed steps with pmc_step_t.no_fuse = 2)"},
+                    "naive_equivalent": {"flops_per_launch": algo_flops, "tflops": algo_flops / t_inv / 1e12,
+                                         "note": "SURVEY 8(d) F_inv = (D+1) F_fwd per walker: zuko's D-pass algorithm, not executed"}}
+        # HBM-nominal sweeps: achieved GB/s against ~8 TB/s.  At this size every array (1.28 MB f32 /
+        # 2.56 MB f64) is cache-resident, so these kernels are launch / latency limited -- reported with that caveat.
+        b_accept = n * 4 * (6 * D + 13)                           # SURVEY figure (fp32 state)
+        b_accept_f64 = n * (8 * (4 * D + 9) + 4 * 2 * D)          # what this build moves: f64 u, x (+theta f32/f64), 9 scalars
+        b_scaler = n * (8 * D + 4)
+        sweeps = {"bound": "hbm", "peak": 8000.0, "unit": "GB/s",
+                  "accept_kernel": {"avg_launch_us": us["accept_reduce"], "algorithmic_bytes": b_accept,
+                                    "achieved": b_accept / us["accept_reduce"] * 1e-3,
+                                    "frac": b_accept / us["accept_reduce"] * 1e-3 / 8000.0,
+                                    "bytes_moved_f64_state": b_accept_f64},
+                  "scaler_inverse_kernel": {"avg_launch_us": us["scaler_inverse"], "algorithmic_bytes": b_scaler,
+                                            "achieved": b_scaler / us["scaler_inverse"] * 1e-3,
+                                            "frac": b_scaler / us["scaler_inverse"] * 1e-3 / 8000.0},
+                  "note": "state is cache-resident at 1e4 x 32: launch/latency bound, not bandwidth bound (SURVEY 8(d) caveat); "
+                          "durations from the instrumented pass (fine-grained launches with device-to-host copies)"}
+        # resample sweep (sampler.py:680-715) on a config-4 sized persistent pool: multinomial indices + gather of 1e4 rows
+        # out of 8e4 pooled particles, f64 state (what this build moves; SURVEY counts 4 B elements)
+        try:
+            P_pool = 8 * n
+            g = torch.Generator(device="cuda").manual_seed(5)
+            pu = torch.randn(P_pool, D, dtype=torch.float64, device="cuda", generator=g)
+            px = torch.randn(P_pool, D, dtype=torch.float64, device="cuda", generator=g)
+            ps = [torch.randn(P_pool, dtype=torch.float64, device="cuda", generator=g) for _ in range(3)]
+            wts = torch.rand(P_pool, dtype=torch.float64, device="cuda", generator=g); wts /= wts.sum()
+            unif = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
+            cdf = torch.empty(P_pool, dtype=torch.float64, device="cuda")
+            ridx = torch.empty(n, dtype=torch.int64, device="cuda")
+            ou, ox = torch.empty(n, D, dtype=torch.float64, device="cuda"), torch.empty(n, D, dtype=torch.float64, device="cuda")
+            os_ = [torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(3)]
+            from pocomc_amd import _lib as _L
+            st_h = _L.stream_handle()
+
+            def resample_once():
+                _L.check(lib.pmc_resample_multinomial(_L.ptr(wts), P_pool, _L.ptr(unif), n, _L.ptr(cdf), _L.ptr(ridx), st_h))
+
+            def gather_once():
+                _L.check(lib.pmc_gather(_L.ptr(ridx), n, D, _L.ptr(pu), _L.ptr(px), _L.ptr(ps[0]), _L.ptr(ps[1]), _L.ptr(ps[2]),
+                                        _L.ptr(ou), _L.ptr(ox), _L.ptr(os_[0]), _L.ptr(os_[1]), _L.ptr(os_[2]), st_h))
+
+            def timed(fn, reps=10):
+                for _ in range(5):
+                    fn()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                for _ in range(10):
-                    f5.log_prob(x5)
+                for _ in range(reps):
+                    fn()
                 e1.record()
                 torch.cuda.synchronize()
-                us5 = e0.elapsed_time(e1) / 10 * 1e3
-                tf = 5000 * 2 * sp5.macs_masked() / us5 / 1e6
-                flow_cfg5[prec] = {"us_per_call": us5, "rows_per_s": 5000 / us5 * 1e6, "achieved_tflops": tf, "peak_tflops": peak,
-                                   "frac": tf / peak, "dense_equivalent_tflops": 5000 * sp5.flops_forward_dense() / us5 / 1e6}
-                if prec == "f32":
-                    # the sweep every MCMC step of this config runs (flow.py:116-132; float32 whatever the flow's precision,
-                    # csrc/maf_inverse_tri6.hip): 5000 walkers are two rounds of 256 workgroups x 16 walkers, 4096 are one
-                    z5 = torch.randn(5000, 128, device="cuda", generator=torch.Generator(device="cuda").manual_seed(4))
-                    inv = {}
-                    for rows in (4096, 5000):
-                        for _ in range(2):
-                            f5.inverse(z5[:rows])
-                        e0.record()
-                        for _ in range(5):
-                            f5.inverse(z5[:rows])
-                        e1.record()
-                        torch.cuda.synchronize()
-                        us_inv = e0.elapsed_time(e1) / 5 * 1e3
-                        tf_inv = rows * 2 * sp5.macs_masked() / us_inv / 1e6
-                        inv[str(rows)] = {"us_per_call": us_inv, "rows_per_s": rows / us_inv * 1e6, "achieved_tflops": tf_inv,
-                                          "peak_tflops": PEAK_F32_MFMA_TFLOPS, "frac": tf_inv / PEAK_F32_MFMA_TFLOPS}
-                    flow_cfg5["inverse_f32"] = inv
-                # Flow.fit's optimizer step at the reference's batch size (sampler.py:289: 512 rows): loss + gradient,
-                # clip, AdamW, image refresh -- the float32 chain + weight-gradient kernels against the bf16 per-layer products
-                from pocomc_amd.train import AdamW
-                opt5 = AdamW(f5, 1e-3)
-                acc5 = torch.zeros(1, dtype=torch.float32, device="cuda")
-                opt5.epoch(x5, None, None, 512, 1.0, acc5)
-                e0.record()
-                for _ in range(3):
+                return e0.elapsed_time(e1) / reps * 1e3
+            t_res, t_gat = timed(resample_once), timed(gather_once)
+            b_gather = n * (2 * D + 3) * 8 * 2 + n * 8                       # rows read + written (f64) + indices
+            sweeps["resample_gather"] = {"pool": P_pool, "rows_out": n, "indices_us": t_res, "gather_us": t_gat,
+                                         "algorithmic_bytes": 4 * n * (3 * D + 3), "bytes_moved_f64_state": b_gather,
+                                         "achieved": b_gather / t_gat * 1e-3, "frac": b_gather / t_gat * 1e-3 / 8000.0,
+                                         "note": "achieved / frac use the f64 bytes this build moves for the gather launch"}
+            del pu, px, ps, ou, ox, os_, cdf
+        except Exception as exc:                                              # (a sub-metric must not take the bench down)
+            sweeps["resample_gather"] = {"error": repr(exc)}
+        # BASELINE configs[4] flow (128-D, 8 transforms, H = 512; "8-layer MAF bf16"): log_prob on 5000 rows per GPU with the
+        # float32 and the bf16 matrix-core kernels -- rows/s and executed-flop fraction of the respective dense MFMA peak
+        flow_cfg5 = None
+        if rank == 0 and not args.no_flow_bench:
+            try:
+                from pocomc_amd.maf_spec import MAFSpec
+                sp5 = MAFSpec(128, 8)
+                x5 = torch.randn(5000, 128, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+                flow_cfg5 = {"workload": "log_prob of 5000 rows, 128-D MAF, 8 transforms, H=512 (BASELINE configs[4] per-GPU shard)",
+                             "flops_per_row_executed": 2 * sp5.macs_masked(), "flops_per_row_dense": sp5.flops_forward_dense()}
+                for prec, peak in (("f32", PEAK_F32_MFMA_TFLOPS), ("bf16", PEAK_BF16_MFMA_TFLOPS)):
+                    f5 = Flow(128, sp5, seed=0, precision=prec)
+                    for _ in range(3):
+                        f5.log_prob(x5)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(10):
+                        f5.log_prob(x5)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us5 = e0.elapsed_time(e1) / 10 * 1e3
+                    tf = 5000 * 2 * sp5.macs_masked() / us5 / 1e6
+                    flow_cfg5[prec] = {"us_per_call": us5, "rows_per_s": 5000 / us5 * 1e6, "achieved_tflops": tf, "peak_tflops": peak,
+                                       "frac": tf / peak, "dense_equivalent_tflops": 5000 * sp5.flops_forward_dense() / us5 / 1e6}
+                    if prec == "f32":
+                        # the sweep every MCMC step of this config runs (flow.py:116-132; float32 whatever the flow's precision,
+                        # csrc/maf_inverse_tri6.hip): 5000 walkers are two rounds of 256 workgroups x 16 walkers, 4096 are one
+                        z5 = torch.randn(5000, 128, device="cuda", generator=torch.Generator(device="cuda").manual_seed(4))
+                        inv = {}
+                        for rows in (4096, 5000):
+                            for _ in range(2):
+                                f5.inverse(z5[:rows])
+                            e0.record()
+                            for _ in range(5):
+                                f5.inverse(z5[:rows])
+                            e1.record()
+                            torch.cuda.synchronize()
+                            us_inv = e0.elapsed_time(e1) / 5 * 1e3
+                            tf_inv = rows * 2 * sp5.macs_masked() / us_inv / 1e6
+                            inv[str(rows)] = {"us_per_call": us_inv, "rows_per_s": rows / us_inv * 1e6, "achieved_tflops": tf_inv,
+                                              "peak_tflops": PEAK_F32_MFMA_TFLOPS, "frac": tf_inv / PEAK_F32_MFMA_TFLOPS}
+                        flow_cfg5["inverse_f32"] = inv
+                    # Flow.fit's optimizer step at the reference's batch size (sampler.py:289: 512 rows): loss + gradient,
+                    # clip, AdamW, image refresh -- the float32 chain + weight-gradient kernels against the bf16 per-layer products
+                    from pocomc_amd.train import AdamW
+                    opt5 = AdamW(f5, 1e-3)
+                    acc5 = torch.zeros(1, dtype=torch.float32, device="cuda")
                     opt5.epoch(x5, None, None, 512, 1.0, acc5)
-                e1.record()
-                torch.cuda.synchronize()
-                us_step = e0.elapsed_time(e1) / 30 * 1e3
-                dense = 3 * sp5.flops_forward_dense() * 5000 / 10 / us_step / 1e6
-                executed = dense if prec == "bf16" else 3 * 2 * sp5.macs_masked() * 5000 / 10 / us_step / 1e6
-                flow_cfg5[prec]["fit"] = {"us_per_step_of_512_rows": us_step, "rows_per_s": 5000 / 10 / us_step * 1e6,
-                                          "dense_equivalent_tflops": dense, "executed_tflops": executed,
-                                          "frac": executed / peak,
-                                          "engine": "csrc/maf_train_bf16.hip (dense products, masked weights are zeros)"
-                                          if prec == "bf16" else "csrc/maf_train.hip (masked tiles skipped)"}
-                del f5, opt5
-            flow_cfg5["speedup_bf16"] = flow_cfg5["f32"]["us_per_call"] / flow_cfg5["bf16"]["us_per_call"]
-            flow_cfg5["fit_speedup_bf16"] = (flow_cfg5["f32"]["fit"]["us_per_step_of_512_rows"]
-                                             / flow_cfg5["bf16"]["fit"]["us_per_step_of_512_rows"])
-        except Exception as exc:                                          # (a sub-metric must not take the bench down)
-            flow_cfg5 = {"error": repr(exc)}
+                    e0.record()
+                    for _ in range(3):
+                        opt5.epoch(x5, None, None, 512, 1.0, acc5)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us_step = e0.elapsed_time(e1) / 30 * 1e3
+                    dense = 3 * sp5.flops_forward_dense() * 5000 / 10 / us_step / 1e6
+                    executed = dense if prec == "bf16" else 3 * 2 * sp5.macs_masked() * 5000 / 10 / us_step / 1e6
+                    flow_cfg5[prec]["fit"] = {"us_per_step_of_512_rows": us_step, "rows_per_s": 5000 / 10 / us_step * 1e6,
+                                              "dense_equivalent_tflops": dense, "executed_tflops": executed,
+                                              "frac": executed / peak,
+                                              "engine": "csrc/maf_train_bf16.hip (dense products, masked weights are zeros)"
+                                              if prec == "bf16" else "csrc/maf_train.hip (masked tiles skipped)"}
+                    del f5, opt5
+                flow_cfg5["speedup_bf16"] = flow_cfg5["f32"]["us_per_call"] / flow_cfg5["bf16"]["us_per_call"]
+                flow_cfg5["fit_speedup_bf16"] = (flow_cfg5["f32"]["fit"]["us_per_step_of_512_rows"]
+                                                 / flow_cfg5["bf16"]["fit"]["us_per_step_of_512_rows"])
+            except Exception as exc:                                          # (a sub-metric must not take the bench down)
+                flow_cfg5 = {"error": repr(exc)}
     ms_per_step = dt / args.steps * 1e3
     value = (n * world * args.steps / dt) / 1e4
     # 16-bit helper products: how far the sweep this run timed is from the float32 sweep ON THE TRAINED FLOW, at the current
-    # walkers' theta (the opt-in precision's cost in accuracy, measured where it is used)
+    # walkers' theta (the opt-in precision's cost in accuracy, measured where it is used).  A plain run checks it too: a
+    # sweep that fails it refuses the headline value below
     lane16_check = None
     if args.precision != "f32" and bool(flow._desc.lane16):
         th = (leng.lanes[0].theta32 if leng is not None else eng.theta32)[:4096].clone()
@@ -1088,27 +1103,29 @@ def main():
                       "collectives": (None if world == 1 else
                                       ("pmc_comm mailboxes inside the C pipeline (" + comm_kind_name() + ", one D+4-double sum per step; "
                                        "the process group only exchanges the handles at start-up)"
-                                       if (laned_host or {}).get("pipeline") else
+                                       if leng is not None and leng.pipeline_stats(reset=False) is not None else
                                        ("RCCL (torch.distributed nccl backend on ROCm)" if dist.get_backend() == "nccl"
                                         else "gloo (functional check on a shared GPU)"))),
                       "ranks_reported_by_backend": (dist.get_world_size() if world > 1 else 1),
                       "shared_gpu": bool(os.environ.get("PMC_BENCH_SHARE_GPU"))},
-           "roofline": roofline,
-           "roofline_sweeps": sweeps,
            "flow_fit": flow_fit,
            "inverse_16bit_vs_f32": lane16_check,
-           "flow_config5": flow_cfg5,
-           "device_only_steps_per_s": 1e6 / (us["propose"] + us["maf_inverse"] + us["scaler_inverse"]
-                                             + us["accept_reduce"]),
-           "breakdown_us_per_step": dict(us, host_prior_likelihood=t_host[0] / n_inst * 1e6,
-                                         device_kernels=us["propose"] + us["maf_inverse"] + us["scaler_inverse"]
-                                         + us["accept_reduce"], wall=ms_per_step * 1e3,
-                                         instrumented_pass_wall=dt_inst / n_inst * 1e6),
-           "timed_region_host_us_per_step": seg_timed,
-           "laned_path_host_us_per_step": laned_host,
-           "composite_path_host_us_per_step": composite_host,
-           "host_us_per_step": {**{k: v / n_inst * 1e6 for k, v in eng.host_timers.items()},
-                                **{k: v / n_inst * 1e6 for k, v in t_seg.items()}}}
+           "timed_region_host_us_per_step": seg_timed}
+    if args.full:
+        out.update({
+            "roofline": roofline,
+            "roofline_sweeps": sweeps,
+            "flow_config5": flow_cfg5,
+            "device_only_steps_per_s": 1e6 / (us["propose"] + us["maf_inverse"] + us["scaler_inverse"]
+                                              + us["accept_reduce"]),
+            "breakdown_us_per_step": dict(us, host_prior_likelihood=t_host[0] / n_inst * 1e6,
+                                          device_kernels=us["propose"] + us["maf_inverse"] + us["scaler_inverse"]
+                                          + us["accept_reduce"], wall=ms_per_step * 1e3,
+                                          instrumented_pass_wall=dt_inst / n_inst * 1e6),
+            "laned_path_host_us_per_step": laned_host,
+            "composite_path_host_us_per_step": composite_host,
+            "host_us_per_step": {**{k: v / n_inst * 1e6 for k, v in eng.host_timers.items()},
+                                 **{k: v / n_inst * 1e6 for k, v in t_seg.items()}}})
     out["config"]["driver_pinned_to_core"] = pinned_core
     out["config"]["pin_calibration"] = pin_probe
     if per_rank is not None:
@@ -1121,10 +1138,10 @@ def main():
         out["value_refused"] = {"value_measured": value, "reason": f"16-bit sweep: max per-walker relative error on x "
                                 f"{lane16_check['x_rel_err_max']:.3g} > {LANE16_BOUND:g} against the float32 sweep of the trained flow"}
         out["value"] = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(D, n, beta, flow.params.cpu().numpy(), spec, x, u, geo, sigma0, seed=0,
                                            target=target, bounds=(p_lo, p_hi))
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out))

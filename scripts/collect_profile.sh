@@ -8,7 +8,7 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p "$out"
 cd /tmp; export TMPDIR=/tmp
-args="--steps 100 --warmup 10 --no-cpu-baseline $*"
+args="--full --steps 100 --warmup 10 --no-cpu-baseline $*"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -o kt -- python "$root/bench.py" $args \
     > "$out/bench_under_rocprof.json" 2> "$out/kt.log" < /dev/null
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o pmc -- python "$root/bench.py" $args \

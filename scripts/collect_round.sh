@@ -5,7 +5,7 @@ set -u
 tag=$1
 out=gpurun_out/$tag
 mkdir -p $out
-b() { name=$1; shift; timeout 900 python bench.py "$@" > $out/bench_$name.json 2> $out/bench_$name.err; tail -c 300 $out/bench_$name.err > $out/bench_$name.errtail; rm -f $out/bench_$name.err; }
+b() { name=$1; shift; timeout 900 python bench.py --full "$@" > $out/bench_$name.json 2> $out/bench_$name.err; tail -c 300 $out/bench_$name.err > $out/bench_$name.errtail; rm -f $out/bench_$name.err; }
 b default
 b driver_cmd --gpus 1 --steps 20 --warmup 5
 b cfg2 --target gaussian --steps 100 --warmup 10 --no-cpu-baseline --no-flow-bench
@@ -17,5 +17,5 @@ b cfg5_bf16 --dim 128 --particles 5000 --flow custom8 --target funnel --precisio
 b cfg5_f16 --dim 128 --particles 5000 --flow custom8 --target funnel --precision f16 --steps 50 --warmup 5 --no-cpu-baseline --no-flow-bench
 b nsf3 --flow nsf3 --steps 100 --warmup 10 --no-cpu-baseline --no-flow-bench
 b nsf6 --flow nsf6 --steps 100 --warmup 10 --no-cpu-baseline --no-flow-bench
-PMC_BENCH_EPI_STAMPS=1 timeout 600 python bench.py --no-cpu-baseline --no-flow-bench 2>&1 >/dev/null | grep "epilogue stamps" > $out/epilogue_stamps.txt
+PMC_BENCH_EPI_STAMPS=1 timeout 600 python bench.py --full --no-cpu-baseline --no-flow-bench 2>&1 >/dev/null | grep "epilogue stamps" > $out/epilogue_stamps.txt
 timeout 3000 python -m pytest tests -m gpu -q -x 2>&1 | tail -25 > $out/gpu_tests.txt

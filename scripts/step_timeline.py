@@ -1,7 +1,7 @@
 """Timeline of the pipelined step from a rocprofv3 kernel trace (``*_kernel_trace.csv``): every kernel of a window in
 the middle of the timed region with its start (us, relative), duration, queue, and the idle gap of the device before it.
 
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o kt -- python bench.py --steps 100 --no-cpu-baseline --no-flow-bench
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o kt -- python bench.py --full --steps 100 --no-cpu-baseline --no-flow-bench
     python scripts/step_timeline.py /tmp/kt [n_rows] [where]     (where: fraction of the accept launches at which the window
                                                                   starts, default 0.2 = inside bench.py's timed region)
 """

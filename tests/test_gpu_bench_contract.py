@@ -1,5 +1,6 @@
 """bench.py prints ONE JSON line with the fields the driver's contract names (metric / value / unit / n_gpus / steps /
-warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config + roofline + cpu_baseline)."""
+warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config); ``--full`` adds roofline +
+cpu_baseline and the other side measurements."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("extra", [[], ["--lanes", "1", "--no-pipeline"], ["--flow", "nsf3"]])
 def test_bench_line_follows_the_contract(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "1024", "--steps", "6", "--warmup", "2"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--particles", "1024", "--steps", "6", "--warmup", "2"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -68,12 +69,45 @@ def test_dump_outputs_writes_the_timed_paths_results(tmp_path):
     assert not np.array_equal(more["u"], got["u"]) and not np.array_equal(more["mu"], got["mu"])
 
 
+def test_plain_line_is_the_headline_of_a_full_run(tmp_path):
+    """Without ``--full`` the line carries the contract's fields and none of the side measurements, and the timed steps
+    are those of a ``--full`` run: the same arguments dump the same arrays bit for bit."""
+    import numpy as np
+
+    def run(extra, tag):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "1024", "--steps", "4", "--warmup", "2",
+               "--dump-outputs", str(tmp_path / tag)] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(tmp_path / tag / f) for f in sorted(os.listdir(tmp_path / tag))}
+
+    plain, got = run([], "plain")
+    full, ref = run(["--full", "--no-cpu-baseline", "--no-flow-bench"], "full")
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in plain, key
+        assert key in full, key
+    for key in ("roofline", "roofline_sweeps", "flow_config5", "breakdown_us_per_step", "steady_state", "cpu_baseline"):
+        assert key not in plain, key
+    for key in ("roofline", "roofline_sweeps", "breakdown_us_per_step", "steady_state", "cpu_baseline"):
+        assert key in full, key
+    for d in (plain, full):
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True
+        assert d["value"] > 0 and abs(d["ms_per_step"] - 1024 / 1e4 / d["value"] * 1e3) < 1e-6 * d["ms_per_step"] + 1e-9
+    assert (plain["metric"], plain["unit"], plain["dtype"]) == (full["metric"], full["unit"], full["dtype"])
+    assert sorted(got) == sorted(ref)
+    for k in ref:
+        np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
+
+
 def test_two_ranks_on_a_shared_gpu_report_a_two_rank_line():
     """``python bench.py --gpus 2`` on a one-GPU box: the bench launches its own two ranks (``torch.distributed.run``;
     with fewer GPUs than ranks they share device 0 over gloo -- the multi-rank code path, flagged ``shared_gpu``): rc 0,
     one JSON line from rank 0, ``n_gpus == 2``, 2 x 10000 walkers, a backend that reports two ranks, no CPU baseline at
     N > 1, roofline present -- so that the first run on a real 8-GPU node cannot die on plumbing."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-flow-bench"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-flow-bench"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -107,8 +141,8 @@ def test_eight_ranks_on_a_shared_gpu_report_an_eight_rank_line():
     n = torch.cuda.device_count()
     if n < 8:
         pytest.skip(f"needs 8 GPUs, found {n}: below 8, bench.py puts the eight ranks on one GPU (10 processes, at most 6)")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2", "--no-flow-bench",
-           "--no-steady-state"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "6", "--warmup", "2",
+           "--no-flow-bench", "--no-steady-state"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
