@@ -518,6 +518,21 @@ typedef struct pmc_step {
      * The device copy p_x keeps x'.  Needs h_clean / clean_count and a device prior. */
     int32_t fill_rejected;
     int32_t fill_pad;
+    /* Likelihood on the device (mcmc.py:99-121 with the user's likelihood a GPU callable): with lik_x non-NULL x' is never
+     * copied to the host and logl' never uploaded.
+     *   pmc_step_pre writes x' into lik_x, column-major ((n, D) with strides (1, n)), with the walker's current x (cur.x) in
+     *   every row that does not reach the likelihood -- x' or logdetj' not finite, or the device-evaluated logp' not finite
+     *   (the finite_mask of mcmc.py:99-109) -- and counts those rows in clean_count (device word, zero between steps); no
+     *   completion word, no copy to the host.  Without a device prior it hands x' and the finite mask to the host as before
+     *   (for Prior.logpdf only); pmc_step_lik_rows then uploads the host's logp' and fills lik_x and the count.
+     *   The caller evaluates the likelihood on lik_x into p_logl (device) on the same stream.
+     *   pmc_step_post reads logl' from p_logl and logp' from p_logp (no H2D) and gates logl' to -inf wherever p_fin is 0 or
+     *   logp' is not finite (mcmc.py:118-121) before the ratio of mcmc.py:124-134: accepted rows store the gated value; a
+     *   NaN from the likelihood gives alpha = 0 (:134).  Its last block writes n - clean_count, the number of rows that
+     *   reached the likelihood (mcmc.py:121's n_calls increment), to h_calls ahead of the sums and the completion word
+     *   h_done[1], and zeroes clean_count.  Needs clean_count and h_calls; adapt_state is optional as for the host path. */
+    double* lik_x;            /* device f64 [D][n] or NULL */
+    int64_t* h_calls;         /* pinned host int64 [1] */
 } pmc_step_t;
 
 #define PMC_ADAPT_TPCN 1      /* sigma <- |min(sigma + c (mean alpha - 0.234), cap)|      (mcmc.py:152, :476) */
@@ -545,6 +560,11 @@ int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double si
 /* mcmc.py:124-156 in one call: H2D logl', logp' -> accept + reductions -> [D2H sums, accept mask]. */
 int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask,
                   int copy_sums, void* stream);
+/* Device likelihood with a prior the device does not evaluate (pmc_step_t.lik_x, prior == NULL): behind the host's
+ * Prior.logpdf of the finite rows (mcmc.py:105-107, into h_logp), H2D logp' -> p_logp, then lik_x <- x' or, for the rows
+ * that do not reach the likelihood (p_fin 0 or logp' not finite, mcmc.py:108-109), the walker's current x; those rows
+ * are added to clean_count. */
+int pmc_step_lik_rows(const pmc_step_t* s, void* stream);
 /* The adaptation of pmc_step_t.adapt_state as a launch of its own, for walker sets whose sums come in parts
  * (row ranges stepped one after the other, mcmc.LanedEngine; ranks, after the all-reduce):
  *   total[j] = parts[0][j] + parts[1][j] + ...   (j < D + 4, n_parts <= 8, added in this order)

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256) void accept_kernel(
     pmc_rng_t rng, double* __restrict__ alpha_out, int32_t* __restrict__ accept_out,
     double* __restrict__ partials, unsigned* __restrict__ ticket, double* __restrict__ sums,
     double* __restrict__ sums_copy, long long* __restrict__ done_flag, long long done_value, int64_t n, int D,
-    pmc_adapt_args ad) {
+    pmc_adapt_args ad, pmc_gate_args gate) {
     __shared__ int flag[ACC_ROWS];
     __shared__ double colsum[8][33];
     __shared__ int is_last;
@@ -307,7 +307,10 @@ __global__ __launch_bounds__(256) void accept_kernel(
         int acc = 0;
         if (tid < rows) {
             const double logl = cur.logl[k], logp = cur.logp[k], ldj = cur.logdetj[k];
-            const double logl_p = prop.logl[k], logp_p = prop.logp[k], ldj_p = prop.logdetj[k];
+            const double logp_p = prop.logp[k], ldj_p = prop.logdetj[k];
+            double logl_p = prop.logl[k];
+            // device likelihood (pmc_step_t.lik_x): the rows left out of the likelihood get -inf (mcmc.py:118-121)
+            if (gate.fin && !(gate.fin[k] && isfinite(logp_p))) logl_p = -INFINITY;
             double e;
             {
                 // mcmc.py:130-133, left to right
@@ -448,6 +451,12 @@ __global__ __launch_bounds__(256) void accept_kernel(
         __syncthreads();
         if (ad.state && ad.mode) adapt_apply(ad, total, tid, D);
     } else if (ad.state && ad.mode) adapt_apply(ad, sums, tid, D);   // pmc_step_t.adapt_state: the proposal of the next step
+    if (gate.calls_out && tid == 0) {
+        // rows that reached the likelihood this step (pmc_step_t.h_calls), ahead of the completion word; the count of the
+        // others goes back to zero for the next pre-step (which the stream orders behind this launch)
+        const unsigned bad = gate.bad_count ? __hip_atomic_exchange(gate.bad_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        *gate.calls_out = gate.calls_n - (long long)bad;
+    }
     if (done_flag) {
         // the sums' host copy acknowledged before the completion word (agent-scope release: scaler_body.h says why that
         // is enough); the state updates are device memory, ordered for the next kernel by the kernel boundary
@@ -749,7 +758,9 @@ int pmc_scaler_inverse_prior_ex(const pmc_scaler_t* s, const pmc_prior_t* prior,
     pmc_prior_t pr_val = {};
     if (prior) pr_val = *prior;
     pmc_scaler_extra ex{};
-    if (extra && done && x_colmajor) ex = *extra;       // (the count travels with the completion word, the fill with the host copy)
+    // (the count travels with the completion word, the fill with the host copy -- or, for a device likelihood, both stay
+    //  on the device: no flag, no completion word)
+    if (extra && x_colmajor && (done || !extra->bad_flag)) ex = *extra;
     const size_t lds = (size_t)SCL_ROWS * s->D * sizeof(double) + SCL_ROWS * sizeof(int) +
                        ((x_colmajor || logp) ? (size_t)s->D * (SCL_ROWS + 1) * sizeof(double) : 0);
     if (lds > 160 * 1024 || s->D > 1024) return pmc_fail("pmc_scaler_inverse: n_dim too large");
@@ -782,7 +793,7 @@ extern "C" int64_t pmc_accept_workspace_bytes(int64_t n, int32_t D) {
 static int accept_impl(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta,
                        double nu, const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums,
                        double* sums_copy, bool armed, const pmc_done_t* done, void* workspace, int64_t n, int32_t D,
-                       void* stream, const pmc_adapt_args* adapt = nullptr) {
+                       void* stream, const pmc_adapt_args* adapt = nullptr, const pmc_gate_args* gate = nullptr) {
     if (!cur || !prop || !rng || !sums || !workspace || n < 0 || D < 1) return pmc_fail("pmc_accept: bad argument");
     if (!cur->u || !cur->x || !cur->logdetj || !cur->logl || !cur->logp || !prop->u || !prop->x ||
         !prop->logdetj || !prop->logl || !prop->logp)
@@ -804,7 +815,8 @@ static int accept_impl(int kind, int preconditioned, pmc_state_t* cur, const pmc
     if (!armed && hipMemsetAsync(ticket, 0, sizeof(unsigned), st) != hipSuccess) return pmc_fail("pmc_accept: memset");
     hipLaunchKernelGGL(accept_kernel, dim3(nb), dim3(256), 0, st, preconditioned, tpcn, *cur, *prop, beta, nu, *rng,
                        alpha_out, accept_out, partials, ticket, sums, sums_copy, done ? (long long*)done->flag : nullptr,
-                       done ? (long long)done->value : 0LL, n, (int)D, adapt ? *adapt : pmc_adapt_args{});
+                       done ? (long long)done->value : 0LL, n, (int)D, adapt ? *adapt : pmc_adapt_args{},
+                       gate ? *gate : pmc_gate_args{});
     return pmc_check_launch("accept_kernel");
 }
 
@@ -1097,11 +1109,12 @@ extern "C" int pmc_comm_adapt_update(void* cc, const double* const* parts, int32
 int pmc_accept_adapt(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta, double nu,
                      const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums, double* sums_copy,
                      const pmc_done_t* done, void* workspace, int64_t n, int32_t D, void* stream,
-                     const pmc_adapt_args* adapt) {
+                     const pmc_adapt_args* adapt, const pmc_gate_args* gate) {
     if (adapt && ((adapt->state && adapt->mode) || adapt->n_other) && D > 256)
         return pmc_fail("pmc_accept: device adaptation needs D <= 256");
+    if (gate && gate->calls_out && n < 1) return pmc_fail("pmc_accept: a gated launch needs rows");
     return accept_impl(kind, preconditioned, cur, prop, beta, nu, rng, alpha_out, accept_out, sums, sums_copy, true,
-                       done, workspace, n, D, stream, adapt);
+                       done, workspace, n, D, stream, adapt, gate);
 }
 
 extern "C" int pmc_logw(const double* logl, const double* beta, const double* logz, double beta_final,

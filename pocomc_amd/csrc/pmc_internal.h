@@ -57,9 +57,17 @@ struct pmc_adapt_args {
     const double* other[7];     // sums of the other row ranges (pmc_step_t.adapt_other)
     int n_other;
 };
+// the device-likelihood step's accept (pmc_step_t.lik_x): logl' gated to -inf where fin is 0 or logp' is not finite; the
+// last block writes calls_n - *bad_count to calls_out (pinned host) and zeroes *bad_count.  All NULL: no gate.
+struct pmc_gate_args {
+    const int32_t* fin;
+    unsigned* bad_count;
+    long long* calls_out;
+    long long calls_n;
+};
 int pmc_accept_adapt(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta, double nu,
                      const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums, double* sums_copy,
                      const pmc_done_t* done, void* workspace, int64_t n, int32_t D, void* stream,
-                     const pmc_adapt_args* adapt);
+                     const pmc_adapt_args* adapt, const pmc_gate_args* gate = nullptr);
 
 #endif

@@ -5,6 +5,9 @@
 //   pmc_step_pre :  [H2D mu] -> propose -> flow inverse (one launch for the affine flows) -> scaler inverse [+ prior] -> D2H x', finite
 //   pmc_step_post:  H2D logl', logp' -> accept + reductions -> D2H sums
 //
+// With a likelihood on the device (pmc_step_t.lik_x) x' goes to lik_x instead of the host, the caller's likelihood fills
+// p_logl on the same stream, and the accept gates logl' itself: no copy of x' or logl' in either direction.
+//
 // Pure sequencing of the single-purpose entry points (same kernels, same stream order); host
 // buffers must be pinned for the copies to be asynchronous.
 
@@ -71,11 +74,15 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
     // scaler inverse and (when it runs on the device) Prior.logpdf: one launch, or the epilogue of the fused sweep
     const pmc_prior_t* pr = s->prior;
     double* lp = pr ? s->p_logp : nullptr;
-    double* xT = direct ? s->h_x : s->p_xT;
-    int32_t* fin2 = direct ? s->h_fin : nullptr;
-    double* lp2 = (direct && pr) ? s->h_logp_out : nullptr;
+    // device likelihood with a device prior: x' (rejected rows filled) into lik_x, the count into clean_count; nothing goes
+    // to the host and no completion word follows (the likelihood is the next operation on the stream)
+    const bool devlik = s->lik_x && pr;
+    if (devlik && !s->clean_count) return pmc_fail("pmc_step_pre: a device likelihood needs clean_count");
+    double* xT = devlik ? s->lik_x : direct ? s->h_x : s->p_xT;
+    int32_t* fin2 = (direct && !devlik) ? s->h_fin : nullptr;
+    double* lp2 = (direct && pr && !devlik) ? s->h_logp_out : nullptr;
     pmc_done_t dn{s->h_done, (int64_t)rng->step + 1, s->done_ticket};
-    const pmc_done_t* done = (direct && s->h_done && s->done_ticket) ? &dn : nullptr;
+    const pmc_done_t* done = (direct && !devlik && s->h_done && s->done_ticket) ? &dn : nullptr;
     if (s->preconditioned && !(s->no_fuse & 1) && !pmc_tri6_preferred(s->maf) &&
         (s->inverse_algo == PMC_INVERSE_AUTO || s->inverse_algo == PMC_INVERSE_TRIANGULAR)) {
         // proposal + flow inverse (+ scaler) in one launch (affine flows, D <= 64, fewer than 16 hidden tiles).  The wider
@@ -104,6 +111,7 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
             epi.stamps = (n == g_epilogue_stamps_n) ? g_epilogue_stamps : nullptr;
 #endif
             epi.fill_x = (s->fill_rejected && epi.bad_flag && xT) ? s->cur.x : nullptr;
+            if (devlik) { epi.bad_count = s->clean_count; epi.bad_flag = nullptr; epi.fill_x = s->cur.x; }
         }
         if (s->ev_inv0) (void)hipEventRecord((hipEvent_t)s->ev_inv0, st);
         rc = pmc_launch_propose_inverse_tri4(s->kind, s->cur.theta32, mu, s->inv_cov, s->chol, nu, sigma, cn_a, rng,
@@ -126,6 +134,7 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
     pmc_scaler_extra sx{};
     const bool counted = done && s->h_clean && s->clean_count && xT && (scaled || pr);
     if (!scaled && counted) { sx.bad_count = s->clean_count; sx.bad_flag = (long long*)s->h_clean; sx.fill_x = s->fill_rejected ? s->cur.x : nullptr; }
+    if (!scaled && devlik) { sx.bad_count = s->clean_count; sx.bad_flag = nullptr; sx.fill_x = s->cur.x; }
     if (s->h_clean && !counted) *s->h_clean = -1;     // (this launch sequence does not count)
     if (scaled) {
         rc = 0;
@@ -143,7 +152,7 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
                                          lp, fin2, lp2, done, n, stream, &sx);
     }
     if (rc) return rc;
-    if (direct) return finish();
+    if (direct || devlik) return finish();
     if (pr) {
         if (hipMemcpyAsync(s->h_logp_out, s->p_logp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
             return pmc_fail("pmc_step_pre: D2H logp");
@@ -153,6 +162,34 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
         hipMemcpyAsync(s->h_fin, s->p_fin, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess)
         return pmc_fail("pmc_step_pre: D2H");
     return finish();
+}
+
+// A device likelihood's input behind a host prior (pmc_step_lik_rows): one thread per walker, x' or the current x of its
+// row into the column-major lik_x (coalesced along the walkers)
+__global__ __launch_bounds__(256) void lik_rows_kernel(const double* __restrict__ x_prop, const double* __restrict__ x_cur,
+                                                       const int32_t* __restrict__ fin, const double* __restrict__ logp,
+                                                       double* __restrict__ lik_x, unsigned* __restrict__ bad_count,
+                                                       int64_t n, int D) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const bool reach = fin[r] && isfinite(logp[r]);                 // mcmc.py:108-109
+    const double* src = (reach ? x_prop : x_cur) + r * D;
+    for (int j = 0; j < D; ++j) lik_x[(size_t)j * n + r] = src[j];
+    if (!reach) atomicAdd(bad_count, 1u);
+}
+
+extern "C" int pmc_step_lik_rows(const pmc_step_t* s, void* stream) {
+    if (!s || !s->lik_x || !s->clean_count || !s->p_x || !s->cur.x || !s->p_fin || !s->p_logp || !s->h_logp || s->D < 1)
+        return pmc_fail("pmc_step_lik_rows: needs lik_x, clean_count, p_x, cur.x, p_fin, p_logp and h_logp");
+    if (s->prior) return pmc_fail("pmc_step_lik_rows: with a device prior pmc_step_pre fills lik_x itself");
+    const int64_t n = s->n;
+    if (n <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemcpyAsync(s->p_logp, s->h_logp, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+        return pmc_fail("pmc_step_lik_rows: H2D logp");
+    hipLaunchKernelGGL(lik_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->p_x, s->cur.x, s->p_fin,
+                       s->p_logp, s->lik_x, s->clean_count, n, (int)s->D);
+    return pmc_check_launch("lik_rows_kernel");
 }
 
 extern "C" int pmc_propose_inverse(int kind, const float* cur32, const double* mu, const double* inv_cov,
@@ -181,7 +218,10 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
         rng = &rr;
     }
     const bool direct = s->host_direct && !s->p_xT;
-    if (!direct) {
+    // device likelihood: logl' is in p_logl and logp' in p_logp already (the device prior, or pmc_step_lik_rows)
+    const bool devlik = s->lik_x != nullptr;
+    if (devlik && (!s->clean_count || !s->h_calls)) return pmc_fail("pmc_step_post: a device likelihood needs clean_count and h_calls");
+    if (!direct && !devlik) {
         if (hipMemcpyAsync(s->p_logl, s->h_logl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_post: H2D");
         if (!s->prior &&     // with a device prior logp' never left the device
@@ -193,12 +233,12 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
     prop.theta64 = s->preconditioned ? s->p_theta64 : nullptr;
     prop.u = s->p_u; prop.x = s->p_x; prop.logdetj = s->p_logdetj;
     // host_direct: the accept kernel reads logl' (and a host-evaluated logp') from the pinned host buffers
-    prop.logl = direct ? s->h_logl : s->p_logl;
-    prop.logp = (direct && !s->prior) ? s->h_logp : s->p_logp;
+    prop.logl = (direct && !devlik) ? s->h_logl : s->p_logl;
+    prop.logp = (direct && !devlik && !s->prior) ? s->h_logp : s->p_logp;
     prop.logdetj_flow = s->preconditioned ? s->p_ldjf : nullptr;
     prop.quad = s->quad; prop.quad_prop = s->p_quad;
     int rc;
-    if (direct) {
+    if (direct || devlik) {
         pmc_done_t dn{s->h_done ? s->h_done + 1 : nullptr, (int64_t)rng->step + 1, nullptr};
         pmc_adapt_args ad{s->adapt_state, s->adapt_state ? s->adapt_mode : 0, s->adapt_c_sigma, s->adapt_c_mu,
                           s->adapt_cap, s->adapt_n_total, {}, 0};
@@ -208,9 +248,11 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
             ad.other[k] = s->adapt_other[k];
         }
         ad.n_other = s->adapt_n_other;
+        pmc_gate_args gate{};
+        if (devlik) gate = pmc_gate_args{s->p_fin, s->clean_count, (long long*)s->h_calls, (long long)n};
         rc = pmc_accept_adapt(s->kind, s->preconditioned, &cur, &prop, beta, nu, rng, s->alpha, s->accept, s->sums,
                               copy_sums ? s->h_sums : nullptr, (copy_sums && s->h_done) ? &dn : nullptr, s->ws, n, s->D,
-                              stream, &ad);
+                              stream, &ad, &gate);
     }
     else if (s->adapt_state && s->adapt_mode)
         return pmc_fail("pmc_step_post: adaptation on the device needs host_direct");
@@ -218,7 +260,7 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
         rc = pmc_accept(s->kind, s->preconditioned, &cur, &prop, beta, nu, rng, s->alpha, s->accept, s->sums, s->ws, n,
                         s->D, stream);
     if (rc) return rc;
-    if (copy_sums && !direct &&
+    if (copy_sums && !direct && !devlik &&
         hipMemcpyAsync(s->h_sums, s->sums, (size_t)(s->D + 4) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
         return pmc_fail("pmc_step_post: D2H sums");
     if (want_mask && s->h_accept &&

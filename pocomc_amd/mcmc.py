@@ -7,7 +7,9 @@ call; per step the device runs  propose -> flow inverse -> scaler inverse  and
 accept -> reductions  (``include/pocomc_amd.h``), the host only evaluates the
 user's prior / likelihood black boxes on the compacted finite rows
 (``mcmc.py:100-121``) and the scalar adaptation / stopping logic
-(``mcmc.py:152-180``).
+(``mcmc.py:152-180``).  With ``option_dict["device_likelihood"]`` the likelihood is a
+GPU callable too: x' stays on the device, and the host reads the sums of each step only.
+
 
 ``StepEngine`` is the reusable object (bench.py drives it directly); the four
 functions ``preconditioned_pcn | preconditioned_rwm | pcn | rwm`` wrap it with
@@ -123,6 +125,24 @@ WAIT_TIMEOUT_CAP_S = 7 * 24 * 3600.0
 def _wait_timeout(value):
     v = WAIT_TIMEOUT_DEFAULT_S if value is None else float(value)
     return WAIT_TIMEOUT_CAP_S if (v <= 0.0 or v > WAIT_TIMEOUT_CAP_S) else v
+
+def device_logl(out, n, device):
+    """The value of a device likelihood (``option_dict["device_likelihood"]``): an ``(n,)`` float64 tensor on the walkers'
+    device, a float32 one widened there.  Anything else raises ValueError naming what was received."""
+    if isinstance(out, tuple):
+        out = out[0]
+    if not isinstance(out, torch.Tensor):
+        raise ValueError(f"device likelihood: expected a ({n},) tensor on {device}, got {type(out).__name__}")
+    if tuple(out.shape) != (n,):
+        raise ValueError(f"device likelihood: expected shape ({n},), got {tuple(out.shape)}")
+    if out.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"device likelihood: expected dtype float64 or float32, got {out.dtype}")
+    dev = torch.device(device)
+    index = dev.index if (dev.index is not None or dev.type != "cuda") else torch.cuda.current_device()
+    if out.device.type != dev.type or out.device.index != index:
+        raise ValueError(f"device likelihood: expected a tensor on device {dev.type}:{index}, got one on {out.device}")
+    return out
+
 
 _POOLS = {}
 _PINNED_FREE = {}
@@ -427,6 +447,10 @@ class StepEngine:
         self.events = None       # bench.py: list of per-step HIP event tuples when not None
         self.host_timers = None  # bench.py: dict of accumulated host seconds when not None
         self.wait_timeout = _wait_timeout(None)      # seconds the driver thread spins on a completion word before it raises
+        # likelihood on the device (set_device_likelihood): x' for it in p_xl, column-major; h_calls <- rows that reached it
+        self.device_likelihood = False
+        self.p_xl = None
+        self.h_calls = None
 
     def __del__(self):
         if getattr(self, "_recycle", False):       # (only after the owner synchronised with the device: mcmc._run)
@@ -484,6 +508,21 @@ class StepEngine:
         self._step.prior = C.cast(C.pointer(desc), C.c_void_p)
         self._step.h_logp_out = self.h_logp.data_ptr()
         return True
+
+    def set_device_likelihood(self):
+        """Evaluate the likelihood on the device (:meth:`evaluate_device`): the pre-step writes x' into ``p_xl`` -- the rows
+        that do not reach the likelihood carry the walker's current x -- and the accept gates logl' itself
+        (``pmc_step_t.lik_x``).  Needs the composite path with adaptation on the device."""
+        self.p_xl = torch.empty(self.D, self.n, dtype=torch.float64, device=self.device)
+        self.h_calls = _pinned_take((1,), torch.int64)
+        self._pins.append(self.h_calls)
+        self._np_calls = self.h_calls.numpy()
+        self._clean_count.zero_()
+        self._step.lik_x = self.p_xl.data_ptr()
+        self._step.h_calls = self.h_calls.data_ptr()
+        self._step.clean_count = self._clean_count.data_ptr()
+        self.device_likelihood = True
+        self._pre_cfg = None
 
     def set_mu(self, mu):
         # pinned staging + async copy; the previous upload was consumed by a kernel that has
@@ -603,7 +642,8 @@ class StepEngine:
             self._step.h_done = self.h_done.data_ptr() if self._direct_now else None
             self._step.done_ticket = self._done_ticket.data_ptr() if self._direct_now else None
             self._step.h_clean = self.h_clean.data_ptr() if self._direct_now else None
-            self._step.clean_count = self._clean_count.data_ptr() if self._direct_now else None
+            self._step.clean_count = (self._clean_count.data_ptr() if (self._direct_now or self.device_likelihood)
+                                      else None)
             self._step.ev_pre_done = None if self._direct_now else self._ev_pre     # (the completion word replaces it)
             self._step.fill_rejected = int(bool(self.fill_rejected) and self._direct_now)
 
@@ -713,6 +753,35 @@ class StepEngine:
         logl_prime[~finite] = -np.inf
         self._upload_logs()
         return int(np.sum(finite)), blobs_prime
+
+    def evaluate_device(self, log_prior, log_like):
+        """The likelihood of the step in flight on the device (``pmc_step_t.lik_x``), on the engine's stream: the callable
+        gets ``p_xl.t()``, an (n, D) float64 view of x' (rows in walker order, column-major), and returns (logl', None);
+        logl' goes into ``p_logl``.  A prior the device does not evaluate runs on the host first, on x' and the finite mask
+        (``mcmc.py:105-107``), and ``pmc_step_lik_rows`` uploads its logp' and writes the likelihood's input.  Nothing is
+        waited for otherwise.  Returns the rows handed to the likelihood; the rows that reached it come with the sums
+        (:meth:`calls_reached`)."""
+        stream = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+        if self.prior_desc is None:
+            if self._direct_now:
+                _lib.check(self.lib.pmc_wait_flag(self.h_done.data_ptr(), self.step_idx + 1, self.wait_timeout), "pmc_wait_flag")
+            else:
+                _lib.check(self.lib.pmc_event_synchronize(self._ev_pre), "pmc_event_synchronize")
+            fin = self._np_fin.astype(bool)
+            if fin.all():
+                self._np_logp[:] = log_prior(self._np_x)
+            else:
+                self._np_logp[fin] = log_prior(self._np_x[fin])
+                self._np_logp[~fin] = -np.inf
+            _lib.check(self.lib.pmc_step_lik_rows(C.byref(self._step), self._stream), "pmc_step_lik_rows")
+        with torch.cuda.stream(stream):
+            ll = device_logl(log_like(self.p_xl.t()), self.n, self.device)
+            self.p_logl.copy_(ll)
+        return self.n
+
+    def calls_reached(self):
+        """Rows of the step just waited for (:meth:`accept_wait`) that reached the device likelihood."""
+        return int(self._np_calls[0])
 
     def _upload_logs(self):
         if not self._post_uploads:                    # the composite post step does the H2D itself
@@ -1164,15 +1233,25 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
 
     import torch.distributed as dist
     sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-    x_order = option_dict.get("x_order", "C")
+    # the likelihood is a GPU callable (tensor in, tensor out): x' never goes to the host, logl' is never uploaded
+    device_like = bool(option_dict.get("device_likelihood", False))
+    if device_like:
+        if sharded:
+            raise NotImplementedError("device_likelihood: sharded walkers (world > 1) are not supported; "
+                                      "use a host likelihood or one process")
+        if have_blobs:
+            raise ValueError("device_likelihood: blobs are not supported")
+        if replay is not None or trace is not None:
+            raise ValueError("device_likelihood: replayed variates and traces need the host likelihood")
+    x_order = "F" if device_like else option_dict.get("x_order", "C")
     # lanes > 1: row ranges whose device work overlaps the host likelihood of the others (LanedEngine); opt-in,
     # it pays when the likelihood is expensive next to the device's share of a step
     lanes = int(option_dict.get("lanes") or 1)
-    if have_blobs or trace is not None or replay is not None:
+    if have_blobs or trace is not None or replay is not None or device_like:
         lanes = 1                                   # (blobs / traces / replayed variates: whole-set bookkeeping)
     # pipelined: sigma / mu adapted on the device, the pre-step of step k+1 enqueued behind the accept of step k
     # (needs the kernels to read / write the pinned host buffers themselves: x_order 'F')
-    want_pipe = (option_dict.get("pipeline", True) and x_order == "F" and not have_blobs and trace is None
+    want_pipe = (option_dict.get("pipeline", True) and x_order == "F" and not have_blobs and trace is None and not device_like
                  and replay is None and all(option_dict.get(k, True) for k in ("host_direct", "spin_wait")))
     if lanes > 1 or want_pipe:                      # (the pipelined step lives behind pmc_pipeline_*: one lane is a pipeline too)
         eng = LanedEngine(kind, n_walkers, n_dim, flow, scaler, lanes=lanes, group=group,
@@ -1199,6 +1278,8 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     owner = getattr(log_prior, "__self__", None)
     if owner is not None and option_dict.get("device_prior", True) and hasattr(owner, "device_descriptor"):
         eng.set_device_prior(owner)                 # Prior.logpdf of uniform / normal factors on the device
+    if device_like:
+        eng.set_device_likelihood()
     eng.load_state(u, x, logdetj, logl, logp)
     nu = 0.0
     if tpcn:
@@ -1246,7 +1327,7 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     pipelined = want_pipe and eng.can_pipeline() and (laned or not sharded)
     if pipelined and laned:
         eng.start_pipeline(float(ad.sigma), ad.mu, nu)
-    elif pipelined:
+    elif pipelined or device_like:
         # adaptation on the device: the pre-step of step k+1 is enqueued right behind the accept of step k and
         # runs while the host still waits for / digests the sums of step k (which it needs for the stop rule only)
         eng.adapt_upload(float(ad.sigma), ad.mu)
@@ -1257,7 +1338,16 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
             replay.begin_step()
             rp = dict(gamma=replay.std_gamma((n_dim + nu) / 2, n_walkers) if tpcn else None,
                       z=replay.normal(n_walkers, n_dim), u=replay.uniform(n_walkers))
-        if pipelined and laned:
+        if device_like:
+            # pre-step (in flight) -> likelihood -> accept + adaptation -> the next pre-step, all on one stream; then the one
+            # wait of the step, for the sums (and the rows that reached the likelihood) the stop rule needs
+            eng.evaluate_device(log_prior, log_like)
+            eng.accept_enqueue(beta, nu, adapt=ad.coefficients(), n_total=n_total)
+            if ad.i + 1 < n_max:
+                eng.propose(None, nu, step=eng.step_idx + 1)
+            sums = eng.accept_wait()
+            calls = eng.calls_reached()
+        elif pipelined and laned:
             calls, sums = eng.step_pipelined(beta, nu, ad.coefficients(), n_total, log_prior, log_like,
                                              more=ad.i + 1 < n_max)
         elif pipelined:
@@ -1277,7 +1367,7 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
             mask = eng.h_accept.numpy().astype(bool)
             blobs[mask] = blobs_prime[mask]
         stop = ad.update(sums)
-        if kind == "preconditioned_pcn" and not pipelined:
+        if kind == "preconditioned_pcn" and not (pipelined or device_like):
             eng.set_mu(ad.mu)
         if trace is not None:
             trace.append(dict(alpha=eng.alpha.cpu().numpy(), accept=eng.h_accept.numpy().astype(bool).copy(),
@@ -1291,7 +1381,7 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
                                            logP=sums[1] / n_total, eff=ad.sigma / (2.38 / np.sqrt(n_dim))))
         if stop:
             break
-    if pipelined:
+    if pipelined or device_like:
         # a pre-step launched ahead of a plateau stop is still in flight; it touches proposal buffers only
         if laned:
             eng.finish_pipeline()

@@ -144,7 +144,8 @@ class Sampler:
                  transform="probit", pool=None, pytorch_threads=1, flow="nsf6", train_config=None,
                  train_frequency=None, precondition=True, dynamic=True, metric="ess", n_prior=None,
                  sample="tpcn", n_steps=None, n_max_steps=None, resample="mult", output_dir=None,
-                 output_label=None, random_state=None, n_ess=None, group=None, mcmc_options=None):
+                 output_label=None, random_state=None, n_ess=None, group=None, mcmc_options=None,
+                 device_likelihood=False):
         """Arguments and defaults of ``pocomc/sampler.py:154-185``, plus
 
         ``group``         a ``torch.distributed`` process group (default: the initialised default group): one process
@@ -152,7 +153,13 @@ class Sampler:
                           replicate the pool bookkeeping from the same numpy / torch streams);
         ``mcmc_options``  extra keys of the MCMC kernels' ``option_dict`` (``pocomc_amd/mcmc.py``), e.g.
                           ``dict(x_order='F')`` (Fortran-ordered ``x`` for the likelihood, pipelined kernel call),
-                          ``dict(lanes=2)``.
+                          ``dict(lanes=2)``;
+        ``device_likelihood``  (needs ``vectorize=True``, no blobs, one process) the likelihood runs on the GPU: it is
+                          called with an ``(n, D)`` float64 tensor on the flow's device (rows in walker order; a column-major
+                          view inside the MCMC steps) on the current torch stream and returns an ``(n,)`` float64 or
+                          float32 tensor on that device.  It must be row-wise and free of side effects, and must not keep
+                          its input, whose buffer is reused.  In the MCMC steps x' never goes to the host and logl' is
+                          never uploaded.
 
         Supported ``train_config`` keys: those of ``sampler.py:287-299`` (``validation_split, epochs, batch_size,
         patience, learning_rate, annealing, gaussian_scale, laplace_scale, noise, shuffle, clip_grad_norm, verbose``),
@@ -191,6 +198,14 @@ class Sampler:
         self.n_steps = D // 2 if n_steps is None else int(n_steps)                       # sampler.py:244
         self.n_max_steps = 10 * self.n_steps if n_max_steps is None else int(n_max_steps)   # :250
         self.vectorize = vectorize
+        self.device_likelihood = bool(device_likelihood)
+        if self.device_likelihood:
+            if not vectorize:
+                raise ValueError("device_likelihood=True needs vectorize=True: the likelihood is called on whole blocks of rows")
+            if self.have_blobs:
+                raise ValueError("device_likelihood=True does not support blobs (blobs_dtype)")
+            if self.ranks.world > 1:
+                raise NotImplementedError("device_likelihood=True is not supported for a sharded Sampler (world > 1)")
         if vectorize and self.have_blobs:
             raise ValueError("Cannot vectorize likelihood with blobs.")
         self.pool, self.distribute = pool, map
@@ -433,6 +448,9 @@ class Sampler:
         opts = dict(n_max=self.n_max_steps, n_steps=self.n_steps, progress_bar=self.pbar,
                     proposal_scale=self.proposal_scale, device_state=True)
         opts.update(self.mcmc_options)
+        if self.device_likelihood:
+            funcs["loglike"] = lambda xt: (self.log_likelihood(xt), None)
+            opts["device_likelihood"] = True
         if self.world > 1:
             opts.update(group=self.group, shard_offset=sl.start)
         res = _KERNELS[(bool(self.preconditioned), self.sample)](state, funcs, opts)
@@ -490,6 +508,11 @@ class Sampler:
 
     def _log_like_all(self, x):
         """The likelihood of all rows of ``x`` (identical on every rank), each rank evaluating its share."""
+        if self.device_likelihood:
+            # (warm-up and evidence: the rows go up, the values come back)
+            xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.flow.device)
+            logl = _mcmc.device_logl(self.log_likelihood(xt), len(x), self.flow.device)
+            return logl.to(torch.float64).cpu().numpy(), None
         if self.world == 1:
             return self._log_like(x)
         sl = self.ranks.share(len(x))
