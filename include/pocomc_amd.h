@@ -302,19 +302,42 @@ int pmc_scaler_forward(const pmc_scaler_t* s, const double* x, double* u, int64_
 /* ----------------------------------------------------------------- prior */
 
 /* pocomc/prior.py: a product of frozen scipy.stats distributions.  Unlike the likelihood it is not a
- * user black box: the families below are evaluated on the device, everything else stays on the host. */
-#define PMC_PRIOR_UNIFORM 1   /* scipy.stats.uniform(loc, scale) */
-#define PMC_PRIOR_NORM 2      /* scipy.stats.norm(loc, scale) */
+ * user black box: the families below are evaluated on the device, everything else stays on the host.
+ * Every family is scipy's logpdf(x) = _logpdf(z; shapes) - log(scale), z = (x - loc) / scale, with scipy's support
+ * test on z.  Families 1 and 2 need family / loc / scale only; the others read their shapes and constants from par
+ * (rows 0-2 as listed, unlisted rows unused; row 3 log(scale)), all computed on the host in float64 with scipy.special. */
+#define PMC_PRIOR_UNIFORM 1     /* scipy.stats.uniform(loc, scale) */
+#define PMC_PRIOR_NORM 2        /* scipy.stats.norm(loc, scale) */
+#define PMC_PRIOR_TRUNCNORM 3   /* truncnorm(a, b):    par = a, b, log-mass of [a, b] */
+#define PMC_PRIOR_LOGUNIFORM 4  /* loguniform / reciprocal(a, b):  par = a, b, log(log(b) - log(a)) */
+#define PMC_PRIOR_LOGNORM 5     /* lognorm(s):         par = s, 2 s^2 */
+#define PMC_PRIOR_HALFNORM 6    /* halfnorm:           par = -, -, 0.5 log(2 / pi) */
+#define PMC_PRIOR_EXPON 7       /* expon */
+#define PMC_PRIOR_GAMMA 8       /* gamma(a):           par = a - 1, -, gammaln(a) */
+#define PMC_PRIOR_INVGAMMA 9    /* invgamma(a):        par = a + 1, -, gammaln(a) */
+#define PMC_PRIOR_BETA 10       /* beta(a, b):         par = a - 1, b - 1, betaln(a, b) */
+#define PMC_PRIOR_CAUCHY 11     /* cauchy:             par = -, -, log(pi) */
+#define PMC_PRIOR_HALFCAUCHY 12 /* halfcauchy:         par = -, -, log(2 / pi) */
+#define PMC_PRIOR_LAPLACE 13    /* laplace */
+#define PMC_PRIOR_T 14          /* t(df):              par = df, (df + 1) / 2, log(poch(df/2, 1/2)) - (log(df) + log(pi)) / 2;
+                                   df = inf: the normal */
+#define PMC_PRIOR_NPAR 4        /* rows of pmc_prior_t.par: three family constants (as above), then log(scale) */
 typedef struct pmc_prior {
     const int32_t* family;    /* [D] */
     const double* loc;        /* [D] */
     const double* scale;      /* [D] */
     int32_t D;
     int32_t reserved;
+    /* appended within ABI 9: families 1 and 2 ignore these */
+    const double* par;        /* [PMC_PRIOR_NPAR][D] (row k of dimension j at par[k * D + j]), or NULL */
+    int32_t n_extended;       /* number of factors of families 3.. : they need par, and take the scaler launch of their own
+                                 in pmc_step_pre instead of the epilogue of the fused sweep */
+    int32_t reserved2;
 } pmc_prior_t;
 
 /* Prior.logpdf, prior.py:70-100, with the gating of mcmc.py:105-107: logp[k] = -inf where finite[k] == 0
- * (finite may be NULL).  x f64 [n][D], logp f64 [n]. */
+ * (finite may be NULL).  x f64 [n][D], logp f64 [n].  Fails when n_extended > 0 and par is NULL.  A non-finite x
+ * without the mask gives a non-finite logp. */
 int pmc_prior_logpdf(const pmc_prior_t* pr, const double* x, const int32_t* finite, double* logp, int64_t n,
                      void* stream);
 

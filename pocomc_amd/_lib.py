@@ -61,7 +61,8 @@ class pmc_done_t(C.Structure):
 
 
 class pmc_prior_t(C.Structure):
-    _fields_ = [("family", c_p), ("loc", c_p), ("scale", c_p), ("D", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("family", c_p), ("loc", c_p), ("scale", c_p), ("D", C.c_int32), ("reserved", C.c_int32),
+                ("par", c_p), ("n_extended", C.c_int32), ("reserved2", C.c_int32)]
 
 
 class pmc_rng_t(C.Structure):

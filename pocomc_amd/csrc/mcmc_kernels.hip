@@ -115,6 +115,7 @@ __global__ __launch_bounds__(PROP_ROWS) void propose_kernel(
 }
 
 #include "scaler_body.h"
+#include "prior_body.h"
 
 // SCL_THREADS threads per block: the probit / logit maps are long dependent f64 chains, so the block's 64 x D elements
 // are spread over as many lanes as a block can have (four elements per lane at D = 32 instead of eight; 1024 threads would halve the registers of a lane and spill)
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(SCL_THREADS) void scaler_inverse_kernel(
             double lp = -INFINITY;
             if (fin) {
                 lp = 0.0;
-                for (int j = 0; j < D; ++j) lp += prior_term(pr, j, Xt[j * (SCL_ROWS + 1) + tid]);
+                for (int j = 0; j < D; ++j) lp += prior_term_any(pr, j, Xt[j * (SCL_ROWS + 1) + tid]);
             }
             logp_out[row0 + tid] = lp;
             if (logp_copy) logp_copy[row0 + tid] = lp;
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(256) void scaler_forward_kernel(pmc_scaler_t s, con
 }
 
 // ===========================================================================
-// Prior.logpdf (pocomc/prior.py:70-100) for the scipy.stats families the device knows:
+// Prior.logpdf (pocomc/prior.py:70-100) for the scipy.stats families the device knows (prior_body.h):
 // logp = sum_j dist_j.logpdf(x[:, j]), accumulated dimension after dimension like the reference
 // ===========================================================================
 __global__ __launch_bounds__(256) void prior_logpdf_kernel(pmc_prior_t pr, const double* __restrict__ x,
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(256) void prior_logpdf_kernel(pmc_prior_t pr, const
         if (!finite || finite[k]) {                                  // mcmc.py:105-107
             lp = 0.0;
             const double* xr = x + k * D;
-            for (int j = 0; j < D; ++j) lp += prior_term(pr, j, xr[j]);
+            for (int j = 0; j < D; ++j) lp += prior_term_any(pr, j, xr[j]);
         }
         logp[k] = lp;
     }
@@ -243,6 +244,8 @@ extern "C" int pmc_prior_logpdf(const pmc_prior_t* pr, const double* x, const in
                                 int64_t n, void* stream) {
     if (!pr || !pr->family || !pr->loc || !pr->scale || pr->D < 1 || !x || !logp || n < 0)
         return pmc_fail("pmc_prior_logpdf: bad argument");
+    if (pr->n_extended < 0 || (pr->n_extended > 0 && !pr->par))
+        return pmc_fail("pmc_prior_logpdf: factors other than uniform / normal need the parameter table (par)");
     if (n == 0) return 0;
     int64_t grid = (n + 255) / 256; if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(prior_logpdf_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, *pr, x, finite,
@@ -755,6 +758,8 @@ int pmc_scaler_inverse_prior_ex(const pmc_scaler_t* s, const pmc_prior_t* prior,
     if (logp_copy && !logp) return pmc_fail("pmc_scaler_inverse_prior: logp_copy without logp");
     if (prior && (!prior->family || !prior->loc || !prior->scale || prior->D != s->D))
         return pmc_fail("pmc_scaler_inverse_prior: bad prior descriptor");
+    if (prior && (prior->n_extended < 0 || (prior->n_extended > 0 && !prior->par)))
+        return pmc_fail("pmc_scaler_inverse_prior: factors other than uniform / normal need the parameter table (par)");
     pmc_prior_t pr_val = {};
     if (prior) pr_val = *prior;
     pmc_scaler_extra ex{};

@@ -115,8 +115,20 @@ __device__ __forceinline__ double apply_bc(const pmc_scaler_t& s, int j, double 
     return x;
 }
 
-// one factor of Prior.logpdf (pocomc/prior.py:70-100), shared by prior_logpdf_kernel and the fused scaler kernel
-__device__ __forceinline__ double prior_term(const pmc_prior_t& pr, int j, double xv) {
+// The two families the epilogues of the fused sweeps evaluate: pmc_prior_t up to `reserved` (a prior with a factor of
+// another family takes the scaler launch of its own, prior_body.h)
+struct pmc_prior_un_t {
+    const int32_t* family;
+    const double* loc;
+    const double* scale;
+    int32_t D;
+    int32_t reserved;
+};
+
+// one uniform / normal factor of Prior.logpdf (pocomc/prior.py:70-100), shared by prior_logpdf_kernel, the scaler kernel
+// and the epilogues of the fused sweeps (P: pmc_prior_t or pmc_prior_un_t)
+template <class P>
+__device__ __forceinline__ double prior_term(const P& pr, int j, double xv) {
     const double loc = pr.loc[j], sc = pr.scale[j];
     if (pr.family[j] == PMC_PRIOR_UNIFORM) {
         // scipy uniform(loc, scale).logpdf: -log(scale) on [loc, loc+scale], -inf outside
@@ -136,7 +148,7 @@ __device__ __forceinline__ double prior_term(const pmc_prior_t& pr, int j, doubl
 struct ScalerEpi {
     int on, have_prior;
     pmc_scaler_t s;
-    pmc_prior_t pr;
+    pmc_prior_un_t pr;
     double* u_out; double* x_out; double* x_colmajor; double* ldj_out; int32_t* finite_out;
     double* logp_out; int32_t* finite_copy; double* logp_copy;
     unsigned* done_ticket; long long* done_flag; long long done_value;

@@ -95,11 +95,13 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
         ScalerEpi epi{};
         const bool want_epi = !(s->no_fuse & 2) && s->scaler && s->scaler->low && s->scaler->high && s->scaler->kind &&
                               s->scaler->log_width && (!s->scaler->scale || (s->scaler->mu && s->scaler->sigma)) &&
-                              (!pr || (pr->family && pr->loc && pr->scale && pr->D == D));
+                              (!pr || (pr->family && pr->loc && pr->scale && pr->D == D && pr->n_extended == 0));
+        // (the epilogues evaluate uniform / normal factors only: a prior with a factor of another family keeps the scaler
+        //  launch of its own, which counts, fills and hands over x' the same way)
         if (want_epi) {
             epi.s = *s->scaler;
             epi.have_prior = pr ? 1 : 0;
-            if (pr) epi.pr = *pr;
+            if (pr) epi.pr = pmc_prior_un_t{pr->family, pr->loc, pr->scale, pr->D, pr->reserved};
             epi.u_out = s->p_u; epi.x_out = s->p_x; epi.x_colmajor = xT; epi.ldj_out = s->p_logdetj;
             epi.finite_out = s->p_fin; epi.logp_out = lp; epi.finite_copy = fin2; epi.logp_copy = lp2;
             epi.done_ticket = done ? done->ticket : nullptr;

@@ -497,9 +497,11 @@ class StepEngine:
             self.set_mu(mu)
 
     def set_device_prior(self, prior):
-        """Evaluate ``prior.logpdf`` (a product of uniform / normal ``scipy.stats`` factors) on the
-        device right after the scaler instead of on the host.  Returns False if the prior has a factor
-        the device does not know (then it stays a host callback)."""
+        """Evaluate ``prior.logpdf`` on the device right after the scaler instead of on the host: a product of
+        ``scipy.stats`` factors the device knows -- uniform / normal for ``Prior(dists)``, the families of
+        ``prior.DEVICE_FAMILIES`` for ``Prior(dists, device=True)``.  Returns False if the prior gives no descriptor
+        (a factor the device does not know under ``device="auto"``, or ``device=False``); then it stays a host
+        callback."""
         desc = prior.device_descriptor(self.device) if hasattr(prior, "device_descriptor") else None
         if desc is None:
             return False
@@ -1277,7 +1279,7 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
         tune(prefetcher=host_prefetch(eng.lib, int(option_dict["host_prefetch"]), option_dict.get("host_prefetch_cores")))
     owner = getattr(log_prior, "__self__", None)
     if owner is not None and option_dict.get("device_prior", True) and hasattr(owner, "device_descriptor"):
-        eng.set_device_prior(owner)                 # Prior.logpdf of uniform / normal factors on the device
+        eng.set_device_prior(owner)                 # Prior.logpdf on the device when the Prior gives a descriptor
     if device_like:
         eng.set_device_likelihood()
     eng.load_state(u, x, logdetj, logl, logp)

@@ -1,15 +1,94 @@
 """``Prior`` -- host-side mirror of ``pocomc/prior.py``: a product of frozen
 ``scipy.stats`` distributions.  It is a host black box like the likelihood
 (SURVEY.md section 2 row 8); uniform / normal factors are evaluated with one vectorised numpy
-expression instead of one scipy call per dimension (same values)."""
+expression instead of one scipy call per dimension (same values).
+
+The MCMC step can evaluate it on the device instead (``device_descriptor``, ``include/pocomc_amd.h`` pmc_prior_t):
+``device="auto"`` does so for products of uniform / normal factors (the device's values are scipy's bit for bit),
+``device=True`` for every family in ``DEVICE_FAMILIES`` (scipy's values to ~1e-12 relative, the same support),
+``device=False`` never."""
 from __future__ import annotations
 
 import numpy as np
 
+# scipy.stats name -> PMC_PRIOR_* family code (include/pocomc_amd.h)
+DEVICE_FAMILIES = {"uniform": 1, "norm": 2, "truncnorm": 3, "loguniform": 4, "reciprocal": 4, "lognorm": 5,
+                   "halfnorm": 6, "expon": 7, "gamma": 8, "invgamma": 9, "beta": 10, "cauchy": 11, "halfcauchy": 12,
+                   "laplace": 13, "t": 14}
+NPAR = 4           # PMC_PRIOR_NPAR: three family constants, then log(scale)
+
+
+def _log_gauss_mass(a, b):
+    """log of the normal mass of [a, b], as scipy's truncnorm computes it (so that far-tail truncations agree)."""
+    try:
+        from scipy.stats._continuous_distns import _log_gauss_mass as lgm
+        return float(lgm(a, b))
+    except ImportError:                                   # (private helper moved: take it from truncnorm.logpdf itself)
+        from scipy.stats import norm, truncnorm
+        z = 0.5 * (a + b) if np.isfinite(a) and np.isfinite(b) else (b - 1.0 if np.isfinite(b) else
+                                                                      a + 1.0 if np.isfinite(a) else 0.0)
+        return float(norm.logpdf(z) - truncnorm.logpdf(z, a, b))
+
+
+def _factor(j, d):
+    """(family code, loc, scale, (p0, p1, p2)) of factor j for the device, or ValueError naming it.  The constants are
+    computed in float64 the way scipy's ``_logpdf`` computes them (scipy.special)."""
+    import scipy.special as sc
+    dist = getattr(d, "dist", None)
+    name = getattr(dist, "name", None)
+    if name is None or not hasattr(d, "args") or not hasattr(d, "kwds"):
+        raise ValueError(f"Prior(device=True): dimension {j}: {type(d).__name__} is not a frozen scipy.stats distribution")
+    if name not in DEVICE_FAMILIES:
+        raise ValueError(f"Prior(device=True): dimension {j}: the device does not evaluate scipy.stats.{name} "
+                         f"(it evaluates {', '.join(sorted(DEVICE_FAMILIES))})")
+    try:
+        shapes, loc, scale = dist._parse_args(*d.args, **d.kwds)
+        shapes = tuple(float(v) for v in shapes)
+        loc, scale = float(loc), float(scale)
+        ok = bool(np.all(dist._argcheck(*shapes))) if shapes else True
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"Prior(device=True): dimension {j}: scipy.stats.{name}: {e}") from None
+    if not (ok and np.isfinite(loc) and np.isfinite(scale) and scale > 0 and not np.isnan(shapes).any()):
+        raise ValueError(f"Prior(device=True): dimension {j}: scipy.stats.{name}{shapes} with loc={loc}, scale={scale} "
+                         "has invalid parameters")
+    p = (0.0, 0.0, 0.0)
+    if name == "truncnorm":
+        a, b = shapes
+        p = (a, b, _log_gauss_mass(a, b))
+    elif name in ("loguniform", "reciprocal"):
+        a, b = shapes
+        p = (a, b, float(np.log(np.log(b) - np.log(a))))
+    elif name == "lognorm":
+        s, = shapes
+        p = (s, 2 * (s * s), 0.0)
+    elif name == "halfnorm":
+        p = (0.0, 0.0, float(0.5 * np.log(2.0 / np.pi)))
+    elif name == "gamma":
+        a, = shapes
+        p = (a - 1.0, 0.0, float(sc.gammaln(a)))
+    elif name == "invgamma":
+        a, = shapes
+        p = (a + 1, 0.0, float(sc.gammaln(a)))
+    elif name == "beta":
+        a, b = shapes
+        p = (a - 1.0, b - 1.0, float(sc.betaln(a, b)))
+    elif name == "cauchy":
+        p = (0.0, 0.0, float(np.log(np.pi)))
+    elif name == "halfcauchy":
+        p = (0.0, 0.0, float(np.log(2.0 / np.pi)))
+    elif name == "t":
+        df, = shapes
+        p = (df, np.inf, 0.0) if np.isinf(df) else \
+            (df, (df + 1) / 2, float(np.log(sc.poch(0.5 * df, 0.5)) - 0.5 * (np.log(df) + np.log(np.pi))))
+    return DEVICE_FAMILIES[name], loc, scale, p
+
 
 class Prior:
-    def __init__(self, dists=None):
+    def __init__(self, dists=None, device="auto"):
+        if device not in ("auto", True, False):
+            raise ValueError(f"Prior: device must be 'auto', True or False, got {device!r}")
         self.dists = dists
+        self.device = device
         self._fast = None
         try:
             kinds = [d.dist.name for d in dists]
@@ -19,28 +98,61 @@ class Prior:
                 self._fast = (np.array([k == "uniform" for k in kinds]), loc, scale)
         except Exception:
             self._fast = None
+        if device is True:
+            self.device_table()                           # every factor must be one the device evaluates
 
     # ---------------------------------------------------------------- device
-    def device_descriptor(self, device=None):
-        """``pmc_prior_t`` for the MCMC engine, or ``None`` when a factor is not a family the device
-        evaluates (then ``logpdf`` is called on the host like any black box)."""
-        if self._fast is None:
+    def device_table(self):
+        """The device's description of the prior as numpy arrays -- ``family`` (int32 [D], PMC_PRIOR_*), ``loc``,
+        ``scale`` (float64 [D]) and ``par`` (float64 [NPAR, D]: the family constants of include/pocomc_amd.h, then
+        log(scale); None when every factor is uniform / normal) -- or None when the prior stays on the host
+        (``device=False``, or ``"auto"`` with a factor that is not uniform / normal).  ``device=True`` raises ValueError
+        for the first factor the device does not evaluate.  No torch, no GPU."""
+        if self.device is False:
             return None
+        if self.device == "auto":
+            if self._fast is None:
+                return None
+            is_u, loc, scale = self._fast
+            return dict(family=np.where(is_u, 1, 2).astype(np.int32), loc=loc.copy(), scale=scale.copy(), par=None)
+        rows = [_factor(j, d) for j, d in enumerate(self.dists)]
+        family = np.array([r[0] for r in rows], np.int32)
+        loc = np.array([r[1] for r in rows], float)
+        scale = np.array([r[2] for r in rows], float)
+        par = None
+        if (family > 2).any():
+            par = np.empty((NPAR, len(rows)))
+            par[:3] = np.array([r[3] for r in rows], float).T
+            par[3] = np.log(scale)
+        return dict(family=family, loc=loc, scale=scale, par=par)
+
+    def device_descriptor(self, device=None):
+        """``pmc_prior_t`` for the MCMC engine (``device_table`` uploaded once), or ``None`` when the prior stays on the
+        host (then ``logpdf`` is called on the host like any black box)."""
         if getattr(self, "_ddesc", None) is None:
+            tab = self.device_table()
+            if tab is None:
+                return None
             import torch
             from . import _lib
             dev = device if device is not None else _lib.require_gpu()
-            is_u, loc, scale = self._fast
-            fam = np.where(is_u, 1, 2).astype(np.int32)
-            self._dtensors = [torch.from_numpy(a).to(dev) for a in (fam, loc.copy(), scale.copy())]
+            arrs = [tab["family"], tab["loc"], tab["scale"]] + ([] if tab["par"] is None else [tab["par"]])
+            self._dtensors = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrs]
+            n_ext = int((tab["family"] > 2).sum())
             self._ddesc = _lib.pmc_prior_t(family=self._dtensors[0].data_ptr(), loc=self._dtensors[1].data_ptr(),
-                                           scale=self._dtensors[2].data_ptr(), D=len(fam), reserved=0)
+                                           scale=self._dtensors[2].data_ptr(), D=len(tab["family"]), reserved=0,
+                                           par=self._dtensors[3].data_ptr() if n_ext else None, n_extended=n_ext,
+                                           reserved2=0)
         return self._ddesc
 
     def __getstate__(self):
         st = self.__dict__.copy()
         st.pop("_ddesc", None); st.pop("_dtensors", None)
         return st
+
+    def __setstate__(self, st):
+        st.setdefault("device", "auto")                   # (states saved before the choice existed)
+        self.__dict__.update(st)
 
     def logpdf(self, x):
         """``pocomc/prior.py:70-100``."""
