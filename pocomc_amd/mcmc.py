@@ -25,14 +25,32 @@ from __future__ import annotations
 import ctypes as C
 import os
 import time
+from functools import partial
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _lib
 
 KINDS = ("preconditioned_pcn", "preconditioned_rwm", "pcn", "rwm")
 PMC_KIND_TPCN, PMC_KIND_RWM = 0, 1
+
+
+# --------------------------------------------------------------------------
+# Every environment variable this module reads.  All but the first are read again at each use: the tests set them with
+# monkeypatch.setenv after the import.
+# --------------------------------------------------------------------------
+# seconds, the default of StepEngine.wait_timeout; read once, at import (set by whoever launches a run)
+def _env_wait_timeout(): return float(os.environ.get("PMC_WAIT_TIMEOUT", "600"))
+# bit 0: proposal and sweep as separate launches, bit 1: the scaler too; every StepEngine() -- the tests' fused-versus-unfused runs
+def _env_no_fuse(): return int(os.environ.get("PMC_NO_FUSE", "0"))
+# 0: the pipelined step enqueued from Python where the C pipeline would serve; every LanedEngine() -- the tests compare the two
+def _env_c_pipeline(): return os.environ.get("PMC_C_PIPELINE", "1") != "0"
+# 0: the sharded step all-reduces through torch.distributed, not inside the library; every small_comm() -- the sharded tests
+def _env_c_allreduce(): return os.environ.get("PMC_C_ALLREDUCE", "1") != "0"
+# device | host: the one kind of mailbox to try (default: device, then host); every small_comm() -- the sharded tests run both
+def _env_comm_mailbox(): return os.environ.get("PMC_COMM_MAILBOX", "")
 
 
 # --------------------------------------------------------------------------
@@ -118,13 +136,14 @@ class Adaptation:
 # likelihood raises it through option_dict["wait_timeout"] / PMC_WAIT_TIMEOUT.  It is a property of the engine
 # (``StepEngine.wait_timeout``), never of the process; values <= 0 or above the cap mean the cap (a dead peer or a hung
 # device must surface as an error, not as a silent spin).
-WAIT_TIMEOUT_DEFAULT_S = float(os.environ.get("PMC_WAIT_TIMEOUT", "600"))
+WAIT_TIMEOUT_DEFAULT_S = _env_wait_timeout()
 WAIT_TIMEOUT_CAP_S = 7 * 24 * 3600.0
 
 
 def _wait_timeout(value):
     v = WAIT_TIMEOUT_DEFAULT_S if value is None else float(value)
     return WAIT_TIMEOUT_CAP_S if (v <= 0.0 or v > WAIT_TIMEOUT_CAP_S) else v
+
 
 def device_logl(out, n, device):
     """The value of a device likelihood (``option_dict["device_likelihood"]``): an ``(n,)`` float64 tensor on the walkers'
@@ -142,6 +161,14 @@ def device_logl(out, n, device):
     if out.device.type != dev.type or out.device.index != index:
         raise ValueError(f"device likelihood: expected a tensor on device {dev.type}:{index}, got one on {out.device}")
     return out
+
+
+def _timed(fn, timers, key):
+    """``fn`` of one argument, its wall time added to ``timers[key]`` (bench.py's host clocks)."""
+    def call(a):
+        t = time.perf_counter(); r = fn(a); timers[key] += time.perf_counter() - t
+        return r
+    return call
 
 
 _POOLS = {}
@@ -186,14 +213,18 @@ def _host_pool(n_threads, cores=None):
     return _POOLS[key]
 
 
+def _sharded(group):
+    """Whether the walkers are row-sharded over more than one rank of ``group``."""
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+
+
 def allreduce_sums(sums_dev, group=None):
     """Sum the per-shard reductions over all ranks (no-op without a process group) IN RANK ORDER: beyond two ranks the
     shards are all-gathered and added ((r0 + r1) + r2) + ..., so the bits of sigma, mu and of the stop rule do not depend
     on the backend's reduction algorithm (gloo's ring, RCCL's tree) and equal the library's own exchange
     (``pmc_comm_adapt_update`` adds the ranks' mailbox slots in the same order).  D + 4 doubles per rank: the gather costs
     what the all-reduce costs."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+    if _sharded(group):
         world = dist.get_world_size(group)
         if world == 2:
             dist.all_reduce(sums_dev, op=dist.ReduceOp.SUM, group=group)      # (a + b: the same double in either order)
@@ -213,7 +244,6 @@ _COMMS = {}
 def _group_key(group):
     """What identifies a process group across its lifetime: the global ranks of its members (``id(group)`` can be recycled
     for another subgroup once a group is gone)."""
-    import torch.distributed as dist
     if group is None:
         return ("world", dist.get_world_size())
     try:
@@ -241,8 +271,7 @@ def small_comm(lib, group, width):
     through hipIpc handles (xGMI peer stores), then pinned host memory in POSIX shared memory (PCIe).  One node, one
     process per GPU, <= 8 ranks; returns None where that does not hold, where neither kind passes its self-test exchange,
     or with ``PMC_C_ALLREDUCE=0`` (the step then exchanges through ``torch.distributed``)."""
-    import torch.distributed as dist
-    if os.environ.get("PMC_C_ALLREDUCE", "1") == "0":
+    if not _env_c_allreduce():
         return None
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     if world > 8:
@@ -252,7 +281,7 @@ def small_comm(lib, group, width):
     if c is not None and c[1] >= width:
         return c[0]
     w = max(int(width), 260)                          # (D <= 256: one communicator serves every engine of the group)
-    want = os.environ.get("PMC_COMM_MAILBOX", "")
+    want = _env_comm_mailbox()
     kinds = [k for k in ("device", "host") if want in ("", k)]
     h = None
     for kind in kinds:
@@ -264,7 +293,6 @@ def small_comm(lib, group, width):
 
 
 def _try_comm(lib, group, world, rank, w, kind):
-    import torch.distributed as dist
     h = (lib.pmc_comm_create if kind == "device" else lib.pmc_comm_create_host)(rank, world, w)
     ok = bool(h)
     buf = (C.c_ubyte * 64)()
@@ -346,7 +374,6 @@ class StepEngine:
         self.mu_d, self.inv_cov_d, self.chol_d = f64(D), f64(D, D), f64(D, D)
         # replay variates
         self.r_gamma, self.r_normal, self.r_uniform = f64(n), f64(n, D), f64(n)
-        # pinned host mirrors
         # pinned host mirrors come from a process-wide free list: page-locking costs ~1 ms per buffer, and the
         # Sampler builds an engine per kernel call
         self._pins = []
@@ -394,7 +421,7 @@ class StepEngine:
             h_mu=self.h_mu.data_ptr() if self.tpcn else None, h_x=self.h_x.data_ptr(), h_fin=self.h_fin.data_ptr(),
             h_logl=self.h_logl.data_ptr(), h_logp=self.h_logp.data_ptr(), h_sums=self.h_sums.data_ptr(),
             h_accept=self.h_accept.data_ptr(),
-            no_fuse=int(os.environ.get("PMC_NO_FUSE", "0")))     # A/B: bit 0 separate proposal / inverse, bit 1 separate scaler
+            no_fuse=_env_no_fuse())
         self._rng_fast = _lib.pmc_rng_t(gamma=None, normal=None, uniform=None, seed=self.seed, step=0,
                                         offset=self.offset)
         # throughput mode: the Philox variates of step k+1 are generated behind step k's kernels, while the host
@@ -428,23 +455,22 @@ class StepEngine:
         self.fill_rejected_max = 0.05
         self._direct_now = False
         self._pre_cfg = None     # switches the composite pre-step's struct fields were last written for
-        # adaptation on the device (pmc_step_t.adapt_state): {sigma, cn_a, mu[D]}; see run_pipelined
+        # adaptation on the device (pmc_step_t.adapt_state): {sigma, cn_a, mu[D]}; see LanedEngine.step_pipelined
         self.adapt_state = f64(D + 2)
         self._h_adapt = pin(D + 2)
         self.device_adapt = False
         self.prior_desc = None   # pmc_prior_t when Prior.logpdf runs on the device (set_device_prior)
-        self.composite = True    # one C call before / after the host black boxes (pmc_step_pre / _post)
-        # x_order 'F' on the composite path: the scaler kernel writes x', the finite mask and logp' straight
-        # into the pinned host buffers (and the proposal reads mu from one) -- no copy operations in the pre-step
+        # x_order 'F' behind the composite entry points (pmc_step_pre / _post: one C call before / after the host black
+        # boxes): the scaler kernel writes x', the finite mask and logp' straight into the pinned host buffers (and the
+        # proposal reads mu from one) -- no copy operations in the pre-step
         self.host_direct = (x_order == "F")
-        self._post_uploads = False
         self.step_idx = 0
         self.host_threads = 1    # >1: evaluate the black boxes on row chunks, this thread + (host_threads - 1) pool threads
         self.host_cores = None   # optional list of cores the pool's threads are pinned to (one each)
         self.prefetcher = None   # handle of pmc_prefetcher_create (shared by the lanes of a walker set), see host_prefetch()
         self._pool = None
         self.stream = None       # torch.cuda.Stream of the composite path (LanedEngine); None: the current one
-        self.events = None       # bench.py: list of per-step HIP event tuples when not None
+        self.events = None       # bench.py: list of per-step HIP event tuples when not None (see _instrumented)
         self.host_timers = None  # bench.py: dict of accumulated host seconds when not None
         self.wait_timeout = _wait_timeout(None)      # seconds the driver thread spins on a completion word before it raises
         # likelihood on the device (set_device_likelihood): x' for it in p_xl, column-major; h_calls <- rows that reached it
@@ -465,12 +491,22 @@ class StepEngine:
                 pass
             self._ev_pre = None
 
+    def _instrumented(self):
+        """bench.py's event pass: one launch per stage (``pmc_propose`` / ``pmc_maf_inverse`` / ``pmc_scaler_inverse`` /
+        ``pmc_prior_logpdf`` / ``pmc_accept``), HIP events between them, instead of ``pmc_step_pre`` / ``pmc_step_post``."""
+        return self.events is not None
+
     def _ev(self):
         e = torch.cuda.Event(enable_timing=True)
         e.record(torch.cuda.current_stream())
         return e
 
     # ---------------------------------------------------------------- setup
+    def configure(self, **kw):
+        """Set switches of the engine by name (``host_direct``, ``rng_prefill``, ``wait_timeout``, ...)."""
+        for k, v in kw.items():
+            setattr(self, k, v)
+
     def load_state(self, u, x, logdetj, logl, logp):
         """numpy arrays or (device) tensors: a walker set that already lives in HBM (the Sampler's pool) is copied
         device to device."""
@@ -530,8 +566,8 @@ class StepEngine:
         # pinned staging + async copy; the previous upload was consumed by a kernel that has
         # completed (accept_reduce synchronises) before the host buffer is rewritten
         self._np_mu[:] = mu
-        if not (self.composite and self.events is None):
-            self.mu_d.copy_(self.h_mu, non_blocking=True)      # the composite pre-step uploads h_mu itself
+        if self._instrumented():
+            self.mu_d.copy_(self.h_mu, non_blocking=True)      # (pmc_step_pre uploads h_mu itself)
 
     # ----------------------------------------------------------------- step
     def _rng(self, replay):
@@ -547,9 +583,9 @@ class StepEngine:
                               offset=self.offset)
 
     def can_pipeline(self):
-        """Adaptation on the device + the next pre-step enqueued behind the accept: composite path with the
+        """Adaptation on the device + the next pre-step enqueued behind the accept: the composite entry points with the
         kernels reading / writing pinned host memory themselves."""
-        return bool(self.composite and self.events is None and self.host_direct and self.x_order == "F"
+        return bool(not self._instrumented() and self.host_direct and self.x_order == "F"
                     and self.spin_wait and self.D <= 256)
 
     def adapt_upload(self, sigma, mu=None):
@@ -563,61 +599,58 @@ class StepEngine:
         self.device_adapt = True
 
     def propose(self, sigma, nu=0.0, replay=None, step=None):
-        """propose -> flow inverse -> scaler inverse, then start the D2H of x'.  ``step``: the step number the
-        launch belongs to when it is enqueued ahead of time (run_pipelined), default: the current one."""
+        """propose -> flow inverse -> scaler inverse (-> prior), x' on its way to the host: one ``pmc_step_pre``.
+        ``step``: the step number the launch belongs to when it is enqueued ahead of time
+        (``LanedEngine.step_pipelined``), default: the current one."""
+        if self._instrumented():
+            return self._propose_instrumented(sigma, nu, replay)
+        if replay is not None:
+            self._rng_cur = self._rng(replay)
+        else:
+            self._rng_fast.step = self.step_idx if step is None else int(step)
+            self._rng_cur = self._rng_fast
+        self._step.adapt_mode = 1 if self.device_adapt else 0         # (pre: any non-zero mode = read the state)
+        self._configure_step()
+        if self.device_adapt:
+            sigma, cn_a = 0.0, 0.0                      # the kernels read adapt_state instead
+        else:
+            cn_a = float((1.0 - sigma ** 2.0) ** 0.5) if self.tpcn else 0.0    # mcmc.py:85
+        self._stream = self.stream.cuda_stream if self.stream is not None else _lib.stream_handle()
+        _lib.check(self.lib.pmc_step_pre(C.byref(self._step), C.byref(self._rng_cur), float(nu), float(sigma), cn_a,
+                                         self._stream), "pmc_step_pre")
+        if self.prefetcher is not None and self._direct_now:
+            # helper threads read x' once as soon as the completion word of this pre-step shows up
+            self.lib.pmc_prefetcher_submit(self.prefetcher, self.h_done.data_ptr(), int(self._rng_cur.step) + 1,
+                                           self.h_x.data_ptr(), self.n * self.D * 8, self.wait_timeout)
+
+    def _propose_instrumented(self, sigma, nu, replay):
+        """:meth:`propose` as one launch per stage, HIP events between them (``_cur_ev``), then the copies of x', the finite
+        mask and logp' to the host."""
         lib, n, D = self.lib, self.n, self.D
-        if self.composite and self.events is None:
-            if replay is not None:
-                self._rng_cur = self._rng(replay)
-            else:
-                self._rng_fast.step = self.step_idx if step is None else int(step)
-                self._rng_cur = self._rng_fast
-            self._step.adapt_mode = 1 if self.device_adapt else 0         # (pre: any non-zero mode = read the state)
-            self._configure_step()
-            if self.device_adapt:
-                sigma, cn_a = 0.0, 0.0                      # the kernels read adapt_state instead
-            else:
-                cn_a = float((1.0 - sigma ** 2.0) ** 0.5) if self.tpcn else 0.0    # mcmc.py:85
-            self._stream = self.stream.cuda_stream if self.stream is not None else _lib.stream_handle()
-            _lib.check(lib.pmc_step_pre(C.byref(self._step), C.byref(self._rng_cur), float(nu), float(sigma), cn_a,
-                                        self._stream), "pmc_step_pre")
-            if self.prefetcher is not None and self._direct_now:
-                # helper threads read x' once as soon as the completion word of this pre-step shows up
-                lib.pmc_prefetcher_submit(self.prefetcher, self.h_done.data_ptr(), int(self._rng_cur.step) + 1,
-                                          self.h_x.data_ptr(), n * D * 8, self.wait_timeout)
-            self._post_uploads = True
-            return
-        self._post_uploads = False
-        self._np_clean[0] = -1        # (the fine-grained launches count no rows: a word left by a composite pre-step is stale)
+        self._np_clean[0] = -1        # (these launches count no rows: a word left by a composite pre-step is stale)
         self._rng_cur = self._rng(replay)
         st = _lib.stream_handle()
         kind = PMC_KIND_TPCN if self.tpcn else PMC_KIND_RWM
         cn_a = float((1.0 - sigma ** 2.0) ** 0.5) if self.tpcn else 0.0            # mcmc.py:85
-        timed = self.events is not None
         with torch.cuda.device(self.device):
-            e0 = self._ev() if timed else None
+            e0 = self._ev()
             _lib.check(lib.pmc_propose(
                 kind, _lib.ptr(self.theta32) if self.pre else None, None if self.pre else _lib.ptr(self.u),
                 _lib.ptr(self.mu_d), _lib.ptr(self.inv_cov_d), _lib.ptr(self.chol_d), float(nu), float(sigma), cn_a,
                 C.byref(self._rng_cur), _lib.ptr(self.p_theta64), _lib.ptr(self.p_theta32) if self.pre else None,
                 _lib.ptr(self.quad) if self.tpcn else None, _lib.ptr(self.p_quad) if self.tpcn else None,
                 n, D, st), "pmc_propose")
-            e1 = self._ev() if timed else None
+            e1 = self._ev()
             e2 = e1
             if self.pre:
                 _lib.check(lib.pmc_maf_inverse(C.byref(self.flow._desc), _lib.ptr(self.p_theta32), _lib.ptr(self.p_u32),
                                                _lib.ptr(self.p_ldjf), n, self.flow.inverse_algo, st), "pmc_maf_inverse")
-                e2 = self._ev() if timed else None
-                _lib.check(lib.pmc_scaler_inverse(C.byref(self.scaler_desc), _lib.ptr(self.p_u32), None,
-                                                  _lib.ptr(self.p_u), _lib.ptr(self.p_x), _lib.ptr(self.p_xT),
-                                                  _lib.ptr(self.p_logdetj),
-                                                  _lib.ptr(self.p_fin), n, st), "pmc_scaler_inverse")
-            else:
-                _lib.check(lib.pmc_scaler_inverse(C.byref(self.scaler_desc), None, _lib.ptr(self.p_theta64),
-                                                  _lib.ptr(self.p_u), _lib.ptr(self.p_x), _lib.ptr(self.p_xT),
-                                                  _lib.ptr(self.p_logdetj),
-                                                  _lib.ptr(self.p_fin), n, st), "pmc_scaler_inverse")
-            e3 = self._ev() if timed else None
+                e2 = self._ev()
+            _lib.check(lib.pmc_scaler_inverse(C.byref(self.scaler_desc), _lib.ptr(self.p_u32) if self.pre else None,
+                                              None if self.pre else _lib.ptr(self.p_theta64),
+                                              _lib.ptr(self.p_u), _lib.ptr(self.p_x), _lib.ptr(self.p_xT),
+                                              _lib.ptr(self.p_logdetj), _lib.ptr(self.p_fin), n, st), "pmc_scaler_inverse")
+            e3 = self._ev()
             if self.prior_desc is not None:
                 _lib.check(lib.pmc_prior_logpdf(C.byref(self.prior_desc), _lib.ptr(self.p_x), _lib.ptr(self.p_fin),
                                                 _lib.ptr(self.p_logp), n, st), "pmc_prior_logpdf")
@@ -625,8 +658,7 @@ class StepEngine:
             self.h_logp.copy_(self.p_logp, non_blocking=True)
         self.h_x.copy_(self.p_xT if self.x_order == "F" else self.p_x, non_blocking=True)
         self.h_fin.copy_(self.p_fin, non_blocking=True)
-        if timed:
-            self._cur_ev = [e0, e1, e2, e3, self._ev()]
+        self._cur_ev = [e0, e1, e2, e3, self._ev()]
 
     def _configure_step(self):
         """The fields of the composite entry points' struct that depend on the engine's switches only: written when
@@ -649,112 +681,101 @@ class StepEngine:
             self._step.ev_pre_done = None if self._direct_now else self._ev_pre     # (the completion word replaces it)
             self._step.fill_rejected = int(bool(self.fill_rejected) and self._direct_now)
 
+    def _wait_pre_step(self):
+        """Until x', the finite mask and logp' of the step in flight are complete on the host."""
+        if self._instrumented():
+            torch.cuda.current_stream().synchronize()
+        elif self._direct_now:
+            # the kernels' completion word; the next step's variates are generated behind it
+            _lib.check(self.lib.pmc_wait_flag(self.h_done.data_ptr(), self.step_idx + 1, self.wait_timeout), "pmc_wait_flag")
+        else:
+            _lib.check(self.lib.pmc_event_synchronize(self._ev_pre), "pmc_event_synchronize")
+
     def evaluate(self, log_prior, log_like, have_blobs=False, blobs=None, waited=False):
-        """Host black boxes on the compacted rows, ``mcmc.py:100-121``.  Returns
-        ``(n_calls, blobs_prime)``."""
+        """Host black boxes on the compacted rows, ``mcmc.py:100-121``.  Returns ``(n_calls, blobs_prime)``.
+        ``waited``: the caller already waited for this engine's x' (``pmc_pipeline_next`` returned behind the lane's
+        completion word)."""
         tm = self.host_timers
         t0 = time.perf_counter() if tm is not None else 0.0
-        if waited:
-            pass                                      # (pmc_pipeline_next returned behind this lane's completion word)
-        elif self._post_uploads:
-            # x', finite, logp' are complete at this event / completion word; the next step's variates are
-            # generated behind it
-            if self._direct_now:
-                _lib.check(self.lib.pmc_wait_flag(self.h_done.data_ptr(), self.step_idx + 1, self.wait_timeout), "pmc_wait_flag")
-            else:
-                _lib.check(self.lib.pmc_event_synchronize(self._ev_pre), "pmc_event_synchronize")
-        else:
-            torch.cuda.current_stream().synchronize()
-        if tm is not None:
-            t1 = time.perf_counter(); tm["wait_device"] += t1 - t0
-            _lp, _ll = log_prior, log_like
-
-            def log_prior(a, _f=_lp):
-                ta = time.perf_counter(); r = _f(a); tm["prior"] += time.perf_counter() - ta
-                return r
-
-            def log_like(a, _f=_ll):
-                ta = time.perf_counter(); r = _f(a); tm["likelihood"] += time.perf_counter() - ta
-                return r
+        if not waited:
+            self._wait_pre_step()
         if self.prior_desc is not None:
             log_prior = None                          # logp' came back from the device with x'
-            if ((waited or self._post_uploads) and self._direct_now and self._np_clean[0] == 0
-                    and self.host_threads <= 1 and not have_blobs):
-                # the fused pre-step counted no row with a non-finite x' or logp' (pmc_step_t.h_clean): both masks of
-                # mcmc.py:100-109 are all-true, x'[mask] is x' itself
-                self._np_logl[:] = log_like(self._np_x)[0]
-                return self.n, None
-            bad = int(self._np_clean[0])
-            if ((waited or self._post_uploads) and self._direct_now and self._step.fill_rejected
-                    and 0 < bad <= self.fill_rejected_max * self.n and self.host_threads <= 1 and not have_blobs):
-                # a few rows do not reach the likelihood; their host rows hold the walkers' current x (fill_rejected): the
-                # whole block goes to the likelihood, those rows' values are dropped -- the calls counted are the rows of
-                # mcmc.py:117's x'[mask]
-                good = self._np_fin.astype(bool) & np.isfinite(self._np_logp)
-                ll = log_like(self._np_x)[0]
-                np.copyto(self._np_logl, ll)
-                self._np_logl[~good] = -np.inf
-                return int(good.sum()), None
+        if tm is not None:
+            tm["wait_device"] += time.perf_counter() - t0
+            log_prior = None if log_prior is None else _timed(log_prior, tm, "prior")
+            log_like = _timed(log_like, tm, "likelihood")
         n = self.n
-        x_prime = self._np_x
-        logp_prime = self._np_logp
-        logl_prime = self._np_logl
-        fin_i = self._np_fin
-        blobs_prime = None
-        if fin_i.all() and self.host_threads > 1 and not have_blobs:
-            # rows are independent for a vectorised likelihood (the reference itself calls it on
-            # arbitrary compacted subsets, mcmc.py:106,117): evaluate row chunks concurrently
-            if self._pool is None:
-                self._pool = _host_pool(self.host_threads - 1, self.host_cores)
-            k = self.host_threads
-            bounds = [(i * n // k, (i + 1) * n // k) for i in range(k)]
-
-            def work(b):
-                lo, hi = b
-                xs = x_prime[lo:hi]
-                if log_prior is not None:
-                    logp_prime[lo:hi] = log_prior(xs)
-                lp = logp_prime[lo:hi]
-                ok = np.isfinite(lp)
-                if ok.all():
-                    logl_prime[lo:hi] = log_like(xs)[0]
-                    return hi - lo
-                ll = np.full(hi - lo, -np.inf)
-                ll[ok] = log_like(xs[ok])[0]
-                logl_prime[lo:hi] = ll
-                return int(ok.sum())
-            # the calling thread takes the last chunk itself, the pool's threads the others
-            futs = [self._pool.submit(work, b) for b in bounds[:-1]]
-            calls = work(bounds[-1]) + sum(f.result() for f in futs)
-            self._upload_logs()
-            return calls, None
-        if fin_i.all():
-            # every proposal is finite (the usual case): x'[mask] of mcmc.py:106 is x' itself
-            if log_prior is not None:
+        x_prime, logp_prime, logl_prime, fin_i = self._np_x, self._np_logp, self._np_logl, self._np_fin
+        # rows with a non-finite x' or logp', where the fused pre-step counted them (pmc_step_t.h_clean) and the whole block
+        # may go to the likelihood on this thread; -1: not known
+        bad = -1
+        if ((waited or not self._instrumented()) and self._direct_now and self.prior_desc is not None
+                and self.host_threads <= 1 and not have_blobs):
+            bad = int(self._np_clean[0])
+        if bad == 0:
+            # both masks of mcmc.py:100-109 are all-true, x'[mask] is x' itself
+            logl_prime[:] = log_like(x_prime)[0]
+            return n, None
+        all_fin = fin_i.all()
+        if all_fin and self.host_threads > 1 and not have_blobs:
+            return self._evaluate_threaded(log_prior, log_like), None
+        # mcmc.py:100-109: finite x' -> prior -> finite logp'; where every proposal is finite (the usual case) x'[mask] of
+        # :106 is x' itself
+        fin = None if all_fin else fin_i.astype(bool)
+        if log_prior is not None:
+            if all_fin:
                 logp_prime[:] = log_prior(x_prime)
-            finite = np.isfinite(logp_prime)
-            if finite.all():
-                if have_blobs:
-                    blobs_prime = np.empty(n, dtype=np.dtype((blobs[0].dtype, blobs[0].shape)))
-                    logl_prime[:], blobs_prime[:] = log_like(x_prime)
-                else:
-                    logl_prime[:], _ = log_like(x_prime)
-                self._upload_logs()
-                return n, blobs_prime
-        else:
-            finite = fin_i.astype(bool)
-            if log_prior is not None:
-                logp_prime[finite] = log_prior(x_prime[finite])
-                logp_prime[~finite] = -np.inf
-            finite = finite & np.isfinite(logp_prime)
+            else:
+                logp_prime[fin] = log_prior(x_prime[fin])
+                logp_prime[~fin] = -np.inf
+        mask = np.isfinite(logp_prime) if all_fin else fin & np.isfinite(logp_prime)
+        whole = bool(mask.all())
+        # mcmc.py:117-121 on x'[mask].  Or on the block as it is: with fill_rejected the host rows outside the mask hold the
+        # walkers' current x, and a few wasted evaluations cost less than the gather -- those rows' values are dropped, the
+        # calls counted are the rows of the mask
+        block = whole or (self._step.fill_rejected and 0 < bad <= self.fill_rejected_max * n)
+        xs, rows = (x_prime, slice(None)) if block else (x_prime[mask], mask)
+        blobs_prime = None
         if have_blobs:
             blobs_prime = np.empty(n, dtype=np.dtype((blobs[0].dtype, blobs[0].shape)))
-            logl_prime[finite], blobs_prime[finite] = log_like(x_prime[finite])
+            logl_prime[rows], blobs_prime[rows] = log_like(xs)
         else:
-            logl_prime[finite], _ = log_like(x_prime[finite])
-        logl_prime[~finite] = -np.inf
+            logl_prime[rows], _ = log_like(xs)
+        if not whole:
+            logl_prime[~mask] = -np.inf
         self._upload_logs()
-        return int(np.sum(finite)), blobs_prime
+        return (n if whole else int(mask.sum())), blobs_prime
+
+    def _evaluate_threaded(self, log_prior, log_like):
+        """:meth:`evaluate` of an all-finite x' on ``host_threads`` row chunks at once: rows are independent for a
+        vectorised likelihood (the reference itself calls it on arbitrary compacted subsets, ``mcmc.py:106,117``).
+        Returns the calls."""
+        n, x_prime, logp_prime, logl_prime = self.n, self._np_x, self._np_logp, self._np_logl
+        if self._pool is None:
+            self._pool = _host_pool(self.host_threads - 1, self.host_cores)
+        k = self.host_threads
+        bounds = [(i * n // k, (i + 1) * n // k) for i in range(k)]
+
+        def work(b):
+            lo, hi = b
+            xs = x_prime[lo:hi]
+            if log_prior is not None:
+                logp_prime[lo:hi] = log_prior(xs)
+            lp = logp_prime[lo:hi]
+            ok = np.isfinite(lp)
+            if ok.all():
+                logl_prime[lo:hi] = log_like(xs)[0]
+                return hi - lo
+            ll = np.full(hi - lo, -np.inf)
+            ll[ok] = log_like(xs[ok])[0]
+            logl_prime[lo:hi] = ll
+            return int(ok.sum())
+        # the calling thread takes the last chunk itself, the pool's threads the others
+        futs = [self._pool.submit(work, b) for b in bounds[:-1]]
+        calls = work(bounds[-1]) + sum(f.result() for f in futs)
+        self._upload_logs()
+        return calls
 
     def evaluate_device(self, log_prior, log_like):
         """The likelihood of the step in flight on the device (``pmc_step_t.lik_x``), on the engine's stream: the callable
@@ -765,10 +786,7 @@ class StepEngine:
         (:meth:`calls_reached`)."""
         stream = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
         if self.prior_desc is None:
-            if self._direct_now:
-                _lib.check(self.lib.pmc_wait_flag(self.h_done.data_ptr(), self.step_idx + 1, self.wait_timeout), "pmc_wait_flag")
-            else:
-                _lib.check(self.lib.pmc_event_synchronize(self._ev_pre), "pmc_event_synchronize")
+            self._wait_pre_step()
             fin = self._np_fin.astype(bool)
             if fin.all():
                 self._np_logp[:] = log_prior(self._np_x)
@@ -786,17 +804,17 @@ class StepEngine:
         return int(self._np_calls[0])
 
     def _upload_logs(self):
-        if not self._post_uploads:                    # the composite post step does the H2D itself
+        if self._instrumented():                      # (pmc_step_post does the H2D itself)
             self.p_logl.copy_(self.h_logl, non_blocking=True)
             if self.prior_desc is None:
                 self.p_logp.copy_(self.h_logp, non_blocking=True)
 
     def accept_enqueue(self, beta, nu=0.0, want_mask=False, host_sums=True, adapt=None, n_total=None, others=()):
-        """Composite path: enqueue the Metropolis accept + this engine's sums behind the host's logl' (no wait).
+        """Enqueue the Metropolis accept + this engine's sums behind the host's logl' (``pmc_step_post``; no wait).
         ``adapt`` = Adaptation.coefficients(): the kernel's last block also updates the device-side sigma / mu.
         ``others``: engines over the other row ranges of the walker set whose accepts are already enqueued on this
         stream -- the kernel adds their sums to its own before the update and the host copy."""
-        assert self._post_uploads
+        assert not self._instrumented()
         self._want_mask = bool(want_mask)
         self._host_sums = bool(host_sums)
         st = self._step
@@ -823,34 +841,32 @@ class StepEngine:
 
     def accept_reduce(self, beta, nu=0.0, want_mask=False):
         """Metropolis accept + global sums; returns the (all-reduced) host copy."""
-        if self._post_uploads:
-            import torch.distributed as dist
-            sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-            self.accept_enqueue(beta, nu, want_mask, host_sums=not sharded)
-            if sharded:
-                allreduce_sums(self.sums, self.group)
-                self.h_sums.copy_(self.sums, non_blocking=True)
-                torch.cuda.current_stream().synchronize()
-                self.step_idx += 1
-                return self._np_sums
-            return self.accept_wait()
+        if self._instrumented():
+            return self._accept_instrumented(beta, nu, want_mask)
+        sharded = _sharded(self.group)
+        self.accept_enqueue(beta, nu, want_mask, host_sums=not sharded)
+        return self._reduced_sums() if sharded else self.accept_wait()
+
+    def _reduced_sums(self):
+        allreduce_sums(self.sums, self.group)
+        self.h_sums.copy_(self.sums, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.step_idx += 1
+        return self._np_sums
+
+    def _accept_instrumented(self, beta, nu, want_mask):
+        """:meth:`accept_reduce` as one ``pmc_accept`` between two HIP events; closes the step's tuple of ``events``."""
         kind = PMC_KIND_TPCN if self.tpcn else PMC_KIND_RWM
-        timed = self.events is not None
         with torch.cuda.device(self.device):
-            e5 = self._ev() if timed else None
+            e5 = self._ev()
             _lib.check(self.lib.pmc_accept(kind, int(self.pre), C.byref(self._state), C.byref(self._prop), float(beta),
                                            float(nu), C.byref(self._rng_cur), _lib.ptr(self.alpha), _lib.ptr(self.accept),
                                            _lib.ptr(self.sums), _lib.ptr(self.ws), self.n, self.D,
                                            _lib.stream_handle()), "pmc_accept")
-            if timed:
-                self.events.append(self._cur_ev + [e5, self._ev()])
-        allreduce_sums(self.sums, self.group)
-        self.h_sums.copy_(self.sums, non_blocking=True)
+            self.events.append(self._cur_ev + [e5, self._ev()])
         if want_mask:
             self.h_accept.copy_(self.accept, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        self.step_idx += 1
-        return self._np_sums
+        return self._reduced_sums()
 
     def download(self, device=False):
         """The walker state as numpy arrays, or (``device=True``) as the engine's own device tensors."""
@@ -906,12 +922,12 @@ class LanedEngine:
         self.host_timers = None
         self._h_flag = torch.zeros(1, dtype=torch.int64).pin_memory()
         self._flag_value = 0
-        self._parts = (C.c_void_p * len(self.lanes))(*[e.sums.data_ptr() for e in self.lanes])
         self._tot_part = (C.c_void_p * 1)(self._tot.data_ptr())
-        # the lane pipeline behind the C ABI (pmc_pipeline_*): default whenever the ranks do not have to all-reduce between
-        # the last accept and the adaptation (that exchange is torch.distributed's); PMC_C_PIPELINE=0: the same launches
-        # enqueued from Python (round 2; kept as the cross-check of the test suite)
-        self.c_pipeline = os.environ.get("PMC_C_PIPELINE", "1") != "0"
+        # the lane pipeline behind the C ABI (pmc_pipeline_*) wherever it can serve: one rank, or ranks whose sums meet inside
+        # the library (small_comm).  The same launches enqueued from Python (step_pipelined's second half) are the
+        # fall-back where they cannot -- PMC_C_ALLREDUCE=0, more than 8 lanes or ranks, no working mailbox: the exchange is
+        # then torch.distributed's -- and, with PMC_C_PIPELINE=0, what the tests compare the C pipeline with
+        self.c_pipeline = _env_c_pipeline()
         self._pipe = None
 
     def __del__(self):
@@ -937,8 +953,7 @@ class LanedEngine:
 
     def configure(self, **kw):
         for e in self.lanes:
-            for k, v in kw.items():
-                setattr(e, k, v)
+            e.configure(**kw)
 
     def load_state(self, u, x, logdetj, logl, logp):
         for e, (lo, hi) in zip(self.lanes, self.bounds):
@@ -958,15 +973,13 @@ class LanedEngine:
         for e in self.lanes[1:]:
             e._step.adapt_state = first.adapt_state.data_ptr()       # one state for all lanes
             e.device_adapt = True
-        import torch.distributed as dist
-        sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        sharded = _sharded(self.group)
         self._drop_pipe()
         comm = small_comm(self.lib, self.group, self.D + 4) if (sharded and self.c_pipeline) else None
         if self.c_pipeline and (not sharded or comm) and len(self.lanes) <= 8:
             K = len(self.lanes)
             for e in self.lanes:
                 e._configure_step()
-                e._post_uploads = True
             assert all(e._direct_now for e in self.lanes)
             self._lane_structs = (C.c_void_p * K)(*[C.addressof(e._step) for e in self.lanes])
             offs = (C.c_uint64 * K)(*[e.offset for e in self.lanes])
@@ -1031,9 +1044,8 @@ class LanedEngine:
             if sums[0] != sums[0]:                       # (NaN: a rank did not arrive within the timeout, pmc_comm_adapt_update)
                 raise _lib.PocomcAmdError("sharded step: a rank did not deliver its sums within wait_timeout")
             return calls, sums
-        import torch.distributed as dist
-        sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-        lib, D, K = self.lib, self.D, len(self.lanes)
+        sharded = _sharded(self.group)
+        lib, D = self.lib, self.D
         tm = self.host_timers
         clock = time.perf_counter
         calls = 0
@@ -1098,12 +1110,11 @@ class LanedEngine:
 
     def set_mu(self, mu):
         for e in self.lanes:
-            e.set_mu(mu)                                   # composite path: a write to the lane's pinned h_mu
+            e.set_mu(mu)                                   # (a write to the lane's pinned h_mu)
 
     def step(self, sigma, nu, beta, log_prior, log_like):
         """One MCMC step of all lanes; returns (likelihood calls, global sums on the host)."""
-        import torch.distributed as dist
-        sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        sharded = _sharded(self.group)
         # (the composite entry points take the lane's stream explicitly: no stream context on this path)
         for e in self.lanes:                               # all proposals are in flight before the first wait
             e.host_timers = self.host_timers
@@ -1164,10 +1175,7 @@ def _proposal_draws(kind, theta32, geometry, sigma, rows, seed=20240929):
 
 
 def _global_count(n, group):
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        return n * dist.get_world_size(group)        # equal shards by construction
-    return n
+    return n * dist.get_world_size(group) if _sharded(group) else n        # (equal shards by construction)
 
 
 _PREFETCHERS = {}
@@ -1188,6 +1196,119 @@ def host_prefetch(lib, n_threads, cores=None):
     return _PREFETCHERS[key]
 
 
+def guard_inverse_precision(flow, kind, theta32, geometry, sigma, group):
+    """The 16-bit sweep's safety net where the sweep is used: on the points THIS call hands to ``flow.inverse``
+    (``mcmc.py:88``) -- proposals drawn from the step's own law at the starting sigma / mu, a strided sample over the
+    walkers ``theta32`` (all lanes') -- float32 from here on if the sweep is not an inverse there.  Sharded: every rank
+    enters the reduction whatever its own state (a rank that already fell back votes for the fallback), one rank's
+    fallback is everybody's.  (``bench.py`` carries a copy of this procedure from before it was a function of its own.)"""
+    armed = flow.inverse_precision_active != "f32"
+    guard = None
+    if armed:
+        guard = flow.check_inverse_precision(theta=_proposal_draws(kind, theta32, geometry, float(sigma), 4096), rows=4096)
+    fall = (not armed) or (guard is not None and not guard["passed"])
+    if _sharded(group):
+        flag = torch.tensor([1.0 if fall else 0.0], device=theta32.device)
+        dist.all_reduce(flag, group=group)
+        fall = float(flag.item()) > 0
+    if fall and flow._desc.lane16:
+        flow._desc.lane16 = None
+        if flow.inverse_guard is not None:
+            flow.inverse_guard["passed"] = False
+
+
+def _counted(fn, rows):
+    """``fn`` of one argument, ``len`` of each appended to ``rows`` (atomic: ``host_threads`` > 1 call from several threads)."""
+    def call(a):
+        rows.append(len(a))
+        return fn(a)
+    return call
+
+
+def _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior, whole_set, device_like):
+    """The engine of one kernel call, configured from ``option_dict``; ``whole_set``: blobs / traces / replayed variates
+    need the bookkeeping of the whole set (one lane, no pipeline).  Returns ``(engine, pipelined)``."""
+    x_order = "F" if device_like else option_dict.get("x_order", "C")
+    # lanes > 1: row ranges whose device work overlaps the host likelihood of the others (LanedEngine); opt-in,
+    # it pays when the likelihood is expensive next to the device's share of a step (DESIGN.md section 5)
+    lanes = 1 if (whole_set or device_like) else int(option_dict.get("lanes") or 1)
+    # pipelined: sigma / mu adapted on the device, the pre-step of step k+1 enqueued behind the accept of step k
+    # (needs the kernels to read / write the pinned host buffers themselves: x_order 'F')
+    want_pipe = bool(option_dict.get("pipeline", True) and x_order == "F" and not whole_set and not device_like
+                     and all(option_dict.get(k, True) for k in ("host_direct", "spin_wait")))
+    common = dict(group=option_dict.get("group"), shard_offset=option_dict.get("shard_offset", 0), seed=seed,
+                  x_order=x_order)
+    if lanes > 1 or want_pipe:                      # (the pipelined step lives behind pmc_pipeline_*: one lane is a pipeline too)
+        eng = LanedEngine(kind, n_walkers, n_dim, flow, scaler, lanes=lanes, first_fraction=option_dict.get("first_lane"),
+                          streams=not want_pipe, **common)
+    else:
+        eng = StepEngine(kind, n_walkers, n_dim, flow, scaler, **common)
+    if option_dict.get("wait_timeout") is not None:
+        eng.configure(wait_timeout=_wait_timeout(option_dict["wait_timeout"]))
+    for key in ("host_direct", "rng_prefill", "spin_wait", "fill_rejected"):
+        if key in option_dict:
+            eng.configure(**{key: bool(option_dict[key])})
+    if option_dict.get("host_threads", 1) > 1:
+        # opt-in: the black boxes are called concurrently on row chunks from this many threads (they must be
+        # thread-safe; the reference calls them on the calling thread only)
+        eng.configure(host_threads=int(option_dict["host_threads"]), host_cores=option_dict.get("host_cores"))
+    if int(option_dict.get("host_prefetch") or 0) > 0:
+        eng.configure(prefetcher=host_prefetch(eng.lib, int(option_dict["host_prefetch"]),
+                                               option_dict.get("host_prefetch_cores")))
+    owner = getattr(log_prior, "__self__", None)
+    if owner is not None and option_dict.get("device_prior", True) and hasattr(owner, "device_descriptor"):
+        eng.set_device_prior(owner)                 # Prior.logpdf on the device when the Prior gives a descriptor
+    if device_like:
+        eng.set_device_likelihood()
+    return eng, want_pipe and eng.can_pipeline()
+
+
+# One step of each mode _run can take: (calls, sums).  ``more``: a further step may follow (the modes that enqueue the next
+# pre-step behind the accept leave it out behind the last permitted step).
+def _step_device_likelihood(eng, ad, beta, nu, n_total, log_prior, log_like, more):
+    # pre-step (in flight) -> likelihood -> accept + adaptation -> the next pre-step, all on one stream; then the one wait of
+    # the step, for the sums (and the rows that reached the likelihood) the stop rule needs
+    eng.evaluate_device(log_prior, log_like)
+    eng.accept_enqueue(beta, nu, adapt=ad.coefficients(), n_total=n_total)
+    if more:
+        eng.propose(None, nu, step=eng.step_idx + 1)
+    sums = eng.accept_wait()
+    return eng.calls_reached(), sums
+
+
+def _step_pipelined(eng, ad, beta, nu, n_total, log_prior, log_like, more):       # lanes on one stream, sigma / mu on the device
+    return eng.step_pipelined(beta, nu, ad.coefficients(), n_total, log_prior, log_like, more=more)
+
+
+def _step_laned(eng, ad, beta, nu, log_prior, log_like, more):                     # lanes on their streams, sigma / mu from the host
+    return eng.step(ad.sigma, nu, beta, log_prior, log_like)
+
+
+def _step_plain(eng, ad, beta, nu, log_prior, log_like, replay, blobs, want_mask, more):
+    """The whole set on one engine, sigma / mu from the host: the one mode with replayed variates, blobs and traces."""
+    rp = None
+    if replay is not None:
+        replay.begin_step()
+        n, D = eng.n, eng.D
+        rp = dict(gamma=replay.std_gamma((D + nu) / 2, n) if eng.tpcn else None, z=replay.normal(n, D), u=replay.uniform(n))
+    eng.propose(ad.sigma, nu, rp)
+    calls, blobs_prime = eng.evaluate(log_prior, log_like, blobs is not None, blobs)
+    sums = eng.accept_reduce(beta, nu, want_mask=want_mask)
+    if blobs is not None:
+        mask = eng.h_accept.numpy().astype(bool)
+        blobs[mask] = blobs_prime[mask]
+    return calls, sums
+
+
+def _trace_record(eng, ad):
+    return dict(alpha=eng.alpha.cpu().numpy(), accept=eng.h_accept.numpy().astype(bool).copy(),
+                theta_prime=eng.p_theta64.cpu().numpy(), u_prime=eng.p_u.cpu().numpy(),
+                x_prime=eng.p_x.cpu().numpy(), logdetj_prime=eng.p_logdetj.cpu().numpy(),
+                logdetj_flow_prime=eng.p_ldjf.cpu().numpy() if eng.pre else None,
+                finite=eng.p_fin.cpu().numpy().astype(bool), sigma=float(ad.sigma),
+                mu=None if ad.mu is None else ad.mu.copy(), **eng.download())
+
+
 def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     pre = kind.startswith("preconditioned")
     tpcn = kind in ("preconditioned_pcn", "pcn")
@@ -1196,33 +1317,22 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     # results stay there too)
     on_device = isinstance(state_dict.get("u"), torch.Tensor)
     cp = (lambda a: a) if on_device else np.copy
-    u = cp(state_dict.get("u"))
-    x = cp(state_dict.get("x"))
-    logdetj = cp(state_dict.get("logdetj"))
-    logl = cp(state_dict.get("logl"))
-    logp = cp(state_dict.get("logp"))
-    beta = state_dict.get("beta")
-    blobs = state_dict.get("blobs")
+    u, x, logdetj, logl, logp = (cp(state_dict.get(k)) for k in ("u", "x", "logdetj", "logl", "logp"))
+    beta, blobs = state_dict.get("beta"), state_dict.get("blobs")
     have_blobs = blobs is not None
 
-    log_like = function_dict.get("loglike")
-    log_prior = function_dict.get("logprior")
     # rows actually handed to the likelihood: with ``fill_rejected`` (default for the pipelined step) a row that does not
     # reach the reference's likelihood call (mcmc.py:117: x'[mask]) is passed with the walker's CURRENT x and its value
     # dropped -- the likelihood must be row-wise and free of side effects (it is for the reference, which calls it on
     # arbitrary compacted subsets); results["calls"] counts the reference's rows, results["evaluations"] these
-    _rows_passed = []
-    _user_like = log_like
-
-    def log_like(a, _f=_user_like, _seen=_rows_passed.append):
-        _seen(len(a))
-        return _f(a)
+    rows_passed = []
+    log_like = _counted(function_dict.get("loglike"), rows_passed)
+    log_prior = function_dict.get("logprior")
     scaler = function_dict.get("scaler")
     flow = function_dict.get("flow") if pre else None
     geometry = function_dict.get("theta_geometry" if pre else "u_geometry")
 
     n_max = option_dict.get("n_max")
-    n_steps = option_dict.get("n_steps")
     progress_bar = option_dict.get("progress_bar")
     group = option_dict.get("group")
     seed = option_dict.get("seed")
@@ -1233,55 +1343,20 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
                                              + int(np.random.randint(0, 2 ** 31 - 1)))
     n_walkers, n_dim = x.shape
 
-    import torch.distributed as dist
-    sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     # the likelihood is a GPU callable (tensor in, tensor out): x' never goes to the host, logl' is never uploaded
     device_like = bool(option_dict.get("device_likelihood", False))
     if device_like:
-        if sharded:
+        if _sharded(group):
             raise NotImplementedError("device_likelihood: sharded walkers (world > 1) are not supported; "
                                       "use a host likelihood or one process")
         if have_blobs:
             raise ValueError("device_likelihood: blobs are not supported")
         if replay is not None or trace is not None:
             raise ValueError("device_likelihood: replayed variates and traces need the host likelihood")
-    x_order = "F" if device_like else option_dict.get("x_order", "C")
-    # lanes > 1: row ranges whose device work overlaps the host likelihood of the others (LanedEngine); opt-in,
-    # it pays when the likelihood is expensive next to the device's share of a step
-    lanes = int(option_dict.get("lanes") or 1)
-    if have_blobs or trace is not None or replay is not None or device_like:
-        lanes = 1                                   # (blobs / traces / replayed variates: whole-set bookkeeping)
-    # pipelined: sigma / mu adapted on the device, the pre-step of step k+1 enqueued behind the accept of step k
-    # (needs the kernels to read / write the pinned host buffers themselves: x_order 'F')
-    want_pipe = (option_dict.get("pipeline", True) and x_order == "F" and not have_blobs and trace is None and not device_like
-                 and replay is None and all(option_dict.get(k, True) for k in ("host_direct", "spin_wait")))
-    if lanes > 1 or want_pipe:                      # (the pipelined step lives behind pmc_pipeline_*: one lane is a pipeline too)
-        eng = LanedEngine(kind, n_walkers, n_dim, flow, scaler, lanes=lanes, group=group,
-                          first_fraction=option_dict.get("first_lane"),
-                          shard_offset=option_dict.get("shard_offset", 0), seed=seed, x_order=x_order,
-                          streams=not want_pipe)
-        tune = eng.configure
-    else:
-        eng = StepEngine(kind, n_walkers, n_dim, flow, scaler, group=group,
-                         shard_offset=option_dict.get("shard_offset", 0), seed=seed, x_order=x_order)
-        tune = lambda **kw: [setattr(eng, k, v) for k, v in kw.items()]
+    eng, pipelined = _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior,
+                                  whole_set=have_blobs or trace is not None or replay is not None, device_like=device_like)
     laned = isinstance(eng, LanedEngine)
-    if option_dict.get("wait_timeout") is not None:
-        tune(wait_timeout=_wait_timeout(option_dict["wait_timeout"]))
-    for key in ("host_direct", "rng_prefill", "spin_wait", "fill_rejected"):
-        if key in option_dict:
-            tune(**{key: bool(option_dict[key])})
-    if option_dict.get("host_threads", 1) > 1:
-        # opt-in: the black boxes are called concurrently on row chunks from this many threads (they must be
-        # thread-safe; the reference calls them on the calling thread only)
-        tune(host_threads=int(option_dict["host_threads"]), host_cores=option_dict.get("host_cores"))
-    if int(option_dict.get("host_prefetch") or 0) > 0:
-        tune(prefetcher=host_prefetch(eng.lib, int(option_dict["host_prefetch"]), option_dict.get("host_prefetch_cores")))
-    owner = getattr(log_prior, "__self__", None)
-    if owner is not None and option_dict.get("device_prior", True) and hasattr(owner, "device_descriptor"):
-        eng.set_device_prior(owner)                 # Prior.logpdf on the device when the Prior gives a descriptor
-    if device_like:
-        eng.set_device_likelihood()
+    lanes = eng.lanes if laned else [eng]
     eng.load_state(u, x, logdetj, logl, logp)
     nu = 0.0
     if tpcn:
@@ -1301,104 +1376,57 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     init = torch.tensor(first + [0.0] * (n_dim + 1), dtype=torch.float64, device=eng.device)
     allreduce_sums(init, group)
     init = init.cpu().numpy()
-    ad = Adaptation(kind, n_dim, n_total, n_steps, n_max, option_dict.get("proposal_scale"),
+    ad = Adaptation(kind, n_dim, n_total, option_dict.get("n_steps"), n_max, option_dict.get("proposal_scale"),
                     geometry.t_mean if tpcn else None, (init[1] if tpcn else init[2]) / n_total)
 
     if pre and getattr(flow, "_lane16", None) is not None and flow.inverse_guard_enabled:
-        # the 16-bit sweep's safety net where the sweep is used: on the points THIS call hands to flow.inverse (mcmc.py:88)
-        # -- proposals drawn from the step's own law at the starting sigma / mu, a strided sample over ALL lanes' walkers;
-        # float32 from here on if the sweep is not an inverse there.  Sharded: every rank enters the reduction whatever its
-        # own state (a rank that already fell back votes for the fallback), one rank's fallback is everybody's.
-        armed = flow.inverse_precision_active != "f32"
-        guard = None
-        if armed:
-            th_all = torch.cat([e_.theta32 for e_ in (eng.lanes if laned else [eng])])
-            thp = _proposal_draws(kind, th_all, geometry, float(ad.sigma), 4096)
-            guard = flow.check_inverse_precision(theta=thp, rows=4096)
-        fall = (not armed) or (guard is not None and not guard["passed"])
-        if sharded:
-            flag = torch.tensor([1.0 if fall else 0.0], device=eng.device)
-            dist.all_reduce(flag, group=group)
-            fall = float(flag.item()) > 0
-        if fall and flow._desc.lane16:
-            flow._desc.lane16 = None
-            if flow.inverse_guard is not None:
-                flow.inverse_guard["passed"] = False
+        guard_inverse_precision(flow, kind, torch.cat([e.theta32 for e in lanes]), geometry, ad.sigma, group)
 
-    n_calls = 0
-    pipelined = want_pipe and eng.can_pipeline() and (laned or not sharded)
-    if pipelined and laned:
-        eng.start_pipeline(float(ad.sigma), ad.mu, nu)
-    elif pipelined or device_like:
-        # adaptation on the device: the pre-step of step k+1 is enqueued right behind the accept of step k and
-        # runs while the host still waits for / digests the sums of step k (which it needs for the stop rule only)
+    # the mode of this call, chosen once.  Adaptation on the device (the first two): the pre-step of step k+1 is enqueued
+    # right behind the accept of step k and runs while the host still waits for / digests the sums of step k, which it
+    # needs for the stop rule only
+    if device_like:
         eng.adapt_upload(float(ad.sigma), ad.mu)
         eng.propose(ad.sigma, nu)
+        step = partial(_step_device_likelihood, eng, ad, beta, nu, n_total, log_prior, log_like)
+    elif pipelined:
+        eng.start_pipeline(float(ad.sigma), ad.mu, nu)
+        step = partial(_step_pipelined, eng, ad, beta, nu, n_total, log_prior, log_like)
+    elif laned:
+        step = partial(_step_laned, eng, ad, beta, nu, log_prior, log_like)
+    else:
+        step = partial(_step_plain, eng, ad, beta, nu, log_prior, log_like, replay, blobs,
+                       have_blobs or trace is not None)
+    mu_from_host = kind == "preconditioned_pcn" and not (device_like or pipelined)
+    n_calls = 0
     while True:
-        rp = None
-        if replay is not None:
-            replay.begin_step()
-            rp = dict(gamma=replay.std_gamma((n_dim + nu) / 2, n_walkers) if tpcn else None,
-                      z=replay.normal(n_walkers, n_dim), u=replay.uniform(n_walkers))
-        if device_like:
-            # pre-step (in flight) -> likelihood -> accept + adaptation -> the next pre-step, all on one stream; then the one
-            # wait of the step, for the sums (and the rows that reached the likelihood) the stop rule needs
-            eng.evaluate_device(log_prior, log_like)
-            eng.accept_enqueue(beta, nu, adapt=ad.coefficients(), n_total=n_total)
-            if ad.i + 1 < n_max:
-                eng.propose(None, nu, step=eng.step_idx + 1)
-            sums = eng.accept_wait()
-            calls = eng.calls_reached()
-        elif pipelined and laned:
-            calls, sums = eng.step_pipelined(beta, nu, ad.coefficients(), n_total, log_prior, log_like,
-                                             more=ad.i + 1 < n_max)
-        elif pipelined:
-            calls, _ = eng.evaluate(log_prior, log_like)
-            eng.accept_enqueue(beta, nu, adapt=ad.coefficients(), n_total=n_total)
-            if ad.i + 1 < n_max:                         # (the last permitted step has no successor)
-                eng.propose(None, nu, step=eng.step_idx + 1)
-            sums = eng.accept_wait()
-        elif laned:
-            calls, sums = eng.step(ad.sigma, nu, beta, log_prior, log_like)
-        else:
-            eng.propose(ad.sigma, nu, rp)
-            calls, blobs_prime = eng.evaluate(log_prior, log_like, have_blobs, blobs)
-            sums = eng.accept_reduce(beta, nu, want_mask=have_blobs or trace is not None)
+        calls, sums = step(ad.i + 1 < n_max)         # (the last permitted step has no successor)
         n_calls += calls
-        if have_blobs:
-            mask = eng.h_accept.numpy().astype(bool)
-            blobs[mask] = blobs_prime[mask]
         stop = ad.update(sums)
-        if kind == "preconditioned_pcn" and not (pipelined or device_like):
+        if mu_from_host:
             eng.set_mu(ad.mu)
         if trace is not None:
-            trace.append(dict(alpha=eng.alpha.cpu().numpy(), accept=eng.h_accept.numpy().astype(bool).copy(),
-                              theta_prime=eng.p_theta64.cpu().numpy(), u_prime=eng.p_u.cpu().numpy(),
-                              x_prime=eng.p_x.cpu().numpy(), logdetj_prime=eng.p_logdetj.cpu().numpy(),
-                              logdetj_flow_prime=eng.p_ldjf.cpu().numpy() if pre else None,
-                              finite=eng.p_fin.cpu().numpy().astype(bool), sigma=float(ad.sigma),
-                              mu=None if ad.mu is None else ad.mu.copy(), **eng.download()))
+            trace.append(_trace_record(eng, ad))
         if progress_bar is not None:
             progress_bar.update_stats(dict(calls=progress_bar.info["calls"] + calls, acc=ad.mean_alpha, steps=ad.i,
                                            logP=sums[1] / n_total, eff=ad.sigma / (2.38 / np.sqrt(n_dim))))
         if stop:
             break
-    if pipelined or device_like:
-        # a pre-step launched ahead of a plateau stop is still in flight; it touches proposal buffers only
-        if laned:
-            eng.finish_pipeline()
-        else:
-            _lib.check(eng.lib.pmc_stream_synchronize(eng._stream), "pmc_stream_synchronize")
+    # a pre-step launched ahead of a plateau stop is still in flight; it touches proposal buffers only
+    if pipelined:
+        eng.finish_pipeline()
+    elif device_like:
+        _lib.check(eng.lib.pmc_stream_synchronize(eng._stream), "pmc_stream_synchronize")
 
     keep = bool(option_dict.get("device_state", False))
     if keep:
         torch.cuda.synchronize(eng.device)             # (nothing of this call is in flight any more)
     out = eng.download(device=keep)                    # (the numpy download synchronises by itself)
-    for e_ in (eng.lanes if laned else [eng]):
-        e_._recycle = True
+    for e in lanes:
+        e._recycle = True
     return dict(u=out["u"], x=out["x"], logdetj=out["logdetj"], logl=out["logl"], logp=out["logp"], blobs=blobs,
                 efficiency=ad.sigma, accept=ad.mean_alpha, steps=ad.i, calls=n_calls, proposal_scale=ad.sigma,
-                evaluations=int(sum(_rows_passed)))
+                evaluations=int(sum(rows_passed)))
 
 
 def preconditioned_pcn(state_dict, function_dict, option_dict, replay=None, trace=None):
