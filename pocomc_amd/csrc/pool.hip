@@ -257,7 +257,11 @@ template <typename T>
 __global__ void pick_median_kernel(const T* __restrict__ sorted, int64_t n, int D, T* __restrict__ med) {
     for (int j = threadIdx.x; j < D; j += blockDim.x) {
         const T* s = sorted + (size_t)j * n;
-        med[j] = (n & 1) ? s[(n - 1) / 2] : (T)((s[n / 2 - 1] + s[n / 2]) / (T)2);
+        // the radix sort orders by bit pattern: a NaN sits at the end of the segment (sign bit set: at its start), and
+        // np.median of a column that holds one is NaN
+        const bool has_nan = s[0] != s[0] || s[n - 1] != s[n - 1];
+        const T m = (n & 1) ? s[(n - 1) / 2] : (T)((s[n / 2 - 1] + s[n / 2]) / (T)2);
+        med[j] = has_nan ? (T)__builtin_nan("") : m;
     }
 }
 

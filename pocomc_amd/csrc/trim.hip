@@ -4,7 +4,10 @@
 // The reference evaluates np.percentile (a partition) and two masked sums per threshold -- up to
 // 1000 passes over the pool.  Here: one radix sort (rocPRIM via hipCUB), two prefix sums, and one
 // 1024-thread kernel that evaluates every threshold at once and picks the first one the
-// reference's downward scan would accept.
+// reference's downward scan would accept.  The accepted bin is equal to the reference's except where a bin's ESS
+// ratio equals `ess` to within rounding: the kept sums here are total minus prefix of the SORTED weights (in the
+// scan's order), the reference's are sums over the unsorted masked array, and on such a knife edge the order decides
+// (dropping exactly 1 % of nearly equal weights gives 0.99 up to the last bit).  tests/pool_regimes.py defines the band.
 
 #include <hip/hip_runtime.h>
 #include <string.h>

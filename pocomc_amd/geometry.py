@@ -75,7 +75,8 @@ def moments(x, idx=None, w=None):
 
 
 def column_medians(x, idx=None):
-    """``np.median(x[idx], axis=0)`` on the device (``pmc_column_medians``), in the input's precision."""
+    """``np.median(x[idx], axis=0)`` on the device (``pmc_column_medians``), in the input's precision; NaN for a column
+    that holds a NaN, like numpy."""
     lib = _lib.load()
     n = int(idx.numel()) if idx is not None else int(x.shape[0])
     D = int(x.shape[1])

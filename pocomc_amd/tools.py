@@ -138,7 +138,10 @@ class PoolWeights:
 def trim_weights(samples, weights, ess=0.99, bins=1000):
     """``pocomc/tools.py:10-53`` (normalises ``weights`` in place like the reference).  The
     threshold search runs on the GPU (``pmc_trim_threshold``); the final mask / renormalisation
-    are the reference's own two lines."""
+    are the reference's own two lines.  The kept set is equal to the reference's except where a
+    percentile bin's ESS ratio equals ``ess`` to within rounding: there the order of the sums decides
+    which bin is accepted (the reference adds the unsorted masked array, the kernel subtracts prefix sums of
+    the sorted one), and either may stop one bin earlier (``tests/pool_regimes.py``: knife edge)."""
     lib = _lib.load()
     weights /= np.sum(weights)
     wd = _up(weights)
@@ -197,7 +200,8 @@ def device_sum(a_d):
 
 def systematic_resample(size, weights, random_state=None, offset=None, device_indices=False):
     """``pocomc/tools.py:136-186``; indices are bit-exact with the reference.  ``weights`` may be a float64 device
-    tensor (the pool's weights); ``device_indices=True`` leaves the indices on the device."""
+    tensor (the pool's weights); ``device_indices=True`` leaves the indices on the device.  Where the reference
+    raises IndexError -- a position above a cumulative sum whose last entry rounds below 1 -- the index is ``P - 1``."""
     lib = _lib.load()
     if random_state is not None:
         np.random.seed(random_state)
