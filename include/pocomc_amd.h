@@ -553,7 +553,15 @@ typedef struct pmc_step {
      *   logp' is not finite (mcmc.py:118-121) before the ratio of mcmc.py:124-134: accepted rows store the gated value; a
      *   NaN from the likelihood gives alpha = 0 (:134).  Its last block writes n - clean_count, the number of rows that
      *   reached the likelihood (mcmc.py:121's n_calls increment), to h_calls ahead of the sums and the completion word
-     *   h_done[1], and zeroes clean_count.  Needs clean_count and h_calls; adapt_state is optional as for the host path. */
+     *   h_done[1], and zeroes clean_count.  Needs clean_count and h_calls; adapt_state is optional as for the host path.
+     * Walkers row-sharded over ranks (one process per GPU), everything on one stream: pmc_step_post with adapt_mode = 0 and
+     * copy_sums = 0 -- this rank's sums stay in `sums`, no adaptation, no completion word, but h_calls is still written
+     * and clean_count still zeroed by that launch (the gate does not depend on a completion word being asked for) -- then
+     * pmc_comm_adapt_update (or the process group's all-reduce + pmc_adapt_update) with `sums` as its single part, h_sums
+     * as the host copy of the GLOBAL sums and h_done[1] as its completion word, then the next pmc_step_pre.  The count is
+     * NOT moved into the exchange kernel: the accept launch completes, its stores to pinned host memory included, before
+     * the exchange launch starts on the same stream, so the host reads h_calls (this rank's rows) once it has seen the
+     * exchange's completion word, and not before. */
     double* lik_x;            /* device f64 [D][n] or NULL */
     int64_t* h_calls;         /* pinned host int64 [1] */
 } pmc_step_t;

@@ -477,6 +477,7 @@ class StepEngine:
         self.device_likelihood = False
         self.p_xl = None
         self.h_calls = None
+        self._sums_part = None   # (exchange_enqueue: this rank's sums as the exchange's single part)
 
     def __del__(self):
         if getattr(self, "_recycle", False):       # (only after the owner synchronised with the device: mcmc._run)
@@ -838,6 +839,42 @@ class StepEngine:
             _lib.check(self.lib.pmc_stream_synchronize(self._stream), "pmc_stream_synchronize")
         self.step_idx += 1
         return self._np_sums
+
+    def exchange_enqueue(self, comm, adapt, n_total):
+        """Sharded device-likelihood step: behind this rank's accept (``accept_enqueue(host_sums=False)``, no adaptation in
+        that launch) the ranks' D + 4 sums are added in rank order, sigma / mu updated on the device, the global sums
+        written to ``h_sums`` and the completion word ``h_done[1]`` stored -- one launch on the engine's stream.  ``comm``:
+        the communicator of :func:`small_comm` (``pmc_comm_adapt_update``: the wait for the peers is bounded by
+        ``wait_timeout`` on the device), or None: ``allreduce_sums`` through the process group, then ``pmc_adapt_update``.
+        The accept launch, which stores ``h_calls``, completes before this launch starts (same stream), so the word orders
+        the host's read of ``h_calls`` too."""
+        mode, c_sigma, c_mu, cap = adapt
+        done = _lib.pmc_done_t(flag=self.h_done.data_ptr() + 8, value=self.step_idx + 1, ticket=None)
+        if self._sums_part is None:
+            self._sums_part = (C.c_void_p * 1)(self.sums.data_ptr())
+        state = self.adapt_state.data_ptr()
+        if comm:
+            _lib.check(self.lib.pmc_comm_adapt_update(comm, self._sums_part, 1, self.D, None, self.h_sums.data_ptr(), state,
+                                                      mode, c_sigma, c_mu, cap, float(n_total), C.byref(done),
+                                                      float(self.wait_timeout), self._stream), "pmc_comm_adapt_update")
+        else:
+            allreduce_sums(self.sums, self.group)
+            _lib.check(self.lib.pmc_adapt_update(self._sums_part, 1, self.D, None, self.h_sums.data_ptr(), state, mode,
+                                                 c_sigma, c_mu, cap, float(n_total), C.byref(done), self._stream),
+                       "pmc_adapt_update")
+
+    def exchange_wait(self):
+        """Wait for the completion word of :meth:`exchange_enqueue`; returns the GLOBAL sums on the host.  A peer that did
+        not deliver within ``wait_timeout`` shows as NaN in ``sums[0]`` and raises on every rank."""
+        # (the device gives its peers wait_timeout from the moment the exchange launch starts, which is behind this step's
+        #  likelihood and accept: the host allows for both, so that a missing peer arrives here as NaN, not as a host timeout)
+        _lib.check(self.lib.pmc_wait_flag(self.h_done.data_ptr() + 8, self.step_idx + 1, 2.0 * self.wait_timeout + 5.0),
+                   "pmc_wait_flag")
+        self.step_idx += 1
+        sums = self._np_sums
+        if sums[0] != sums[0]:
+            raise _lib.PocomcAmdError("sharded step: a rank did not deliver its sums within wait_timeout")
+        return sums
 
     def accept_reduce(self, beta, nu=0.0, want_mask=False):
         """Metropolis accept + global sums; returns the (all-reduced) host copy."""
@@ -1276,6 +1313,20 @@ def _step_device_likelihood(eng, ad, beta, nu, n_total, log_prior, log_like, mor
     return eng.calls_reached(), sums
 
 
+def _step_device_likelihood_sharded(eng, ad, comm, beta, nu, n_total, log_prior, log_like, more):
+    # walkers row-sharded over the ranks: as above, but the accept of this rank's rows neither adapts nor hands its sums to
+    # the host; one more launch behind it exchanges the ranks' sums (rank order: the same bits on every rank), adapts sigma /
+    # mu and stores the completion word the step's one wait is for.  h_calls (this rank's rows that reached the likelihood) is
+    # stored by the accept launch, which completes before the exchange launch starts: read it behind that word only
+    eng.evaluate_device(log_prior, log_like)
+    eng.accept_enqueue(beta, nu, host_sums=False)
+    eng.exchange_enqueue(comm, ad.coefficients(), n_total)
+    if more:
+        eng.propose(None, nu, step=eng.step_idx + 1)
+    sums = eng.exchange_wait()
+    return eng.calls_reached(), sums
+
+
 def _step_pipelined(eng, ad, beta, nu, n_total, log_prior, log_like, more):       # lanes on one stream, sigma / mu on the device
     return eng.step_pipelined(beta, nu, ad.coefficients(), n_total, log_prior, log_like, more=more)
 
@@ -1346,9 +1397,6 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     # the likelihood is a GPU callable (tensor in, tensor out): x' never goes to the host, logl' is never uploaded
     device_like = bool(option_dict.get("device_likelihood", False))
     if device_like:
-        if _sharded(group):
-            raise NotImplementedError("device_likelihood: sharded walkers (world > 1) are not supported; "
-                                      "use a host likelihood or one process")
         if have_blobs:
             raise ValueError("device_likelihood: blobs are not supported")
         if replay is not None or trace is not None:
@@ -1388,7 +1436,14 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     if device_like:
         eng.adapt_upload(float(ad.sigma), ad.mu)
         eng.propose(ad.sigma, nu)
-        step = partial(_step_device_likelihood, eng, ad, beta, nu, n_total, log_prior, log_like)
+        if _sharded(group):
+            if n_dim > 256:
+                raise ValueError("device_likelihood: sharded walkers need D <= 256 (the adaptation runs on the device)")
+            # the ranks' sums meet inside the library where it has a working mailbox; through the process group otherwise
+            comm = small_comm(eng.lib, group, n_dim + 4)
+            step = partial(_step_device_likelihood_sharded, eng, ad, comm, beta, nu, n_total, log_prior, log_like)
+        else:
+            step = partial(_step_device_likelihood, eng, ad, beta, nu, n_total, log_prior, log_like)
     elif pipelined:
         eng.start_pipeline(float(ad.sigma), ad.mu, nu)
         step = partial(_step_pipelined, eng, ad, beta, nu, n_total, log_prior, log_like)

@@ -154,12 +154,14 @@ class Sampler:
         ``mcmc_options``  extra keys of the MCMC kernels' ``option_dict`` (``pocomc_amd/mcmc.py``), e.g.
                           ``dict(x_order='F')`` (Fortran-ordered ``x`` for the likelihood, pipelined kernel call),
                           ``dict(lanes=2)``;
-        ``device_likelihood``  (needs ``vectorize=True``, no blobs, one process) the likelihood runs on the GPU: it is
+        ``device_likelihood``  (needs ``vectorize=True``, no blobs) the likelihood runs on the GPU: it is
                           called with an ``(n, D)`` float64 tensor on the flow's device (rows in walker order; a column-major
                           view inside the MCMC steps) on the current torch stream and returns an ``(n,)`` float64 or
                           float32 tensor on that device.  It must be row-wise and free of side effects, and must not keep
                           its input, whose buffer is reused.  In the MCMC steps x' never goes to the host and logl' is
-                          never uploaded.
+                          never uploaded.  Sharded (one process per GPU): it is called on every rank with that rank's
+                          rows only, on that rank's device and current stream; it must be the same function on every
+                          rank.
 
         Supported ``train_config`` keys: those of ``sampler.py:287-299`` (``validation_split, epochs, batch_size,
         patience, learning_rate, annealing, gaussian_scale, laplace_scale, noise, shuffle, clip_grad_norm, verbose``),
@@ -204,8 +206,6 @@ class Sampler:
                 raise ValueError("device_likelihood=True needs vectorize=True: the likelihood is called on whole blocks of rows")
             if self.have_blobs:
                 raise ValueError("device_likelihood=True does not support blobs (blobs_dtype)")
-            if self.ranks.world > 1:
-                raise NotImplementedError("device_likelihood=True is not supported for a sharded Sampler (world > 1)")
         if vectorize and self.have_blobs:
             raise ValueError("Cannot vectorize likelihood with blobs.")
         self.pool, self.distribute = pool, map
@@ -509,10 +509,12 @@ class Sampler:
     def _log_like_all(self, x):
         """The likelihood of all rows of ``x`` (identical on every rank), each rank evaluating its share."""
         if self.device_likelihood:
-            # (warm-up and evidence: the rows go up, the values come back)
-            xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.flow.device)
-            logl = _mcmc.device_logl(self.log_likelihood(xt), len(x), self.flow.device)
-            return logl.to(torch.float64).cpu().numpy(), None
+            # (warm-up and evidence: this rank's share of the rows goes up to its device, the values come back and are
+            #  gathered, so that every rank holds the same logl)
+            sl = self.ranks.share(len(x))
+            xt = torch.from_numpy(np.ascontiguousarray(x[sl], dtype=np.float64)).to(self.flow.device)
+            logl = _mcmc.device_logl(self.log_likelihood(xt), len(xt), self.flow.device)
+            return self.ranks.gather_rows(logl.to(torch.float64).cpu().numpy(), len(x)), None
         if self.world == 1:
             return self._log_like(x)
         sl = self.ranks.share(len(x))

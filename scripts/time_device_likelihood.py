@@ -2,12 +2,18 @@
 Rosenbrock on the host: 1e4 walkers x 32 dimensions, maf3 flow, prior U(-10, 10)^32, beta = 0.5, preconditioned tpCN.
 
     python scripts/time_device_likelihood.py [--walkers 10000] [--dim 32] [--steps 200] [--repeats 3] [--out FILE]
-                                             [--modes host_numpy,device_torch]
+                                             [--modes host_numpy,device_torch] [--ranks N]
 
 The device mode hands the likelihood an (n, D) float64 view of x' on the GPU (option_dict["device_likelihood"]); the
 host mode is the pipelined host call (x_order='F': x' to pinned host memory, logl' read back by the accept kernel).
 Both calls take the same Philox variates; each mode is timed over --repeats calls of --steps steps after one warm-up
-call, and the best and median steps/s are printed as one JSON line."""
+call, and the best and median steps/s are printed as one JSON line.
+
+``--ranks N`` (N > 1): the walker set row-sharded over N ranks, --walkers rows PER RANK, each rank a fresh child process of
+this script on the visible GPUs round robin, talking over gloo; every rank prints its own JSON line (``rank`` in it) and
+``--out FILE`` becomes ``FILE.rank<r>``.  The exchange tier is the environment's (``PMC_C_ALLREDUCE``, ``PMC_COMM_MAILBOX``).
+Ranks that share one GPU share its compute units: their per-rank figure is what the exchange launch and the contention
+cost together, not a scaling number."""
 import argparse
 import json
 import os
@@ -28,6 +34,21 @@ def rosenbrock_torch(x):
     return -(10.0 * (t * t) + (a - 1.0) ** 2).sum(dim=1)
 
 
+def launch_ranks(n_ranks):
+    """This script once per rank, each a fresh child process; returns the worst exit status."""
+    import socket
+    import subprocess
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    procs = []
+    for r in range(n_ranks):
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE=str(n_ranks))
+        procs.append(subprocess.Popen([sys.executable] + sys.argv, env=env))
+    return max(abs(p_.wait()) for p_ in procs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--walkers", type=int, default=10000)
@@ -37,7 +58,17 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--modes", default="host_numpy,device_torch", help="comma-separated subset to time (e.g. one mode "
                     "under a memory-copy trace)")
+    ap.add_argument("--ranks", type=int, default=1, help="shard the walkers over this many ranks (--walkers rows each)")
     args = ap.parse_args()
+    rank, world = 0, 1
+    if args.ranks > 1:
+        if "WORLD_SIZE" not in os.environ:
+            sys.exit(launch_ranks(args.ranks))
+        import torch.distributed as dist
+        rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+        assert world == args.ranks, f"--ranks {args.ranks} but WORLD_SIZE={world}"
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        torch.cuda.set_device(rank % torch.cuda.device_count())
     from scipy.stats import uniform
     import pocomc_amd as pc
     from pocomc_amd import mcmc as pmcmc
@@ -46,14 +77,15 @@ def main():
 
     N, D = args.walkers, args.dim
     prior = pc.Prior([uniform(-10, 20)] * D)
-    rng = np.random.default_rng(0)
+    rng = np.random.default_rng(rank)                      # (every rank its own rows)
     scaler = pc.Reparameterize(D, bounds=prior.bounds)
-    scaler.fit(prior.rvs(4 * N))
+    scaler.fit(np.random.default_rng(0).uniform(-10.0, 10.0, size=(4 * N, D)) if world > 1 else prior.rvs(4 * N))
     x = rng.uniform(-2.0, 2.0, size=(N, D))
     u = scaler.forward(x)
     flow = pc.Flow(D, "maf3", seed=0)
     geo = Geometry()
-    geo.fit(flow.forward(torch.from_numpy(u).float())[0].numpy().astype(np.float64))
+    u_geo = u if rank == 0 else scaler.forward(np.random.default_rng(0).uniform(-2.0, 2.0, size=(N, D)))   # (replicated: rank 0's rows)
+    geo.fit(flow.forward(torch.from_numpy(u_geo).float())[0].numpy().astype(np.float64))
     logl0 = rosenbrock(np.asfortranarray(x))
 
     def call(device):
@@ -63,6 +95,8 @@ def main():
         funcs = dict(loglike=like, logprior=prior.logpdf, scaler=scaler, flow=flow, theta_geometry=geo)
         opts = dict(n_max=args.steps, n_steps=10 ** 9, progress_bar=None, proposal_scale=2.38 / D ** 0.5, seed=3)
         opts.update(dict(device_likelihood=True) if device else dict(x_order="F"))
+        if world > 1:
+            opts.update(group=None, shard_offset=rank * N)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = pmcmc.preconditioned_pcn(state, funcs, opts)
@@ -71,7 +105,8 @@ def main():
         return res["steps"] / dt, res
 
     out = dict(walkers=N, dim=D, flow="maf3", steps=args.steps, repeats=args.repeats, kind="preconditioned_pcn",
-               gpu=torch.cuda.get_device_name(0))
+               gpu=torch.cuda.get_device_name(torch.cuda.current_device()), rank=rank, ranks=world,
+               c_allreduce=os.environ.get("PMC_C_ALLREDUCE", "1"), mailbox=os.environ.get("PMC_COMM_MAILBOX", ""))
     results = {}
     modes = args.modes.split(",")
     for mode, device in (("host_numpy", False), ("device_torch", True)):
@@ -87,11 +122,17 @@ def main():
         out[mode]["accept"] = float(res["accept"])
     if len(results) == 2:
         out["speedup_median"] = out["device_torch"]["steps_per_s_median"] / out["host_numpy"]["steps_per_s_median"]
+    if world > 1:                                           # 0: device mailboxes, 1: host mailboxes, none: torch.distributed
+        out["comm_kinds"] = sorted({int(pmcmc._lib.load().pmc_comm_kind(v[0])) for v in pmcmc._COMMS.values() if v[0]})
     line = json.dumps(out)
     print(line)
     if args.out:
-        with open(args.out, "w") as f:
+        with open(args.out if world == 1 else f"{args.out}.rank{rank}", "w") as f:
             f.write(line + "\n")
+    if world > 1:
+        pmcmc.drop_comms()
+        dist.barrier()
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
