@@ -564,7 +564,24 @@ typedef struct pmc_step {
      * exchange's completion word, and not before. */
     double* lik_x;            /* device f64 [D][n] or NULL */
     int64_t* h_calls;         /* pinned host int64 [1] */
+    /* Blobs of a likelihood on the device (the derived quantities a likelihood returns next to logl, mcmc.py:112-121 and
+     * :139: `blobs[mask] = blobs_prime[mask]`): each walker owns one row of blob_row_bytes bytes of any content -- the
+     * kernels move bytes, the caller knows the element type.  With lik_x and both pointers non-NULL and blob_row_bytes > 0,
+     *   the caller's likelihood writes the blobs of x' into blob_prop on the same stream as logl' into p_logl (all n rows:
+     *   the rows that did not reach the likelihood hold whatever it returned for the walker's current x);
+     *   pmc_step_post's accept launch copies blob_prop's row to blob_cur for every ACCEPTED walker, in the same launch
+     *   that moves u, x and theta -- no further launch, no mask on the host.  A rejected walker's row is neither read nor
+     *   written: rows the gate set to -inf and a NaN logl' have alpha = 0 (:134), so their blobs never move.
+     * Both buffers are device memory: the kernel boundary orders the copy for the next launch on the stream; the blobs take
+     * no part in the completion words.  blob_row_bytes is a multiple of 4, at most PMC_BLOB_ROW_BYTES_MAX; the buffers are
+     * 4-byte aligned and distinct.  Zero / NULL: no blobs, and the accept launch is the one without them.  pmc_accept and
+     * pmc_accept_armed take no blobs. */
+    void* blob_cur;           /* device [n][blob_row_bytes] or NULL */
+    const void* blob_prop;    /* device [n][blob_row_bytes] or NULL */
+    int64_t blob_row_bytes;
 } pmc_step_t;
+
+#define PMC_BLOB_ROW_BYTES_MAX (1 << 20)
 
 #define PMC_ADAPT_TPCN 1      /* sigma <- |min(sigma + c (mean alpha - 0.234), cap)|      (mcmc.py:152, :476) */
 #define PMC_ADAPT_PRWM 2      /* sigma <- sigma + c (mean alpha - 0.234)                   (mcmc.py:314) */

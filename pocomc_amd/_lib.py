@@ -98,7 +98,8 @@ class pmc_step_t(C.Structure):
                 ("adapt_c_sigma", C.c_double), ("adapt_c_mu", C.c_double), ("adapt_cap", C.c_double),
                 ("adapt_n_total", C.c_double), ("adapt_other", C.c_void_p * 7), ("adapt_n_other", C.c_int32),
                 ("adapt_pad2", C.c_int32), ("h_clean", c_p), ("clean_count", c_p),
-                ("fill_rejected", C.c_int32), ("fill_pad", C.c_int32), ("lik_x", c_p), ("h_calls", c_p)]
+                ("fill_rejected", C.c_int32), ("fill_pad", C.c_int32), ("lik_x", c_p), ("h_calls", c_p),
+                ("blob_cur", c_p), ("blob_prop", c_p), ("blob_row_bytes", C.c_int64)]
 
 
 # name -> (restype, argtypes); every symbol include/pocomc_amd.h declares

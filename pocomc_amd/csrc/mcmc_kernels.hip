@@ -16,6 +16,7 @@
 #include <sys/stat.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 #include "philox.h"
 #include "pmc_internal.h"
 
@@ -289,12 +290,16 @@ __device__ __forceinline__ void adapt_apply(const pmc_adapt_args& ad, const doub
     }
 }
 
+// BLOBS: the walkers carry blobs (pmc_step_t.blob_cur) and an accepted row also takes its proposal's blob row.  The
+// instance without them has no blob argument at all: it is the kernel as it was before blobs existed.
+struct accept_no_blobs {};
+template <bool BLOBS>
 __global__ __launch_bounds__(256) void accept_kernel(
     int preconditioned, int tpcn, pmc_state_t cur, pmc_proposal_t prop, double beta, double nu,
     pmc_rng_t rng, double* __restrict__ alpha_out, int32_t* __restrict__ accept_out,
     double* __restrict__ partials, unsigned* __restrict__ ticket, double* __restrict__ sums,
     double* __restrict__ sums_copy, long long* __restrict__ done_flag, long long done_value, int64_t n, int D,
-    pmc_adapt_args ad, pmc_gate_args gate) {
+    pmc_adapt_args ad, pmc_gate_args gate, std::conditional_t<BLOBS, pmc_blob_args, accept_no_blobs> blob) {
     __shared__ int flag[ACC_ROWS];
     __shared__ double colsum[8][33];
     __shared__ int is_last;
@@ -395,6 +400,29 @@ __global__ __launch_bounds__(256) void accept_kernel(
             P[4 + j] = t;
         }
         __syncthreads();
+    }
+
+    if constexpr (BLOBS) {
+        // the block's rows are contiguous in both blob buffers: one flattened (row, dword) index over them, so that narrow
+        // rows (a few dwords) and wide ones alike move in coalesced dwords; four loads in flight per thread.  Rejected rows
+        // are neither read nor written.  Device memory: the kernel boundary orders the stores for the next launch
+        const int rw = blob.row_dwords;
+        const uint32_t* __restrict__ src = blob.prop + (size_t)row0 * rw;
+        uint32_t* __restrict__ dst = blob.cur + (size_t)row0 * rw;
+        const int total = rows * rw;
+        for (int i0 = tid; i0 < total; i0 += 4 * 256) {
+            uint32_t v[4];
+            bool a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = i0 + k * 256;
+                a[k] = i < total && flag[i / rw];
+                v[k] = a[k] ? src[i] : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (a[k]) dst[i0 + k * 256] = v[k];
+        }
     }
 
     // ---- publish this block's partials, draw a ticket; the last arriver reduces (guide G16)
@@ -798,7 +826,8 @@ extern "C" int64_t pmc_accept_workspace_bytes(int64_t n, int32_t D) {
 static int accept_impl(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta,
                        double nu, const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums,
                        double* sums_copy, bool armed, const pmc_done_t* done, void* workspace, int64_t n, int32_t D,
-                       void* stream, const pmc_adapt_args* adapt = nullptr, const pmc_gate_args* gate = nullptr) {
+                       void* stream, const pmc_adapt_args* adapt = nullptr, const pmc_gate_args* gate = nullptr,
+                       const pmc_blob_args* blob = nullptr) {
     if (!cur || !prop || !rng || !sums || !workspace || n < 0 || D < 1) return pmc_fail("pmc_accept: bad argument");
     if (!cur->u || !cur->x || !cur->logdetj || !cur->logl || !cur->logp || !prop->u || !prop->x ||
         !prop->logdetj || !prop->logl || !prop->logp)
@@ -818,10 +847,16 @@ static int accept_impl(int kind, int preconditioned, pmc_state_t* cur, const pmc
     // the ticket word is re-armed by every call (a memset node ahead of the launch): no state between calls.
     // pmc_accept_armed skips it: the kernel leaves the word at zero itself.
     if (!armed && hipMemsetAsync(ticket, 0, sizeof(unsigned), st) != hipSuccess) return pmc_fail("pmc_accept: memset");
-    hipLaunchKernelGGL(accept_kernel, dim3(nb), dim3(256), 0, st, preconditioned, tpcn, *cur, *prop, beta, nu, *rng,
-                       alpha_out, accept_out, partials, ticket, sums, sums_copy, done ? (long long*)done->flag : nullptr,
-                       done ? (long long)done->value : 0LL, n, (int)D, adapt ? *adapt : pmc_adapt_args{},
-                       gate ? *gate : pmc_gate_args{});
+    if (blob && blob->row_dwords > 0)
+        hipLaunchKernelGGL(accept_kernel<true>, dim3(nb), dim3(256), 0, st, preconditioned, tpcn, *cur, *prop, beta, nu, *rng,
+                           alpha_out, accept_out, partials, ticket, sums, sums_copy, done ? (long long*)done->flag : nullptr,
+                           done ? (long long)done->value : 0LL, n, (int)D, adapt ? *adapt : pmc_adapt_args{},
+                           gate ? *gate : pmc_gate_args{}, *blob);
+    else
+        hipLaunchKernelGGL(accept_kernel<false>, dim3(nb), dim3(256), 0, st, preconditioned, tpcn, *cur, *prop, beta, nu, *rng,
+                           alpha_out, accept_out, partials, ticket, sums, sums_copy, done ? (long long*)done->flag : nullptr,
+                           done ? (long long)done->value : 0LL, n, (int)D, adapt ? *adapt : pmc_adapt_args{},
+                           gate ? *gate : pmc_gate_args{}, accept_no_blobs{});
     return pmc_check_launch("accept_kernel");
 }
 
@@ -1114,12 +1149,13 @@ extern "C" int pmc_comm_adapt_update(void* cc, const double* const* parts, int32
 int pmc_accept_adapt(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta, double nu,
                      const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums, double* sums_copy,
                      const pmc_done_t* done, void* workspace, int64_t n, int32_t D, void* stream,
-                     const pmc_adapt_args* adapt, const pmc_gate_args* gate) {
+                     const pmc_adapt_args* adapt, const pmc_gate_args* gate, const pmc_blob_args* blob) {
     if (adapt && ((adapt->state && adapt->mode) || adapt->n_other) && D > 256)
         return pmc_fail("pmc_accept: device adaptation needs D <= 256");
     if (gate && gate->calls_out && n < 1) return pmc_fail("pmc_accept: a gated launch needs rows");
+    if (blob && blob->row_dwords > 0 && (!blob->cur || !blob->prop)) return pmc_fail("pmc_accept: null blob buffer");
     return accept_impl(kind, preconditioned, cur, prop, beta, nu, rng, alpha_out, accept_out, sums, sums_copy, true,
-                       done, workspace, n, D, stream, adapt, gate);
+                       done, workspace, n, D, stream, adapt, gate, blob);
 }
 
 extern "C" int pmc_logw(const double* logl, const double* beta, const double* logz, double beta_final,

@@ -65,9 +65,17 @@ struct pmc_gate_args {
     long long* calls_out;
     long long calls_n;
 };
+// the walkers' blobs (pmc_step_t.blob_cur / blob_prop) as rows of row_dwords 32-bit words: the accept launch copies the
+// accepted rows' from prop to cur.  row_dwords 0: no blobs.
+struct pmc_blob_args {
+    uint32_t* cur;
+    const uint32_t* prop;
+    int row_dwords;
+};
 int pmc_accept_adapt(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta, double nu,
                      const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums, double* sums_copy,
                      const pmc_done_t* done, void* workspace, int64_t n, int32_t D, void* stream,
-                     const pmc_adapt_args* adapt, const pmc_gate_args* gate = nullptr);
+                     const pmc_adapt_args* adapt, const pmc_gate_args* gate = nullptr,
+                     const pmc_blob_args* blob = nullptr);
 
 #endif

@@ -223,6 +223,15 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
     // device likelihood: logl' is in p_logl and logp' in p_logp already (the device prior, or pmc_step_lik_rows)
     const bool devlik = s->lik_x != nullptr;
     if (devlik && (!s->clean_count || !s->h_calls)) return pmc_fail("pmc_step_post: a device likelihood needs clean_count and h_calls");
+    // blobs of a device likelihood (blob_cur / blob_prop): the accept launch moves the accepted rows'
+    const bool blobs = s->blob_row_bytes != 0 && s->blob_cur && s->blob_prop;
+    if (blobs) {
+        if (!devlik) return pmc_fail("pmc_step_post: blobs on the device need a device likelihood (lik_x)");
+        if (s->blob_row_bytes < 0 || s->blob_row_bytes % 4 || s->blob_row_bytes > PMC_BLOB_ROW_BYTES_MAX)
+            return pmc_fail("pmc_step_post: blob_row_bytes must be a multiple of 4 between 4 and PMC_BLOB_ROW_BYTES_MAX");
+        if (((uintptr_t)s->blob_cur | (uintptr_t)s->blob_prop) & 3) return pmc_fail("pmc_step_post: blob buffers must be 4-byte aligned");
+        if (s->blob_cur == s->blob_prop) return pmc_fail("pmc_step_post: blob_cur and blob_prop must be different buffers");
+    }
     if (!direct && !devlik) {
         if (hipMemcpyAsync(s->p_logl, s->h_logl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_post: H2D");
@@ -252,9 +261,11 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
         ad.n_other = s->adapt_n_other;
         pmc_gate_args gate{};
         if (devlik) gate = pmc_gate_args{s->p_fin, s->clean_count, (long long*)s->h_calls, (long long)n};
+        pmc_blob_args blob{};
+        if (blobs) blob = pmc_blob_args{(uint32_t*)s->blob_cur, (const uint32_t*)s->blob_prop, (int)(s->blob_row_bytes / 4)};
         rc = pmc_accept_adapt(s->kind, s->preconditioned, &cur, &prop, beta, nu, rng, s->alpha, s->accept, s->sums,
                               copy_sums ? s->h_sums : nullptr, (copy_sums && s->h_done) ? &dn : nullptr, s->ws, n, s->D,
-                              stream, &ad, &gate);
+                              stream, &ad, &gate, &blob);
     }
     else if (s->adapt_state && s->adapt_mode)
         return pmc_fail("pmc_step_post: adaptation on the device needs host_direct");

@@ -8,7 +8,8 @@ accept -> reductions  (``include/pocomc_amd.h``), the host only evaluates the
 user's prior / likelihood black boxes on the compacted finite rows
 (``mcmc.py:100-121``) and the scalar adaptation / stopping logic
 (``mcmc.py:152-180``).  With ``option_dict["device_likelihood"]`` the likelihood is a
-GPU callable too: x' stays on the device, and the host reads the sums of each step only.
+GPU callable too: x' stays on the device, and the host reads the sums of each step only; blobs such a likelihood returns
+stay in HBM as well and move with the accepted walkers in the accept launch.
 
 
 ``StepEngine`` is the reusable object (bench.py drives it directly); the four
@@ -156,11 +157,51 @@ def device_logl(out, n, device):
         raise ValueError(f"device likelihood: expected shape ({n},), got {tuple(out.shape)}")
     if out.dtype not in (torch.float64, torch.float32):
         raise ValueError(f"device likelihood: expected dtype float64 or float32, got {out.dtype}")
+    _on_device(out, device, "device likelihood")
+    return out
+
+
+def _on_device(t, device, who):
     dev = torch.device(device)
     index = dev.index if (dev.index is not None or dev.type != "cuda") else torch.cuda.current_device()
-    if out.device.type != dev.type or out.device.index != index:
-        raise ValueError(f"device likelihood: expected a tensor on device {dev.type}:{index}, got one on {out.device}")
-    return out
+    if t.device.type != dev.type or t.device.index != index:
+        raise ValueError(f"{who}: expected a tensor on device {dev.type}:{index}, got one on {t.device}")
+
+
+BLOB_DTYPES = (torch.float64, torch.float32, torch.int64, torch.int32)
+
+
+def _blob_row_bytes(b):
+    """Bytes of one walker's blob in the ``(n, *blob_shape)`` tensor ``b``."""
+    elems = 1
+    for s in b.shape[1:]:
+        elems *= int(s)
+    return elems * b.element_size()
+
+
+def device_blobs(out, n, device, like=None):
+    """The blobs of a device likelihood that returns ``(logl, blobs)``: ``blobs`` an ``(n, *blob_shape)`` tensor on the
+    walkers' device, float64 / float32 / int64 / int32, returned contiguous.  ``like``: a tensor whose trailing shape and
+    dtype the blobs must have (the walkers' own blobs: shape and dtype are fixed by the first call).  Anything else raises
+    ValueError naming what was received."""
+    if not isinstance(out, tuple) or len(out) != 2:
+        got = f"a tuple of {len(out)}" if isinstance(out, tuple) else type(out).__name__
+        raise ValueError(f"device blobs: expected the likelihood to return a tuple (logl, blobs), got {got}")
+    b = out[1]
+    if not isinstance(b, torch.Tensor):
+        raise ValueError(f"device blobs: expected a ({n}, ...) tensor on {device}, got {type(b).__name__}")
+    if b.ndim < 1 or b.shape[0] != n:
+        raise ValueError(f"device blobs: expected shape ({n}, ...), got {tuple(b.shape)}")
+    if b.dtype not in BLOB_DTYPES:
+        raise ValueError(f"device blobs: expected dtype float64, float32, int64 or int32, got {b.dtype}")
+    _on_device(b, device, "device blobs")
+    if _blob_row_bytes(b) == 0:
+        raise ValueError(f"device blobs: expected at least one element per walker, got shape {tuple(b.shape)}")
+    if like is not None and tuple(b.shape[1:]) != tuple(like.shape[1:]):
+        raise ValueError(f"device blobs: expected blob_shape {tuple(like.shape[1:])} as in the first call, got {tuple(b.shape[1:])}")
+    if like is not None and b.dtype != like.dtype:
+        raise ValueError(f"device blobs: expected dtype {like.dtype} as in the first call, got {b.dtype}")
+    return b.contiguous()
 
 
 def _timed(fn, timers, key):
@@ -477,6 +518,9 @@ class StepEngine:
         self.device_likelihood = False
         self.p_xl = None
         self.h_calls = None
+        # blobs of the device likelihood (set_device_blobs): the walkers' and the proposals', (n, *blob_shape) each
+        self.blobs = None
+        self.p_blobs = None
         self._sums_part = None   # (exchange_enqueue: this rank's sums as the exchange's single part)
 
     def __del__(self):
@@ -562,6 +606,20 @@ class StepEngine:
         self._step.clean_count = self._clean_count.data_ptr()
         self.device_likelihood = True
         self._pre_cfg = None
+
+    def set_device_blobs(self, blobs):
+        """The walkers carry blobs of a device likelihood that returns ``(logl, blobs)``: ``blobs`` (a device tensor
+        ``(n, *blob_shape)``, checked by :func:`device_blobs`) is copied into the engine's own buffer, and the accept launch
+        moves an accepted walker's row from the proposals' buffer, which :meth:`evaluate_device` fills
+        (``pmc_step_t.blob_cur``).  After :meth:`set_device_likelihood`."""
+        assert self.device_likelihood
+        b = device_blobs((None, blobs), self.n, self.device)
+        self.blobs = torch.empty_like(b)
+        self.blobs.copy_(b)
+        self.p_blobs = torch.empty_like(b)
+        self._step.blob_cur = self.blobs.data_ptr()
+        self._step.blob_prop = self.p_blobs.data_ptr()
+        self._step.blob_row_bytes = _blob_row_bytes(b)
 
     def set_mu(self, mu):
         # pinned staging + async copy; the previous upload was consumed by a kernel that has
@@ -780,8 +838,9 @@ class StepEngine:
 
     def evaluate_device(self, log_prior, log_like):
         """The likelihood of the step in flight on the device (``pmc_step_t.lik_x``), on the engine's stream: the callable
-        gets ``p_xl.t()``, an (n, D) float64 view of x' (rows in walker order, column-major), and returns (logl', None);
-        logl' goes into ``p_logl``.  A prior the device does not evaluate runs on the host first, on x' and the finite mask
+        gets ``p_xl.t()``, an (n, D) float64 view of x' (rows in walker order, column-major), and returns (logl', None), or
+        (logl', blobs') where the walkers carry blobs (:meth:`set_device_blobs`); logl' goes into ``p_logl``, blobs' into
+        ``p_blobs``.  A prior the device does not evaluate runs on the host first, on x' and the finite mask
         (``mcmc.py:105-107``), and ``pmc_step_lik_rows`` uploads its logp' and writes the likelihood's input.  Nothing is
         waited for otherwise.  Returns the rows handed to the likelihood; the rows that reached it come with the sums
         (:meth:`calls_reached`)."""
@@ -796,8 +855,10 @@ class StepEngine:
                 self._np_logp[~fin] = -np.inf
             _lib.check(self.lib.pmc_step_lik_rows(C.byref(self._step), self._stream), "pmc_step_lik_rows")
         with torch.cuda.stream(stream):
-            ll = device_logl(log_like(self.p_xl.t()), self.n, self.device)
-            self.p_logl.copy_(ll)
+            out = log_like(self.p_xl.t())
+            self.p_logl.copy_(device_logl(out, self.n, self.device))
+            if self.blobs is not None:
+                self.p_blobs.copy_(device_blobs(out, self.n, self.device, like=self.blobs))
         return self.n
 
     def calls_reached(self):
@@ -908,7 +969,10 @@ class StepEngine:
     def download(self, device=False):
         """The walker state as numpy arrays, or (``device=True``) as the engine's own device tensors."""
         g = (lambda t: t) if device else (lambda t: t.cpu().numpy())
-        return dict(u=g(self.u), x=g(self.x), logdetj=g(self.logdetj), logl=g(self.logl), logp=g(self.logp))
+        out = dict(u=g(self.u), x=g(self.x), logdetj=g(self.logdetj), logl=g(self.logl), logp=g(self.logp))
+        if self.blobs is not None:
+            out["blobs"] = g(self.blobs)
+        return out
 
 
 # --------------------------------------------------------------------------
@@ -1397,8 +1461,9 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     # the likelihood is a GPU callable (tensor in, tensor out): x' never goes to the host, logl' is never uploaded
     device_like = bool(option_dict.get("device_likelihood", False))
     if device_like:
-        if have_blobs:
-            raise ValueError("device_likelihood: blobs are not supported")
+        if have_blobs and not isinstance(blobs, torch.Tensor):
+            raise ValueError("device_likelihood: blobs must be a device tensor (n, *blob_shape) that the likelihood "
+                             f"returns next to logl, got {type(blobs).__name__}")
         if replay is not None or trace is not None:
             raise ValueError("device_likelihood: replayed variates and traces need the host likelihood")
     eng, pipelined = _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior,
@@ -1406,6 +1471,8 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     laned = isinstance(eng, LanedEngine)
     lanes = eng.lanes if laned else [eng]
     eng.load_state(u, x, logdetj, logl, logp)
+    if device_like and have_blobs:
+        eng.set_device_blobs(blobs)                # (the engine's own copy: the accept launches move its rows)
     nu = 0.0
     if tpcn:
         nu = float(geometry.t_nu)
@@ -1479,7 +1546,8 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     out = eng.download(device=keep)                    # (the numpy download synchronises by itself)
     for e in lanes:
         e._recycle = True
-    return dict(u=out["u"], x=out["x"], logdetj=out["logdetj"], logl=out["logl"], logp=out["logp"], blobs=blobs,
+    return dict(u=out["u"], x=out["x"], logdetj=out["logdetj"], logl=out["logl"], logp=out["logp"],
+                blobs=out.get("blobs", blobs),
                 efficiency=ad.sigma, accept=ad.mean_alpha, steps=ad.i, calls=n_calls, proposal_scale=ad.sigma,
                 evaluations=int(sum(rows_passed)))
 

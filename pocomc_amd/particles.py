@@ -9,6 +9,9 @@ rows per iteration; the kernels of ``csrc/mcmc_kernels.hip`` / ``csrc/pool.hip``
 * ``compute_logw_and_logz`` (``particles.py:215-231``): ``pmc_logw`` + ``pmc_logw_stats`` on the resident ``logl``;
 * importance weights, trimming, resampling indices and the row gather of the next walkers: ``select`` / ``take``.
 
+Blobs a device likelihood returned (``Sampler(device_blobs=True)``) arrive as device tensors and live in one more growing
+device buffer, ``(P, *blob_shape)`` of their own dtype; blobs of a host likelihood stay host arrays.
+
 Per-iteration scalars (``beta, logz, calls, ...``) stay host lists -- they are a handful of floats.  ``get`` keeps the
 reference's accessor (numpy out) for results / posterior / tests.
 """
@@ -35,9 +38,12 @@ class Particles:
         self.T = 0                                        # iterations held
         self._cap = 0
         self._rows = {}
+        self._blob_rows = None
         self._grow(32)
         self.scalars = {k: [] for k in SCALAR_KEYS}
-        self.blobs = []                                   # host arrays (arbitrary dtype), one per iteration, or None
+        # one entry per iteration: a host array (arbitrary dtype), None, or -- blobs of a device likelihood -- the
+        # iteration's block of the resident buffer _blob_rows (a view)
+        self.blobs = []
         self.results_dict = None
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self._h_stats = torch.zeros(4, dtype=torch.float64).pin_memory()
@@ -52,6 +58,21 @@ class Particles:
         for k, old in self._rows.items():
             new[k][:self.T * N].copy_(old[:self.T * N])
         self._rows, self._cap = new, cap_iters
+        if self._blob_rows is not None:
+            self._blob_buffer(self._blob_rows)
+
+    def _blob_buffer(self, like):
+        """The resident blob buffer at the current capacity, rows of ``like``'s trailing shape and dtype; the blocks held
+        so far move over and ``blobs`` points into the new buffer."""
+        N, old = self.n_particles, self._blob_rows
+        self._blob_rows = torch.empty((self._cap * N,) + tuple(like.shape[1:]), dtype=like.dtype, device=self.device)
+        if old is not None:
+            self._blob_rows[:self.T * N].copy_(old[:self.T * N])
+            self.blobs = [self._blob_rows[i * N:(i + 1) * N] for i in range(self.T)]
+
+    def blob_rows(self):
+        """Device view of the blobs over the whole pool (blobs of a device likelihood), or None."""
+        return None if self._blob_rows is None else self._blob_rows[:self.P]
 
     @property
     def P(self):
@@ -77,7 +98,20 @@ class Particles:
         for k in SCALAR_KEYS:
             if k in data:
                 self.scalars[k].append(data[k])
-        self.blobs.append(data.get("blobs"))
+        b = data.get("blobs")
+        if isinstance(b, torch.Tensor):
+            if b.shape[0] != N:
+                raise ValueError(f"blobs: expected {N} rows, got {b.shape[0]}")
+            if self._blob_rows is None:
+                if self.T:
+                    raise ValueError("blobs: device blobs must be there from the first iteration on")
+                self._blob_buffer(b)
+            if tuple(b.shape[1:]) != tuple(self._blob_rows.shape[1:]) or b.dtype != self._blob_rows.dtype:
+                raise ValueError(f"blobs: expected rows of shape {tuple(self._blob_rows.shape[1:])} and dtype "
+                                 f"{self._blob_rows.dtype}, got {tuple(b.shape[1:])} and {b.dtype}")
+            self._blob_rows[lo:lo + N].copy_(b.to(self.device), non_blocking=True)
+            b = self._blob_rows[lo:lo + N]
+        self.blobs.append(b)
         self.T += 1
         self.results_dict = None
 
@@ -90,6 +124,11 @@ class Particles:
         if key in SCALAR_KEYS:
             return self.scalars[key][index] if index is not None else np.asarray(self.scalars[key])
         if key == "blobs":
+            if self._blob_rows is not None:                     # (resident: downloaded like the row quantities)
+                if index is not None:
+                    return self.blobs[index].cpu().numpy()          # (that iteration's block alone)
+                a = self.blob_rows().cpu().numpy()
+                return a if flat else a.reshape((self.T, N) + a.shape[1:])
             if index is not None:
                 return self.blobs[index]
             return np.concatenate(self.blobs) if flat else np.asarray(self.blobs)
@@ -189,8 +228,10 @@ class Particles:
 
     # ------------------------------------------------------------- checkpoints
     def __getstate__(self):
-        return dict(n_particles=self.n_particles, n_dim=self.n_dim, T=self.T, scalars=self.scalars, blobs=self.blobs,
-                    rows={k: self.rows(k).cpu().numpy() for k in ROW_KEYS})
+        resident = self._blob_rows is not None
+        blobs = list(self.get("blobs")) if resident else self.blobs         # (one download, split by iteration)
+        return dict(n_particles=self.n_particles, n_dim=self.n_dim, T=self.T, scalars=self.scalars, blobs=blobs,
+                    blobs_resident=resident, rows={k: self.rows(k).cpu().numpy() for k in ROW_KEYS})
 
     def __setstate__(self, st):
         self.__init__(st["n_particles"], st["n_dim"])
@@ -200,3 +241,9 @@ class Particles:
         for k in ROW_KEYS:
             self._rows[k][:T * self.n_particles].copy_(torch.from_numpy(st["rows"][k]))
         self.T, self.scalars, self.blobs = T, st["scalars"], st["blobs"]
+        if st.get("blobs_resident") and T:
+            host = np.ascontiguousarray(np.concatenate(st["blobs"]))
+            self._blob_rows = None
+            self._blob_buffer(torch.from_numpy(host[:0]))
+            self._blob_rows[:T * self.n_particles].copy_(torch.from_numpy(host))
+            self.blobs = [self._blob_rows[i * self.n_particles:(i + 1) * self.n_particles] for i in range(T)]

@@ -145,7 +145,7 @@ class Sampler:
                  train_frequency=None, precondition=True, dynamic=True, metric="ess", n_prior=None,
                  sample="tpcn", n_steps=None, n_max_steps=None, resample="mult", output_dir=None,
                  output_label=None, random_state=None, n_ess=None, group=None, mcmc_options=None,
-                 device_likelihood=False):
+                 device_likelihood=False, device_blobs=False):
         """Arguments and defaults of ``pocomc/sampler.py:154-185``, plus
 
         ``group``         a ``torch.distributed`` process group (default: the initialised default group): one process
@@ -154,14 +154,20 @@ class Sampler:
         ``mcmc_options``  extra keys of the MCMC kernels' ``option_dict`` (``pocomc_amd/mcmc.py``), e.g.
                           ``dict(x_order='F')`` (Fortran-ordered ``x`` for the likelihood, pipelined kernel call),
                           ``dict(lanes=2)``;
-        ``device_likelihood``  (needs ``vectorize=True``, no blobs) the likelihood runs on the GPU: it is
+        ``device_likelihood``  (needs ``vectorize=True``, no ``blobs_dtype``) the likelihood runs on the GPU: it is
                           called with an ``(n, D)`` float64 tensor on the flow's device (rows in walker order; a column-major
                           view inside the MCMC steps) on the current torch stream and returns an ``(n,)`` float64 or
                           float32 tensor on that device.  It must be row-wise and free of side effects, and must not keep
                           its input, whose buffer is reused.  In the MCMC steps x' never goes to the host and logl' is
                           never uploaded.  Sharded (one process per GPU): it is called on every rank with that rank's
                           rows only, on that rank's device and current stream; it must be the same function on every
-                          rank.
+                          rank;
+        ``device_blobs``  (needs ``device_likelihood=True``) the likelihood returns ``(logl, blobs)``: ``blobs`` an
+                          ``(n, *blob_shape)`` tensor on the same device, float64 / float32 / int64 / int32 -- derived
+                          quantities of each row.  ``blob_shape`` and the dtype are fixed by the first call; a later call
+                          that disagrees raises.  The blobs stay in HBM through the run (an accepted walker's row moves in
+                          the accept launch, the pool keeps every iteration's block on the device); they come out as numpy
+                          arrays like everything else: ``posterior(return_blobs=True)``, ``results["blobs"]``, checkpoints.
 
         Supported ``train_config`` keys: those of ``sampler.py:287-299`` (``validation_split, epochs, batch_size,
         patience, learning_rate, annealing, gaussian_scale, laplace_scale, noise, shuffle, clip_grad_norm, verbose``),
@@ -205,8 +211,14 @@ class Sampler:
             if not vectorize:
                 raise ValueError("device_likelihood=True needs vectorize=True: the likelihood is called on whole blocks of rows")
             if self.have_blobs:
-                raise ValueError("device_likelihood=True does not support blobs (blobs_dtype)")
-        if vectorize and self.have_blobs:
+                raise ValueError("device_likelihood=True takes no blobs_dtype: blobs of a device likelihood are tensors "
+                                 "it returns next to logl (device_blobs=True)")
+        self.device_blobs = bool(device_blobs)
+        if self.device_blobs and not self.device_likelihood:
+            raise ValueError("device_blobs=True needs device_likelihood=True")
+        self.have_blobs = self.have_blobs or self.device_blobs
+        self._blob_spec = None         # (blob_shape, dtype name) of the device blobs, fixed by the first call
+        if vectorize and self.have_blobs and not self.device_blobs:
             raise ValueError("Cannot vectorize likelihood with blobs.")
         self.pool, self.distribute = pool, map
         if isinstance(pool, int) and pool > 1:
@@ -325,8 +337,11 @@ class Sampler:
         if np.any(bad):
             rows = np.arange(len(x))
             src = np.random.choice(rows[~bad], size=int(bad.sum()), replace=True)
-            for arr in (x, u, logdetj, logp, logl) + ((blobs,) if self.have_blobs else ()):
+            for arr in (x, u, logdetj, logp, logl) + ((blobs,) if self.have_blobs and not self.device_blobs else ()):
                 arr[rows[bad]] = arr[src]
+            if self.device_blobs:
+                to = lambda i: torch.from_numpy(i).to(blobs.device)
+                blobs = blobs.index_copy(0, to(rows[bad]), blobs[to(src)])      # (a new tensor: the likelihood's own stays)
         self.walkers = dict(u=u, x=x, logl=logl, logp=logp, logdetj=logdetj, blobs=blobs, iter=self.t, calls=self.calls,
                             steps=1, efficiency=1.0, ess=self.n_effective, accept=1.0, beta=0.0, logz=0.0)
         self.particles.update(self.walkers)
@@ -432,7 +447,9 @@ class Sampler:
             pick = systematic_resample(self.n_active, weights=w, device_indices=True)
         rows = idx[pick]
         self.walkers.update(self.particles.take(rows))
-        if self.have_blobs:
+        if self.device_blobs:
+            self.walkers["blobs"] = self.particles.blob_rows()[rows]        # (row gather on the device)
+        elif self.have_blobs:
             self.walkers["blobs"] = self.particles.get("blobs", flat=True)[rows.cpu().numpy()]
 
     # ------------------------------------------------------------------------------------------------- mutate
@@ -442,21 +459,27 @@ class Sampler:
         w, n = self.walkers, self.n_active
         sl = self.ranks.share(n)
         state = {k: w[k][sl] for k in ROW_KEYS}
-        state.update(beta=w["beta"], blobs=w["blobs"][sl].copy() if self.have_blobs else None)
+        if self.device_blobs:
+            blobs = torch.as_tensor(w["blobs"], device=self.flow.device)[sl]     # (numpy right after load_state)
+        else:
+            blobs = w["blobs"][sl].copy() if self.have_blobs else None
+        state.update(beta=w["beta"], blobs=blobs)
         funcs = dict(loglike=self._log_like, logprior=self.log_prior, scaler=self.scaler, flow=self.flow,
                      u_geometry=self.u_geometry, theta_geometry=self.theta_geometry)
         opts = dict(n_max=self.n_max_steps, n_steps=self.n_steps, progress_bar=self.pbar,
                     proposal_scale=self.proposal_scale, device_state=True)
         opts.update(self.mcmc_options)
         if self.device_likelihood:
-            funcs["loglike"] = lambda xt: (self.log_likelihood(xt), None)
+            funcs["loglike"] = self.log_likelihood if self.device_blobs else (lambda xt: (self.log_likelihood(xt), None))
             opts["device_likelihood"] = True
         if self.world > 1:
             opts.update(group=self.group, shard_offset=sl.start)
         res = _KERNELS[(bool(self.preconditioned), self.sample)](state, funcs, opts)
         for k in ROW_KEYS:
             w[k] = self.ranks.gather_rows(res[k], n)
-        if self.have_blobs:
+        if self.device_blobs:
+            w["blobs"] = self.ranks.gather_rows(res["blobs"], n)
+        elif self.have_blobs:
             w["blobs"] = self._gather_blobs(res["blobs"], n)
         self.calls = w["calls"] = self.calls + self.ranks.total(int(res["calls"]))
         w.update(efficiency=res["efficiency"] / (2.38 / self.n_dim ** 0.5), steps=res["steps"], accept=res["accept"],
@@ -506,15 +529,30 @@ class Sampler:
         unit_axes = tuple(ax for ax in range(1, blobs.ndim) if blobs.shape[ax] == 1)
         return logl, (np.squeeze(blobs, unit_axes) if unit_axes else blobs)
 
-    def _log_like_all(self, x):
-        """The likelihood of all rows of ``x`` (identical on every rank), each rank evaluating its share."""
+    def _device_blobs(self, out, n):
+        """The blobs in what the device likelihood returned for ``n`` rows, checked against the first call's."""
+        like = None
+        if self._blob_spec is not None:
+            like = torch.empty((0,) + tuple(self._blob_spec[0]), dtype=getattr(torch, self._blob_spec[1]))
+        b = _mcmc.device_blobs(out, n, self.flow.device, like=like)
+        if self._blob_spec is None:
+            self._blob_spec = (tuple(b.shape[1:]), str(b.dtype).split(".")[-1])
+        return b
+
+    def _log_like_all(self, x, want_blobs=True):
+        """The likelihood of all rows of ``x`` (identical on every rank), each rank evaluating its share.  Blobs of a device
+        likelihood come back as a device tensor (``want_blobs=False``: dropped unseen)."""
         if self.device_likelihood:
             # (warm-up and evidence: this rank's share of the rows goes up to its device, the values come back and are
             #  gathered, so that every rank holds the same logl)
             sl = self.ranks.share(len(x))
             xt = torch.from_numpy(np.ascontiguousarray(x[sl], dtype=np.float64)).to(self.flow.device)
-            logl = _mcmc.device_logl(self.log_likelihood(xt), len(xt), self.flow.device)
-            return self.ranks.gather_rows(logl.to(torch.float64).cpu().numpy(), len(x)), None
+            out = self.log_likelihood(xt)
+            logl = _mcmc.device_logl(out, len(xt), self.flow.device)
+            blobs = None
+            if self.device_blobs and want_blobs:
+                blobs = self.ranks.gather_rows(self._device_blobs(out, len(xt)), len(x))
+            return self.ranks.gather_rows(logl.to(torch.float64).cpu().numpy(), len(x)), blobs
         if self.world == 1:
             return self._log_like(x)
         sl = self.ranks.share(len(x))
@@ -541,7 +579,7 @@ class Sampler:
         logp = self.log_prior(x_q)
         ok = np.isfinite(logp)
         x_q, logdetj, logq, logp = x_q[ok], logdetj[ok], logq[ok], logp[ok]
-        logl, _ = self._log_like_all(x_q)
+        logl, _ = self._log_like_all(x_q, want_blobs=False)
         logw = logl + logp + logdetj - logq
         m = len(logw)
         lib, dev = _lib.load(), self.flow.device
@@ -634,7 +672,10 @@ class Sampler:
         self.ranks.barrier()
 
     def load_state(self, path):
-        """``sampler.py:1051-1061``; ranks / group / pools stay those of the loading process."""
+        """``sampler.py:1051-1061``; ranks / group / pools stay those of the loading process.  A state file holds no
+        random streams (numpy's, torch's), and loading one draws from torch's: a resumed run continues from the saved pool,
+        walkers, flow and blobs, but with the streams of the loading process -- it is not the uninterrupted run draw for
+        draw unless the caller puts the streams back."""
         import dill
         with open(path, "rb") as f:
             state = dill.load(file=f)

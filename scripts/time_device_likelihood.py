@@ -2,10 +2,12 @@
 Rosenbrock on the host: 1e4 walkers x 32 dimensions, maf3 flow, prior U(-10, 10)^32, beta = 0.5, preconditioned tpCN.
 
     python scripts/time_device_likelihood.py [--walkers 10000] [--dim 32] [--steps 200] [--repeats 3] [--out FILE]
-                                             [--modes host_numpy,device_torch] [--ranks N]
+                                             [--modes host_numpy,device_torch] [--ranks N] [--blobs B]
 
 The device mode hands the likelihood an (n, D) float64 view of x' on the GPU (option_dict["device_likelihood"]); the
 host mode is the pipelined host call (x_order='F': x' to pinned host memory, logl' read back by the accept kernel).
+``--blobs B`` (device mode only): the likelihood also returns B float64 columns per row as blobs, which stay on the device
+and move with the accepted walkers in the accept launch (``state_dict["blobs"]`` a device tensor).
 Both calls take the same Philox variates; each mode is timed over --repeats calls of --steps steps after one warm-up
 call, and the best and median steps/s are printed as one JSON line.
 
@@ -59,6 +61,7 @@ def main():
     ap.add_argument("--modes", default="host_numpy,device_torch", help="comma-separated subset to time (e.g. one mode "
                     "under a memory-copy trace)")
     ap.add_argument("--ranks", type=int, default=1, help="shard the walkers over this many ranks (--walkers rows each)")
+    ap.add_argument("--blobs", type=int, default=0, help="float64 blob columns the device likelihood returns per row")
     args = ap.parse_args()
     rank, world = 0, 1
     if args.ranks > 1:
@@ -88,10 +91,22 @@ def main():
     geo.fit(flow.forward(torch.from_numpy(u_geo).float())[0].numpy().astype(np.float64))
     logl0 = rosenbrock(np.asfortranarray(x))
 
+    B = args.blobs
+    if B and "host_numpy" in args.modes.split(","):
+        sys.exit("--blobs times the device mode only: add --modes device_torch")
+
+    def blobs_torch(xt):
+        """B derived columns of a row: x_j scaled (j < D), wrapped around beyond."""
+        return torch.stack([xt[:, j % D] * (j + 1.0) for j in range(B)], dim=1)
+
     def call(device):
+        blobs0 = torch.zeros(N, B, dtype=torch.float64, device="cuda") if (B and device) else None
         state = dict(u=u.copy(), x=x.copy(), logdetj=scaler.inverse(u)[1], logl=logl0.copy(), logp=prior.logpdf(x),
-                     beta=0.5, blobs=None)
-        like = (lambda xt: (rosenbrock_torch(xt), None)) if device else (lambda xx: (rosenbrock(xx), None))
+                     beta=0.5, blobs=blobs0)
+        if device:
+            like = (lambda xt: (rosenbrock_torch(xt), blobs_torch(xt))) if B else (lambda xt: (rosenbrock_torch(xt), None))
+        else:
+            like = lambda xx: (rosenbrock(xx), None)
         funcs = dict(loglike=like, logprior=prior.logpdf, scaler=scaler, flow=flow, theta_geometry=geo)
         opts = dict(n_max=args.steps, n_steps=10 ** 9, progress_bar=None, proposal_scale=2.38 / D ** 0.5, seed=3)
         opts.update(dict(device_likelihood=True) if device else dict(x_order="F"))
@@ -105,7 +120,7 @@ def main():
         return res["steps"] / dt, res
 
     out = dict(walkers=N, dim=D, flow="maf3", steps=args.steps, repeats=args.repeats, kind="preconditioned_pcn",
-               gpu=torch.cuda.get_device_name(torch.cuda.current_device()), rank=rank, ranks=world,
+               gpu=torch.cuda.get_device_name(torch.cuda.current_device()), rank=rank, ranks=world, blobs=B,
                c_allreduce=os.environ.get("PMC_C_ALLREDUCE", "1"), mailbox=os.environ.get("PMC_COMM_MAILBOX", ""))
     results = {}
     modes = args.modes.split(",")
