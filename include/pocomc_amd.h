@@ -540,7 +540,16 @@ typedef struct pmc_step {
      * the rows it left out) instead of gathering the other rows first (x'[mask], mcmc.py:117: 280 us for 6.5e3 x 50 doubles).
      * The device copy p_x keeps x'.  Needs h_clean / clean_count and a device prior. */
     int32_t fill_rejected;
-    int32_t fill_pad;
+    /* A prior that is a GPU callable of the caller's, like the likelihood (lik_x non-NULL, prior == NULL, prior_rows = 1;
+     * the word was reserved padding, zero in every caller so far: no offset and no size changes):
+     *   pmc_step_pre writes x' into lik_x as it does with a device prior table, but the only gate it knows is the finite
+     *   mask: a row whose x' (or logdetj') is not finite carries the walker's current x and is counted in clean_count;
+     *   p_fin is written, nothing goes to pinned host memory, no completion word is stored.
+     *   The caller evaluates its prior on lik_x (every row; the values of the rows above are dropped) on the same stream,
+     *   pmc_step_prior_rows moves the values into p_logp and closes the gate of mcmc.py:108-109, then the likelihood runs
+     *   on lik_x as before.  pmc_step_post is unchanged.
+     * 0: a prior the device does not evaluate is called on the host (pmc_step_lik_rows). */
+    int32_t prior_rows;
     /* Likelihood on the device (mcmc.py:99-121 with the user's likelihood a GPU callable): with lik_x non-NULL x' is never
      * copied to the host and logl' never uploaded.
      *   pmc_step_pre writes x' into lik_x, column-major ((n, D) with strides (1, n)), with the walker's current x (cur.x) in
@@ -613,6 +622,13 @@ int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double
  * that do not reach the likelihood (p_fin 0 or logp' not finite, mcmc.py:108-109), the walker's current x; those rows
  * are added to clean_count. */
 int pmc_step_lik_rows(const pmc_step_t* s, void* stream);
+/* Device likelihood with a prior that is a GPU callable (pmc_step_t.prior_rows): behind the caller's prior on lik_x, whose
+ * values are in `logp` (device [n], float64, or float32 with logp_is_f32 != 0: widened here),
+ *   p_logp[r] = logp[r] where p_fin[r], -inf where not (mcmc.py:105-107; a NaN is stored as it came),
+ * and where p_fin[r] holds but logp[r] is not finite (mcmc.py:108-109) row r of lik_x is overwritten with the walker's
+ * current x and added to clean_count, so that pmc_step_post's h_calls = n - clean_count stays "rows that reached the
+ * likelihood".  One launch on `stream`: no copy, no wait. */
+int pmc_step_prior_rows(const pmc_step_t* s, const void* logp, int logp_is_f32, void* stream);
 /* The adaptation of pmc_step_t.adapt_state as a launch of its own, for walker sets whose sums come in parts
  * (row ranges stepped one after the other, mcmc.LanedEngine; ranks, after the all-reduce):
  *   total[j] = parts[0][j] + parts[1][j] + ...   (j < D + 4, n_parts <= 8, added in this order)

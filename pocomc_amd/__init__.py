@@ -6,7 +6,7 @@ gfx950 kernels behind the C ABI of ``include/pocomc_amd.h``.
 """
 from .maf_spec import MAFSpec  # noqa: F401
 
-__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "mcmc", "tools"]
+__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "mcmc", "tools"]
 
 
 def __getattr__(name):
@@ -26,4 +26,7 @@ def __getattr__(name):
     if name == "Prior":
         from .prior import Prior
         return Prior
+    if name == "DevicePrior":
+        from .prior import DevicePrior
+        return DevicePrior
     raise AttributeError(name)

@@ -7,6 +7,7 @@
 //
 // With a likelihood on the device (pmc_step_t.lik_x) x' goes to lik_x instead of the host, the caller's likelihood fills
 // p_logl on the same stream, and the accept gates logl' itself: no copy of x' or logl' in either direction.
+// A prior that is a GPU callable too (pmc_step_t.prior_rows) sits between the two: pmc_step_prior_rows takes its values.
 //
 // Pure sequencing of the single-purpose entry points (same kernels, same stream order); host
 // buffers must be pinned for the copies to be asynchronous.
@@ -76,7 +77,9 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
     double* lp = pr ? s->p_logp : nullptr;
     // device likelihood with a device prior: x' (rejected rows filled) into lik_x, the count into clean_count; nothing goes
     // to the host and no completion word follows (the likelihood is the next operation on the stream)
-    const bool devlik = s->lik_x && pr;
+    // (a prior that is the caller's GPU callable, pmc_step_t.prior_rows: the same hand-over with the finite mask as the only
+    //  gate -- pmc_step_prior_rows closes the prior's behind the callable)
+    const bool devlik = s->lik_x && (pr || s->prior_rows);
     if (devlik && !s->clean_count) return pmc_fail("pmc_step_pre: a device likelihood needs clean_count");
     double* xT = devlik ? s->lik_x : direct ? s->h_x : s->p_xT;
     int32_t* fin2 = (direct && !devlik) ? s->h_fin : nullptr;
@@ -192,6 +195,37 @@ extern "C" int pmc_step_lik_rows(const pmc_step_t* s, void* stream) {
     hipLaunchKernelGGL(lik_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->p_x, s->cur.x, s->p_fin,
                        s->p_logp, s->lik_x, s->clean_count, n, (int)s->D);
     return pmc_check_launch("lik_rows_kernel");
+}
+
+// The values of a prior that is a GPU callable (pmc_step_prior_rows): one thread per walker; logp' into p_logp, and the row
+// of a finite x' whose logp' is not finite back to the walker's current x in the column-major lik_x (coalesced along the
+// walkers).  The rows whose x' is not finite were filled and counted by the pre-step.
+__global__ __launch_bounds__(256) void prior_rows_kernel(const void* __restrict__ logp_in, int is_f32,
+                                                         const double* __restrict__ x_cur, const int32_t* __restrict__ fin,
+                                                         double* __restrict__ logp, double* __restrict__ lik_x,
+                                                         unsigned* __restrict__ bad_count, int64_t n, int D) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    if (!fin[r]) { logp[r] = -INFINITY; return; }                   // mcmc.py:105-107
+    const double v = is_f32 ? (double)static_cast<const float*>(logp_in)[r] : static_cast<const double*>(logp_in)[r];
+    logp[r] = v;                                                    // (a NaN as it came: the accept's gate and NaN -> 0 rule see it)
+    if (isfinite(v)) return;                                        // mcmc.py:108-109
+    const double* src = x_cur + r * D;
+    for (int j = 0; j < D; ++j) lik_x[(size_t)j * n + r] = src[j];
+    atomicAdd(bad_count, 1u);
+}
+
+extern "C" int pmc_step_prior_rows(const pmc_step_t* s, const void* logp, int logp_is_f32, void* stream) {
+    if (!s || !logp || !s->lik_x || !s->clean_count || !s->cur.x || !s->p_fin || !s->p_logp || s->D < 1)
+        return pmc_fail("pmc_step_prior_rows: needs logp, lik_x, clean_count, cur.x, p_fin and p_logp");
+    if (s->prior) return pmc_fail("pmc_step_prior_rows: with a device prior table pmc_step_pre evaluates the prior itself");
+    if (!s->prior_rows) return pmc_fail("pmc_step_prior_rows: pmc_step_pre filled lik_x for a host prior (prior_rows is 0)");
+    if ((uintptr_t)logp & (logp_is_f32 ? 3 : 7)) return pmc_fail("pmc_step_prior_rows: logp is not aligned to its element size");
+    const int64_t n = s->n;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(prior_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logp,
+                       logp_is_f32, s->cur.x, s->p_fin, s->p_logp, s->lik_x, s->clean_count, n, (int)s->D);
+    return pmc_check_launch("prior_rows_kernel");
 }
 
 extern "C" int pmc_propose_inverse(int kind, const float* cur32, const double* mu, const double* inv_cov,

@@ -9,7 +9,8 @@ user's prior / likelihood black boxes on the compacted finite rows
 (``mcmc.py:100-121``) and the scalar adaptation / stopping logic
 (``mcmc.py:152-180``).  With ``option_dict["device_likelihood"]`` the likelihood is a
 GPU callable too: x' stays on the device, and the host reads the sums of each step only; blobs such a likelihood returns
-stay in HBM as well and move with the accepted walkers in the accept launch.
+stay in HBM as well and move with the accepted walkers in the accept launch.  ``option_dict["device_logprior"]`` makes the
+prior a GPU callable of the same kind, for priors that are no product of the scipy factors the device has a table for.
 
 
 ``StepEngine`` is the reusable object (bench.py drives it directly); the four
@@ -146,19 +147,29 @@ def _wait_timeout(value):
     return WAIT_TIMEOUT_CAP_S if (v <= 0.0 or v > WAIT_TIMEOUT_CAP_S) else v
 
 
+def _device_values(out, n, device, who):
+    if not isinstance(out, torch.Tensor):
+        raise ValueError(f"{who}: expected a ({n},) tensor on {device}, got {type(out).__name__}")
+    if tuple(out.shape) != (n,):
+        raise ValueError(f"{who}: expected shape ({n},), got {tuple(out.shape)}")
+    if out.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: expected dtype float64 or float32, got {out.dtype}")
+    _on_device(out, device, who)
+    return out
+
+
 def device_logl(out, n, device):
     """The value of a device likelihood (``option_dict["device_likelihood"]``): an ``(n,)`` float64 tensor on the walkers'
     device, a float32 one widened there.  Anything else raises ValueError naming what was received."""
     if isinstance(out, tuple):
         out = out[0]
-    if not isinstance(out, torch.Tensor):
-        raise ValueError(f"device likelihood: expected a ({n},) tensor on {device}, got {type(out).__name__}")
-    if tuple(out.shape) != (n,):
-        raise ValueError(f"device likelihood: expected shape ({n},), got {tuple(out.shape)}")
-    if out.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"device likelihood: expected dtype float64 or float32, got {out.dtype}")
-    _on_device(out, device, "device likelihood")
-    return out
+    return _device_values(out, n, device, "device likelihood")
+
+
+def device_logp(out, n, device):
+    """The value of a device prior (``option_dict["device_logprior"]``), checked like :func:`device_logl`: an ``(n,)``
+    float64 or float32 tensor on the walkers' device; -inf and NaN are values like any other."""
+    return _device_values(out, n, device, "device prior")
 
 
 def _on_device(t, device, who):
@@ -521,6 +532,8 @@ class StepEngine:
         # blobs of the device likelihood (set_device_blobs): the walkers' and the proposals', (n, *blob_shape) each
         self.blobs = None
         self.p_blobs = None
+        # prior on the device as the caller's GPU callable (set_device_logprior): its values go through pmc_step_prior_rows
+        self.device_logprior = False
         self._sums_part = None   # (exchange_enqueue: this rank's sums as the exchange's single part)
 
     def __del__(self):
@@ -606,6 +619,14 @@ class StepEngine:
         self._step.clean_count = self._clean_count.data_ptr()
         self.device_likelihood = True
         self._pre_cfg = None
+
+    def set_device_logprior(self):
+        """The prior is a GPU callable like the likelihood (:meth:`evaluate_device` calls it on ``p_xl`` first): the pre-step
+        hands x' over with the finite mask as its only gate, nothing goes to the host (``pmc_step_t.prior_rows``).  After
+        :meth:`set_device_likelihood`; not for a prior the device evaluates from its table (:meth:`set_device_prior`)."""
+        assert self.device_likelihood and self.prior_desc is None
+        self._step.prior_rows = 1
+        self.device_logprior = True
 
     def set_device_blobs(self, blobs):
         """The walkers carry blobs of a device likelihood that returns ``(logl, blobs)``: ``blobs`` (a device tensor
@@ -840,12 +861,19 @@ class StepEngine:
         """The likelihood of the step in flight on the device (``pmc_step_t.lik_x``), on the engine's stream: the callable
         gets ``p_xl.t()``, an (n, D) float64 view of x' (rows in walker order, column-major), and returns (logl', None), or
         (logl', blobs') where the walkers carry blobs (:meth:`set_device_blobs`); logl' goes into ``p_logl``, blobs' into
-        ``p_blobs``.  A prior the device does not evaluate runs on the host first, on x' and the finite mask
-        (``mcmc.py:105-107``), and ``pmc_step_lik_rows`` uploads its logp' and writes the likelihood's input.  Nothing is
-        waited for otherwise.  Returns the rows handed to the likelihood; the rows that reached it come with the sums
-        (:meth:`calls_reached`)."""
+        ``p_blobs``.  A prior that is a GPU callable too (:meth:`set_device_logprior`) is called first, the same way, on every
+        row -- the rows whose x' is not finite hold the walker's current x -- and ``pmc_step_prior_rows`` takes its (n,)
+        float64 / float32 values: logp' into ``p_logp``, the rows it rules out back to the current x.  Any other prior the
+        device does not evaluate runs on the host first, on x' and the finite mask (``mcmc.py:105-107``), and
+        ``pmc_step_lik_rows`` uploads its logp' and writes the likelihood's input.  Nothing is waited for otherwise.  Returns
+        the rows handed to the likelihood; the rows that reached it come with the sums (:meth:`calls_reached`)."""
         stream = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
-        if self.prior_desc is None:
+        if self.prior_desc is None and self.device_logprior:
+            with torch.cuda.stream(stream):
+                lp = device_logp(log_prior(self.p_xl.t()), self.n, self.device).contiguous()
+                _lib.check(self.lib.pmc_step_prior_rows(C.byref(self._step), lp.data_ptr(), int(lp.dtype == torch.float32),
+                                                        self._stream), "pmc_step_prior_rows")
+        elif self.prior_desc is None:
             self._wait_pre_step()
             fin = self._np_fin.astype(bool)
             if fin.all():
@@ -1326,7 +1354,8 @@ def _counted(fn, rows):
     return call
 
 
-def _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior, whole_set, device_like):
+def _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior, whole_set, device_like,
+                 device_logprior=False):
     """The engine of one kernel call, configured from ``option_dict``; ``whole_set``: blobs / traces / replayed variates
     need the bookkeeping of the whole set (one lane, no pipeline).  Returns ``(engine, pipelined)``."""
     x_order = "F" if device_like else option_dict.get("x_order", "C")
@@ -1361,6 +1390,8 @@ def _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_pr
         eng.set_device_prior(owner)                 # Prior.logpdf on the device when the Prior gives a descriptor
     if device_like:
         eng.set_device_likelihood()
+        if device_logprior and eng.prior_desc is None:      # (a Prior with a device descriptor keeps precedence)
+            eng.set_device_logprior()
     return eng, want_pipe and eng.can_pipeline()
 
 
@@ -1466,8 +1497,14 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
                              f"returns next to logl, got {type(blobs).__name__}")
         if replay is not None or trace is not None:
             raise ValueError("device_likelihood: replayed variates and traces need the host likelihood")
+    # ... and so is the prior: function_dict["logprior"] gets the likelihood's tensor and returns an (n,) tensor
+    device_logprior = bool(option_dict.get("device_logprior", False))
+    if device_logprior and not device_like:
+        raise ValueError("device_logprior: a prior on the device needs device_likelihood=True (with a host likelihood x' "
+                         "goes to the host anyway)")
     eng, pipelined = _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior,
-                                  whole_set=have_blobs or trace is not None or replay is not None, device_like=device_like)
+                                  whole_set=have_blobs or trace is not None or replay is not None, device_like=device_like,
+                                  device_logprior=device_logprior)
     laned = isinstance(eng, LanedEngine)
     lanes = eng.lanes if laned else [eng]
     eng.load_state(u, x, logdetj, logl, logp)

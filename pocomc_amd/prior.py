@@ -6,7 +6,10 @@ expression instead of one scipy call per dimension (same values).
 The MCMC step can evaluate it on the device instead (``device_descriptor``, ``include/pocomc_amd.h`` pmc_prior_t):
 ``device="auto"`` does so for products of uniform / normal factors (the device's values are scipy's bit for bit),
 ``device=True`` for every family in ``DEVICE_FAMILIES`` (scipy's values to ~1e-12 relative, the same support),
-``device=False`` never."""
+``device=False`` never.
+
+``DevicePrior`` is the other kind of prior: any joint density, written once as a GPU function (``logpdf_device``), that the
+MCMC step calls on the device like a device likelihood (``Sampler(device_likelihood=True, device_prior=True)``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -185,3 +188,67 @@ class Prior:
     @property
     def dim(self):
         return len(self.dists)
+
+
+class DevicePrior:
+    """A prior in pocoMC's own protocol (``logpdf / rvs / bounds / dim``, the class its documentation asks for where a
+    prior is no product of independent factors: an ordering constraint, a hierarchical prior, a simplex) around ONE
+    function that lives on the GPU.
+
+    ``logpdf_device(x)``  gets an ``(n, D)`` float64 tensor on the device (rows in walker order; inside the MCMC steps a
+                          column-major view, on the step's stream) and returns an ``(n,)`` float64 or float32 tensor on that
+                          device: the log density of every row, -inf outside the support.  Row-wise, free of side effects,
+                          and it does not keep its input, whose buffer is reused.
+    ``bounds``            ``(D, 2)`` floats, the box the support lies in (+-inf or NaN: unbounded on that side);
+    ``rvs(size)``         draws ``(size, D)`` numpy rows from the prior (host: used once, before the first iteration);
+    ``dim``               D, checked against ``bounds`` when given.
+
+    ``logpdf(x)`` (numpy in, numpy out) uploads, calls ``logpdf_device`` and downloads: one source of truth, usable wherever
+    a prior is.  There is no ``device_descriptor``: the device has no table for it, it calls the function."""
+
+    def __init__(self, logpdf_device, bounds, rvs, dim=None):
+        if not callable(logpdf_device):
+            raise ValueError(f"DevicePrior: logpdf_device must be callable, got {type(logpdf_device).__name__}")
+        if not callable(rvs):
+            raise ValueError(f"DevicePrior: rvs must be callable, got {type(rvs).__name__}")
+        try:
+            b = np.array(bounds, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("DevicePrior: bounds must be a (D, 2) array of floats") from None
+        if b.ndim != 2 or b.shape[1] != 2 or b.shape[0] < 1:
+            raise ValueError(f"DevicePrior: bounds must have shape (D, 2), got {b.shape}")
+        lo = np.where(np.isnan(b[:, 0]), -np.inf, b[:, 0])
+        hi = np.where(np.isnan(b[:, 1]), np.inf, b[:, 1])
+        if not np.all(lo < hi):
+            j = int(np.argmin(lo < hi))
+            raise ValueError(f"DevicePrior: bounds of dimension {j}: lower {b[j, 0]} is not below upper {b[j, 1]}")
+        if dim is not None and (int(dim) != dim or int(dim) != len(b)):
+            raise ValueError(f"DevicePrior: dim = {dim!r} but bounds has {len(b)} rows")
+        self.logpdf_device = logpdf_device
+        self._bounds = b
+        self._rvs = rvs
+
+    def logpdf(self, x):
+        import torch
+        from . import _lib
+        from .mcmc import device_logp
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"DevicePrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
+        dev = _lib.require_gpu()
+        out = device_logp(self.logpdf_device(torch.from_numpy(x).to(dev)), len(x), dev)
+        return out.to(torch.float64).cpu().numpy()
+
+    def rvs(self, size=1):
+        x = np.asarray(self._rvs(size), dtype=np.float64)
+        if x.shape != (size, self.dim):
+            raise ValueError(f"DevicePrior.rvs: expected shape ({size}, {self.dim}) from rvs, got {x.shape}")
+        return x
+
+    @property
+    def bounds(self):
+        return self._bounds.copy()
+
+    @property
+    def dim(self):
+        return len(self._bounds)

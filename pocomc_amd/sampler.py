@@ -145,7 +145,7 @@ class Sampler:
                  train_frequency=None, precondition=True, dynamic=True, metric="ess", n_prior=None,
                  sample="tpcn", n_steps=None, n_max_steps=None, resample="mult", output_dir=None,
                  output_label=None, random_state=None, n_ess=None, group=None, mcmc_options=None,
-                 device_likelihood=False, device_blobs=False):
+                 device_likelihood=False, device_blobs=False, device_prior=False):
         """Arguments and defaults of ``pocomc/sampler.py:154-185``, plus
 
         ``group``         a ``torch.distributed`` process group (default: the initialised default group): one process
@@ -168,6 +168,13 @@ class Sampler:
                           that disagrees raises.  The blobs stay in HBM through the run (an accepted walker's row moves in
                           the accept launch, the pool keeps every iteration's block on the device); they come out as numpy
                           arrays like everything else: ``posterior(return_blobs=True)``, ``results["blobs"]``, checkpoints.
+        ``device_prior``  (needs ``device_likelihood=True``) the prior is evaluated on the GPU by a function of the user's:
+                          ``prior.logpdf_device`` (``prior.DevicePrior``, or any prior object with that method) under the
+                          device likelihood's contract -- an ``(n, D)`` float64 tensor in, an ``(n,)`` float64 or float32
+                          tensor out, row-wise, no side effects, the input not kept.  For priors that are no product of
+                          scipy factors (``Prior(dists)``, which the device evaluates from a table by itself).  The MCMC
+                          steps then never hand x' to the host; warm-up and evidence call the same function on uploaded
+                          rows.  Sharded: called on every rank with that rank's rows, the same function on every rank.
 
         Supported ``train_config`` keys: those of ``sampler.py:287-299`` (``validation_split, epochs, batch_size,
         patience, learning_rate, annealing, gaussian_scale, laplace_scale, noise, shuffle, clip_grad_norm, verbose``),
@@ -217,6 +224,12 @@ class Sampler:
         if self.device_blobs and not self.device_likelihood:
             raise ValueError("device_blobs=True needs device_likelihood=True")
         self.have_blobs = self.have_blobs or self.device_blobs
+        self.device_prior = bool(device_prior)
+        if self.device_prior and not self.device_likelihood:
+            raise ValueError("device_prior=True needs device_likelihood=True: with a host likelihood x' goes to the host anyway")
+        if self.device_prior and not callable(getattr(prior, "logpdf_device", None)):
+            raise ValueError(f"device_prior=True needs a prior with a logpdf_device method (pocomc_amd.DevicePrior), "
+                             f"got {type(prior).__name__}")
         self._blob_spec = None         # (blob_shape, dtype name) of the device blobs, fixed by the first call
         if vectorize and self.have_blobs and not self.device_blobs:
             raise ValueError("Cannot vectorize likelihood with blobs.")
@@ -330,7 +343,7 @@ class Sampler:
         likelihood are replaced by copies of finite ones (``:456-468``)."""
         u = self.scaler.forward(x)
         logdetj = self.scaler.inverse(u)[1]
-        logp = self.log_prior(x)
+        logp = self._log_prior_all(x)
         logl, blobs = self._log_like_all(x)
         self.calls += self.n_active
         bad = np.isinf(logl)
@@ -472,6 +485,9 @@ class Sampler:
         if self.device_likelihood:
             funcs["loglike"] = self.log_likelihood if self.device_blobs else (lambda xt: (self.log_likelihood(xt), None))
             opts["device_likelihood"] = True
+        if self.device_prior:
+            funcs["logprior"] = self.prior.logpdf_device
+            opts["device_logprior"] = True
         if self.world > 1:
             opts.update(group=self.group, shard_offset=sl.start)
         res = _KERNELS[(bool(self.preconditioned), self.sample)](state, funcs, opts)
@@ -560,6 +576,16 @@ class Sampler:
         logl = self.ranks.gather_rows(np.asarray(logl, dtype=np.float64), len(x))
         return logl, (None if blobs is None else self._gather_blobs(blobs, len(x)))
 
+    def _log_prior_all(self, x):
+        """The prior of all rows of ``x`` (identical on every rank).  ``device_prior``: through ``prior.logpdf_device``, each
+        rank uploading and evaluating its share, the values gathered -- as :meth:`_log_like_all` does for the likelihood."""
+        if not self.device_prior:
+            return self.log_prior(x)
+        sl = self.ranks.share(len(x))
+        xt = torch.from_numpy(np.ascontiguousarray(x[sl], dtype=np.float64)).to(self.flow.device)
+        logp = _mcmc.device_logp(self.prior.logpdf_device(xt), len(xt), self.flow.device)
+        return self.ranks.gather_rows(logp.to(torch.float64).cpu().numpy(), len(x))
+
     # ----------------------------------------------------------------------------------------------- evidence
     def evidence(self):
         return self.logz, self.logz_err
@@ -576,7 +602,7 @@ class Sampler:
             theta_q, logq = self.flow.sample(n)
         x_q, logdetj = self.scaler.inverse(theta_q.cpu().numpy().astype(np.float64))
         logq = logq.cpu().numpy().astype(np.float64)
-        logp = self.log_prior(x_q)
+        logp = self._log_prior_all(x_q)
         ok = np.isfinite(logp)
         x_q, logdetj, logq, logp = x_q[ok], logdetj[ok], logq[ok], logp[ok]
         logl, _ = self._log_like_all(x_q, want_blobs=False)

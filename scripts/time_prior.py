@@ -9,7 +9,17 @@ device's two-family path, bench.py's prior) is the reference row.
 Modes: {host prior, device prior, uniform reference} x {bench.py's numpy Rosenbrock on the host (pipelined host call,
 x_order='F'), the torch Rosenbrock on the device (device_likelihood=True)}.  Each mode takes one warm-up call, then the
 modes are timed in turn, --repeats rounds; the best and median steps/s per mode and the host cost of one Prior.logpdf
-call on the 1e4 x 32 block are printed as one JSON line."""
+call on the 1e4 x 32 block are printed as one JSON line.
+
+    python scripts/time_prior.py --callable [--only MODE] [...]
+
+The leg of a prior that no Prior(dists) states: uniform on the box (-10, 10)^32 cut by the joint constraint x0 < x1 + 5
+(the Rosenbrock's mass lies inside), torch Rosenbrock on the device throughout, the same prior three ways --
+``callable_host``: a numpy function the step calls on the host (x' and the finite mask cross PCIe, logp' comes back),
+``callable_device``: the same function in torch through ``device_logprior`` (nothing crosses), ``uniform_table``: the
+uniform(-10, 20)^32 ``Prior(dists)`` from the device's table, without the cut, as the baseline.  ``--only MODE`` runs one
+mode (one warm-up call, then --repeats timed calls): the run to put under ``rocprofv3 --memory-copy-trace``, whose copies
+per step are the difference of two runs with different --steps divided by the difference in steps."""
 import argparse
 import json
 import os
@@ -40,6 +50,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--callable", action="store_true", help="time a joint prior as host function, GPU callable and table baseline")
+    ap.add_argument("--only", default=None, help="with --callable: run this mode alone")
     args = ap.parse_args()
     from scipy.stats import uniform
     import pocomc_amd as pc
@@ -83,6 +95,9 @@ def main():
         assert res["steps"] == args.steps
         return res["steps"] / dt, res
 
+    if args.callable:
+        return callable_leg(args, pmcmc, setups["uniform"], x, logl0, rosenbrock_torch)
+
     modes = [(f"{p}_prior__{lk}", p, lk == "device_torch") for lk in ("host_numpy", "device_torch")
              for p in ("host", "device", "uniform")]
     out = dict(walkers=N, dim=D, flow="maf3", steps=args.steps, repeats=args.repeats, kind="preconditioned_pcn",
@@ -111,6 +126,72 @@ def main():
         priors["host"].logpdf(x)
         t.append(time.perf_counter() - t0)
     out["host_prior_logpdf_ms_median"] = 1e3 * float(np.median(t))
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+CUT = 5.0
+
+
+def joint_numpy(x):
+    """log density (up to the constant both forms share) of the uniform box cut by x0 < x1 + CUT."""
+    ok = np.ones(x.shape[0], dtype=bool)
+    for j in range(x.shape[1]):
+        ok = ok & (x[:, j] >= -10.0) & (x[:, j] <= 10.0)
+    ok = ok & (x[:, 0] < x[:, 1] + CUT)
+    return np.where(ok, 0.0, -np.inf)
+
+
+def joint_torch(x):
+    ok = torch.ones(x.shape[0], dtype=torch.bool, device=x.device)
+    for j in range(x.shape[1]):
+        ok = ok & (x[:, j] >= -10.0) & (x[:, j] <= 10.0)
+    ok = ok & (x[:, 0] < x[:, 1] + CUT)
+    zero = torch.zeros(x.shape[0], dtype=torch.float64, device=x.device)
+    return torch.where(ok, zero, torch.full_like(zero, float("-inf")))
+
+
+def callable_leg(args, pmcmc, setup, x, logl0, rosenbrock_torch):
+    table, scaler, flow, geo, u = setup
+    D = x.shape[1]
+    like = lambda xt: (rosenbrock_torch(xt), None)
+    modes = dict(callable_host=(joint_numpy, {}), callable_device=(joint_torch, dict(device_logprior=True)),
+                 uniform_table=(table.logpdf, {}))
+    if args.only:
+        modes = {args.only: modes[args.only]}
+
+    def call(name):
+        logprior, extra = modes[name]
+        logp0 = table.logpdf(x) if name == "uniform_table" else joint_numpy(x)
+        state = dict(u=u.copy(), x=x.copy(), logdetj=scaler.inverse(u)[1], logl=logl0.copy(), logp=logp0, beta=0.5, blobs=None)
+        funcs = dict(loglike=like, logprior=logprior, scaler=scaler, flow=flow, theta_geometry=geo)
+        opts = dict(n_max=args.steps, n_steps=10 ** 9, progress_bar=None, proposal_scale=2.38 / D ** 0.5, seed=3,
+                    device_likelihood=True, **extra)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = pmcmc.preconditioned_pcn(state, funcs, opts)
+        dt = time.perf_counter() - t0
+        assert res["steps"] == args.steps
+        return res["steps"] / dt, res
+    out = dict(leg="callable", walkers=len(x), dim=D, flow="maf3", steps=args.steps, repeats=args.repeats,
+               kind="preconditioned_pcn", gpu=torch.cuda.get_device_name(0))
+    last = {name: call(name)[1] for name in modes}                  # warm-up
+    rates = {name: [] for name in modes}
+    for _ in range(args.repeats):                                   # the modes alternate
+        for name in modes:
+            r, last[name] = call(name)
+            rates[name].append(r)
+    for name, rs in rates.items():
+        out[name] = dict(steps_per_s_best=max(rs), steps_per_s_median=float(np.median(rs)),
+                         us_per_step_median=1e6 / float(np.median(rs)), all=rs, accept=float(last[name]["accept"]),
+                         calls=int(last[name]["calls"]))
+    if "callable_host" in last and "callable_device" in last:       # the two forms of the prior walk the same chain
+        out["callable_device_equals_host"] = bool(all(np.array_equal(last["callable_host"][k], last["callable_device"][k])
+                                                      for k in ("x", "logl", "logp")))
+        out["device_over_host_callable"] = out["callable_device"]["steps_per_s_median"] / out["callable_host"]["steps_per_s_median"]
     line = json.dumps(out)
     print(line)
     if args.out:
