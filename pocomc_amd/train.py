@@ -12,11 +12,14 @@ from __future__ import annotations
 
 import ctypes as C
 import time
+from functools import partial
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _lib
+from .mcmc import _pinned_give, _pinned_take
 
 
 MAX_SETS = 256              # row sets of 16 per loss/gradient launch (one workgroup each; larger batches come in chunks)
@@ -170,6 +173,13 @@ def _wide_state(flow):
     return flow._wide
 
 
+def _loss_grad_call(flow, ts, ws, xb, wb, idx, loss_ptr, n, stream):
+    """The loss / gradient launch of the flow's engine (``ws``: its bf16 state, None = float32) inside the caller's device context."""
+    what = "pmc_maf_loss_grad" if ws is None else "pmc_maf_loss_grad_bf16"
+    _lib.check(getattr(flow.lib, what)(C.byref(flow._desc), C.byref((ws or ts).desc), _lib.ptr(xb), _lib.ptr(wb), _lib.ptr(idx),
+                                       1000.0, _lib.ptr(ts.grad), loss_ptr, n, stream), what)
+
+
 def loss_and_grad(flow, xb, wb=None, idx=None, refresh=True):
     """Loss of one batch (device scalar tensor) and its gradient (in ``flow._train.grad``).
     ``idx`` (int64, device) selects the batch rows out of ``xb`` / ``wb``.  (``refresh=False``: the caller keeps the
@@ -178,23 +188,12 @@ def loss_and_grad(flow, xb, wb=None, idx=None, refresh=True):
     n = xb.shape[0] if idx is None else idx.numel()
     ts.scal.zero_()
     ws = _wide_state(flow)
-    if ws is not None:
-        if refresh:
-            ws.refresh(flow)
-        with torch.cuda.device(flow.device):
-            _lib.check(flow.lib.pmc_maf_loss_grad_bf16(C.byref(flow._desc), C.byref(ws.desc), _lib.ptr(xb),
-                                                       _lib.ptr(wb) if wb is not None else None,
-                                                       _lib.ptr(idx) if idx is not None else None,
-                                                       1000.0, _lib.ptr(ts.grad), _lib.ptr(ts.scal), n,
-                                                       _lib.stream_handle()), "pmc_maf_loss_grad_bf16")
-        return ts.scal[0]
-    ts.ensure_sets(n)
+    if ws is None:
+        ts.ensure_sets(n)
+    elif refresh:
+        ws.refresh(flow)
     with torch.cuda.device(flow.device):
-        _lib.check(flow.lib.pmc_maf_loss_grad(C.byref(flow._desc), C.byref(ts.desc), _lib.ptr(xb),
-                                              _lib.ptr(wb) if wb is not None else None,
-                                              _lib.ptr(idx) if idx is not None else None,
-                                              1000.0, _lib.ptr(ts.grad), _lib.ptr(ts.scal), n, _lib.stream_handle()),
-                   "pmc_maf_loss_grad")
+        _loss_grad_call(flow, ts, ws, xb, wb, idx, _lib.ptr(ts.scal), n, _lib.stream_handle())
     return ts.scal[0]
 
 
@@ -214,7 +213,6 @@ def batch_loss(flow, xb, wb=None, group=None, sharded=False):
         if wb is not None:
             _lib.check(lib.pmc_sum_f32(_lib.ptr(wb), C.c_void_p(ts.scal.data_ptr() + 4), n, st), "pmc_sum_f32")
             if sharded:
-                import torch.distributed as dist
                 dist.all_reduce(ts.scal[1:2], group=group)
         _lib.check(lib.pmc_neg_weighted_sum(_lib.ptr(lp), _lib.ptr(wb) if wb is not None else None,
                                             C.c_void_p(ts.scal.data_ptr() + 4) if wb is not None else None,
@@ -267,9 +265,7 @@ class AdamW:
                                  max_norm=float(max_norm) if max_norm is not None else 0.0, step=self.t)
             with torch.cuda.device(f.device):
                 _lib.check(f.lib.pmc_maf_train_epoch_bf16(C.byref(f._desc), C.byref(ws.desc), C.byref(c), _lib.ptr(x),
-                                                          _lib.ptr(w) if w is not None else None,
-                                                          _lib.ptr(perm) if perm is not None else None,
-                                                          x.shape[0], int(batch_size), _lib.ptr(loss_acc),
+                                                          _lib.ptr(w), _lib.ptr(perm), x.shape[0], int(batch_size), _lib.ptr(loss_acc),
                                                           _lib.ptr(ws.sq), _lib.stream_handle()),
                            "pmc_maf_train_epoch_bf16")
             self.t = int(c.step)
@@ -328,13 +324,6 @@ class ReduceLROnPlateau:
             self.bad = 0
 
 
-def _dist_world(group):
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size(group)
-    return 1
-
-
 def _weight_flags(flow):
     """uint8 [n_params]: 1 for the entries of the hyper-networks' weight matrices (what ``parameter_name.endswith('weight')``
     selects at ``flow.py:409-411`` -- masked-out entries included), 0 for biases."""
@@ -350,26 +339,48 @@ def _weight_flags(flow):
     return ts.weight_flags
 
 
-def sharded_epoch(flow, opt, x, w, perm, batch_size, max_norm, loss_acc, group, penalty=None):
-    """One epoch of data-parallel training: every rank holds a shard of the
-    training rows; a global batch of ``batch_size`` rows is ``batch_size / world`` local rows per rank.
-    Per batch: [all-reduce of the weight sum] -> local loss/gradient -> ONE all-reduce of
-    (gradient, loss) -> the same clip + AdamW step on every rank (the clip needs the norm of the
-    reduced gradient, flow.py:318)."""
-    import torch.distributed as dist
+def _batch_at(x, w, perm, b0, nb):
+    """``(idx, xb, wb)`` of a pass's batch at ``b0``: entries of the permutation (the kernels gather), or slices."""
+    if perm is not None:
+        return perm[b0:b0 + nb], x, w
+    return None, x[b0:b0 + nb], None if w is None else w[b0:b0 + nb]
+
+
+def _add_penalty(flow, penalty, grad, loss, mult=1.0):
+    """flow.py:304-307, :314-315: ``mult`` times the weight penalty onto ``loss``, its gradient onto ``grad`` (or None)."""
+    b, g, flags = penalty
+    with torch.cuda.device(flow.device):
+        _lib.check(flow.lib.pmc_weight_penalty(_lib.ptr(flow.params), _lib.ptr(flags), _lib.ptr(grad), flow.params.numel(),
+                                               b, g, float(mult), _lib.ptr(loss), _lib.ptr(flow._train.sq_partial),
+                                               _lib.stream_handle()), "pmc_weight_penalty")
+
+
+def _train_penalised(flow, opt, x, w, perm, batch_size, max_norm, loss_acc, penalty):
+    """Batch by batch (flow.py:301-321) with the penalty's gradient added before the clip (flow.py:314-318)."""
+    n, bs = x.shape[0], int(batch_size)
+    for b0 in range(0, n, bs):
+        idx, xb, wb = _batch_at(x, w, perm, b0, min(bs, n - b0))
+        loss_acc += loss_and_grad(flow, xb, wb, idx, refresh=False)
+        penalty(flow._train.grad, loss_acc)
+        opt.step(max_norm)
+
+
+def _train_sharded(flow, opt, x, w, perm, batch_size, max_norm, loss_acc, group, penalty=None):
+    """One epoch of data-parallel training: every rank holds a shard of the training rows; a global
+    batch of ``batch_size`` rows is ``batch_size / world`` local rows per rank.  Per batch: [all-reduce of the weight sum] ->
+    local loss/gradient -> ONE all-reduce of (gradient, loss) -> the same clip + AdamW step on every rank (the clip needs the
+    norm of the reduced gradient, flow.py:318)."""
     ts = _train_state(flow)
-    world = dist.get_world_size(group)
-    lb = max(1, int(batch_size) // world)
+    lb = max(1, int(batch_size) // dist.get_world_size(group))
     n = x.shape[0]
     wide = _wide_state(flow)
     if wide is None:
         ts.ensure_sets(lb)
     st = _lib.stream_handle()
+    loss_ptr = C.c_void_p(ts.grad_ext.data_ptr() + 4 * ts.grad.numel())     # (the element behind the gradient)
     for b0 in range(0, n, lb):
         nb = min(lb, n - b0)
-        idx = perm[b0:b0 + nb] if perm is not None else None
-        xb = x if idx is not None else x[b0:b0 + nb]
-        wb = None if w is None else (w if idx is not None else w[b0:b0 + nb])
+        idx, xb, wb = _batch_at(x, w, perm, b0, nb)
         with torch.cuda.device(flow.device):
             if w is not None:
                 ts.wsum.zero_()
@@ -378,19 +389,7 @@ def sharded_epoch(flow, opt, x, w, perm, batch_size, max_norm, loss_acc, group, 
                 dist.all_reduce(ts.wsum, group=group)
                 (wide or ts).desc.wsum = ts.wsum.data_ptr()
             ts.grad_ext[-1:].zero_()
-            if wide is not None:
-                _lib.check(flow.lib.pmc_maf_loss_grad_bf16(C.byref(flow._desc), C.byref(wide.desc), _lib.ptr(xb),
-                                                           _lib.ptr(wb) if wb is not None else None,
-                                                           _lib.ptr(idx) if idx is not None else None, 1000.0,
-                                                           _lib.ptr(ts.grad),
-                                                           C.c_void_p(ts.grad_ext.data_ptr() + 4 * ts.grad.numel()),
-                                                           nb, st), "pmc_maf_loss_grad_bf16")
-            else:
-                _lib.check(flow.lib.pmc_maf_loss_grad(C.byref(flow._desc), C.byref(ts.desc), _lib.ptr(xb),
-                                                      _lib.ptr(wb) if wb is not None else None,
-                                                      _lib.ptr(idx) if idx is not None else None, 1000.0,
-                                                      _lib.ptr(ts.grad), C.c_void_p(ts.grad_ext.data_ptr() + 4 * ts.grad.numel()),
-                                                      nb, st), "pmc_maf_loss_grad")
+            _loss_grad_call(flow, ts, wide, xb, wb, idx, loss_ptr, nb, st)
             (wide or ts).desc.wsum = None
         dist.all_reduce(ts.grad_ext, group=group)
         loss_acc += ts.grad_ext[-1:]
@@ -399,285 +398,241 @@ def sharded_epoch(flow, opt, x, w, perm, batch_size, max_norm, loss_acc, group, 
         opt.step(max_norm)
 
 
-def _batches(n, batch_size, shuffle):
-    """``DataLoader(TensorDataset(...), batch_size, shuffle)``: a fresh permutation per epoch,
-    last partial batch kept."""
-    idx = torch.randperm(n) if shuffle else torch.arange(n)
-    return [idx[i:i + batch_size] for i in range(0, n, batch_size)]
+sharded_epoch = _train_sharded
 
 
-def fit_flow(flow, x, weights=None, validation_split=0.0, epochs=1000, batch_size=1000, patience=20,
-             learning_rate=1e-3, weight_decay=0, laplace_scale=None, gaussian_scale=None, annealing=True,
-             noise=None, shuffle=True, clip_grad_norm=1.0, verbose=0, group=None, sharded=None):
-    """``sharded`` (default: a ``torch.distributed`` group with more than one rank exists): ``x`` /
-    ``weights`` are THIS rank's shard of the training rows (equal shard sizes), ``batch_size`` is the
-    global batch; gradients and losses are all-reduced (RCCL on the GPUs) so that every rank takes
-    the same optimizer steps and the same early-stopping decisions."""
+def _valid_epoch_call(flow, slots, w, batch_size, stream, sl, x):
+    """The whole pass in one library call on ``stream`` (batches of the reference's DataLoader, flow.py:327-348)."""
+    perm = None
+    if slots.shuffle:                               # (fused staging: uploaded with the training pass's permutation)
+        perm = slots.upload(1, sl) if not slots.fused else slots.d_perm[1][sl] if slots.n_valid else None
+    with torch.cuda.device(flow.device):
+        _lib.check(flow.lib.pmc_maf_valid_epoch(C.byref(flow._desc), _lib.ptr(x), _lib.ptr(w), _lib.ptr(perm), slots.n_valid,
+                                                int(batch_size), _lib.ptr(flow._train.logp_scratch),
+                                                _lib.ptr(slots.acc_valid[sl]), stream), "pmc_maf_valid_epoch")
+
+
+def _valid_sharded(flow, slots, w, local_batch, shuffle, group, sl, x):
+    """Batch by batch on this rank's shard of the validation rows, as ``DataLoader(TensorDataset(...), batch_size, shuffle)``
+    hands them out: a fresh permutation per epoch, last partial batch kept (the ranks' sum follows in ``_enqueue``)."""
+    order = torch.randperm(slots.n_valid) if shuffle else torch.arange(slots.n_valid)
+    for b0 in range(0, slots.n_valid, local_batch):
+        idx = order[b0:b0 + local_batch].to(flow.device)
+        slots.acc_valid[sl] += batch_loss(flow, x[idx].contiguous(), None if w is None else w[idx].contiguous(), group, True)
+
+
+class _FitPlan:
+    """Every decision of one fit, taken once: the functions its epochs call follow from these fields alone.
+    ``train_mode``: "epoch_call" (``AdamW.epoch``), "penalised" (``_train_penalised``), "sharded" (``_train_sharded``);
+    ``valid_mode``: None, "call" / "call_side" (``_valid_epoch_call`` on the main / side stream), "sharded" (``_valid_sharded``)."""
+
+    def __init__(self, flow, x_valid, batch_size, shuffle, penalised, annealing, group, sharded):
+        self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+        self.sharded = bool(self.world > 1 if sharded is None else sharded)
+        self.validation, self.n_valid = validation, n_valid = x_valid is not None, 0 if x_valid is None else x_valid.shape[0]
+        self.engine = "bf16" if _wide_state(flow) is not None else "f32"
+        self.train_mode = "sharded" if self.sharded else "penalised" if penalised else "epoch_call"
+        # Float32 engine, one process, no penalty term (the other paths enqueue batch by batch from Python):
+        plain = self.engine == "f32" and not self.sharded and not penalised
+        # Plain shuffled fits: ONE host-to-device copy per epoch carries both
+        # permutations AND the zeros of the two loss accumulators (two int64 words in front of the permutations in one staging
+        # buffer), and the parameters behind the epoch's last step are written by that step itself (pmc_adamw_t.snapshot) --
+        # three ~5 us launches fewer per epoch, of the ~75-120 us an epoch of the Sampler's fits takes.
+        self.fused_staging = plain and bool(shuffle)
+        # The validation pass of epoch e only READS the parameters, and so do the loss / gradient launches of epoch e + 1's
+        # first batch; a batch's chain kernel occupies 32 of 256 compute units.  So the pass runs on a second stream, next to
+        # that batch, and only the first optimizer step of epoch e + 1 waits for it (pmc_maf_train_epoch_gated): plain fits.
+        # It pays where the pass (two cross-stream hand-overs of ~16 us, the forward launch, the reduction, the copies: ~65 us
+        # at the Sampler's sizes) is SHORTER than the first batch's chain + weight-gradient launches it hides behind, and costs
+        # the host ~15 us per epoch: deep or spline flows (chain >= ~80 us) with a validation set of at most two batches' worth
+        # of rows -- the Sampler's regime (README example, nsf6: 152 -> 123 us per epoch).  Measured otherwise: maf3 at D = 10
+        # 76 -> 91 us (the epoch is bound by its ~120 us of enqueue, not by the device), the bench's fit (maf3 at D = 32, ten
+        # batches, 5000 validation rows whose 313 workgroups crowd the chain's 32) 0.95 -> 1.05 ms.
+        long_chain = flow.spec.n_transforms * (2 if flow.spec.univariate == "rqs" else 1) >= 6
+        side = plain and long_chain and n_valid <= 2 * int(batch_size)
+        self.valid_mode = None if not validation else "sharded" if self.sharded else "call_side" if side else "call"
+        # One epoch may be IN FLIGHT while the host looks at the previous epoch's losses (no scheduler, one GPU): the
+        # early-stop test needs every epoch's loss on the host, and waiting for it before enqueuing the next epoch
+        # leaves the GPU idle for the whole host turn-around (most of an epoch when the training set is one or two
+        # batches, the Sampler's usual case).  The speculative epoch changes nothing observable: on an early stop the
+        # best parameters are restored (flow.py:369-374), and no epoch is enqueued past `epochs`.
+        self.pipelined = not annealing and not self.sharded
+        self.slots = 2 if self.pipelined else 1
+
+
+def _prepare_data(flow, x, weights, validation_split, shuffle):
+    """Cast, initial shuffle and split (flow.py:234-259): ``x, (x_train, w_train, x_valid, w_valid)`` -- all rows on the
+    device, then the two parts (the validation part None without a split)."""
     from .flow import torch_double_to_float
     x = torch_double_to_float(torch.as_tensor(x))
-    dev = flow.device
     n_samples, n_dim = x.shape
     if n_dim != flow.n_dim:
         raise ValueError("x has the wrong number of columns")
-    w = None if weights is None else torch.as_tensor(weights).to(torch.float32)
-
-    x = x.to(dev)
-    w = None if w is None else w.to(dev)
+    x = x.to(flow.device)
+    w = None if weights is None else torch.as_tensor(weights).to(torch.float32).to(flow.device)
     if shuffle:                                                     # flow.py:234-238 (the permutation still comes
-        rand_indx = torch.randperm(n_samples).to(dev)               # from torch's CPU generator; rows move on the device)
+        rand_indx = torch.randperm(n_samples).to(flow.device)       # from torch's CPU generator; rows move on the device)
         x = x[rand_indx]
         if w is not None:
             w = w[rand_indx]
     x = x.contiguous()
     w = None if w is None else w.contiguous()
-
     if validation_split > 0.0:                                      # flow.py:247-259
         cut = int(validation_split * n_samples)
-        x_train, x_valid = x[:cut], x[cut:]
-        w_train, w_valid = (None, None) if w is None else (w[:cut], w[cut:])
-        validation = True
-    else:
-        x_train, w_train, x_valid, w_valid = x, w, None, None
-        validation = False
+        return x, (x[:cut], None if w is None else w[:cut], x[cut:], None if w is None else w[cut:])
+    return x, (x, w, None, None)
 
-    world = _dist_world(group)
-    if sharded is None:
-        sharded = world > 1
-    if sharded:
-        import torch.distributed as dist
-    # ---- options (flow.py:240-245, :304-307, :314-315): see pmc_weight_penalty / pmc_add_noise_f32 in the header
-    penalty = None
-    if laplace_scale is not None or gaussian_scale is not None:
-        penalty = (float(laplace_scale or 0.0), float(gaussian_scale or 0.0), _weight_flags(flow))
-    noise_scale, noise_seed = None, 0
-    if noise is not None:
-        # flow.py:241-245: `mean_min_dist = torch.mean(min_dist)` -- the mean of the LAST row's distances to all rows
-        # (the nearest-neighbour distances `min_dists` computed in the loop above it are never used); its loop raises
-        # for a row without a positive distance, like torch.min of an empty tensor
-        if n_samples < 2:
-            raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
-        md = torch.zeros(1, dtype=torch.float32, device=dev)
-        if sharded:
-            # one scale for all ranks, the single-process value: the mean distance of the LAST row of the whole set (the
-            # last rank's last row) to every row of every shard
-            rank = dist.get_rank(group)
-            last = x[-1:].clone()
-            dist.broadcast(last, src=dist.get_global_rank(group, world - 1) if group is not None else world - 1, group=group)
-            xc = torch.cat([x, last]).contiguous()
-            with torch.cuda.device(dev):
-                _lib.check(flow.lib.pmc_mean_distance_f32(_lib.ptr(xc), n_samples + 1, n_dim, n_samples, _lib.ptr(md),
-                                                          _lib.stream_handle()), "pmc_mean_distance_f32")
-            tot = md.double() * (n_samples + 1)            # (the appended row adds a zero distance)
-            dist.all_reduce(tot, group=group)
-            md = (tot / (n_samples * world)).float()
-        else:
-            with torch.cuda.device(dev):
-                _lib.check(flow.lib.pmc_mean_distance_f32(_lib.ptr(x), n_samples, n_dim, n_samples - 1, _lib.ptr(md),
-                                                          _lib.stream_handle()), "pmc_mean_distance_f32")
-        noise_scale = float(noise) * float(md.item())
-        noise_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) * 2 ** 31 + int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        if sharded:
-            sd = torch.tensor([noise_seed], dtype=torch.int64, device=dev)
-            dist.broadcast(sd, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-            noise_seed = int(sd.item())
-    opt = AdamW(flow, learning_rate, weight_decay)
-    sched = ReduceLROnPlateau(opt, patience) if annealing else None
-    _train_state(flow).repack(flow)
 
-    history = dict(loss=[], val_loss=[])
-    monitor = "val_loss" if validation else "loss"
-    best_epoch, best_loss = 0, np.inf
-    best_model = flow.params.clone()
-    start = time.time()
+def _noise_setup(flow, x, noise, plan, group):
+    """``(scale, seed)`` of the noise a fit adds to its rows (flow.py:240-245; pmc_add_noise_f32 in the header), or None."""
+    if noise is None:
+        return None
+    # flow.py:241-245: `mean_min_dist = torch.mean(min_dist)` -- the mean of the LAST row's distances to all rows
+    # (the nearest-neighbour distances `min_dists` computed in the loop above it are never used); its loop raises
+    # for a row without a positive distance, like torch.min of an empty tensor
+    n_samples, n_dim = x.shape
+    if n_samples < 2:
+        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+    dev, world, xc = flow.device, plan.world, x
+    md = torch.zeros(1, dtype=torch.float32, device=dev)
+    if plan.sharded:
+        # one scale for all ranks, the single-process value: the mean distance of the LAST row of the whole set (the
+        # last rank's last row) to every row of every shard
+        last = x[-1:].clone()
+        dist.broadcast(last, src=dist.get_global_rank(group, world - 1) if group is not None else world - 1, group=group)
+        xc = torch.cat([x, last]).contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(flow.lib.pmc_mean_distance_f32(_lib.ptr(xc), xc.shape[0], n_dim, xc.shape[0] - 1, _lib.ptr(md),
+                                                  _lib.stream_handle()), "pmc_mean_distance_f32")
+    if plan.sharded:
+        tot = md.double() * (n_samples + 1)            # (the appended row adds a zero distance)
+        dist.all_reduce(tot, group=group)
+        md = (tot / (n_samples * world)).float()
+    scale = float(noise) * float(md.item())
+    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) * 2 ** 31 + int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+    if plan.sharded:
+        sd = torch.tensor([seed], dtype=torch.int64, device=dev)
+        dist.broadcast(sd, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+        seed = int(sd.item())
+    return scale, seed
 
-    n_train = x_train.shape[0]
-    n_valid = x_valid.shape[0] if validation else 0
-    # One epoch may be IN FLIGHT while the host looks at the previous epoch's losses (no scheduler, one GPU): the
-    # early-stop test needs every epoch's loss on the host, and waiting for it before enqueuing the next epoch
-    # leaves the GPU idle for the whole host turn-around (most of an epoch when the training set is one or two
-    # batches, the Sampler's usual case).  The speculative epoch changes nothing observable: on an early stop the
-    # best parameters are restored (flow.py:369-374), and no epoch is enqueued past `epochs`.
-    pipelined = (sched is None) and not sharded
-    slots = 2 if pipelined else 1
-    acc_d = [torch.zeros(2, dtype=torch.float32, device=dev) for _ in range(slots)]   # [train loss, val loss]
-    from .mcmc import _pinned_take, _pinned_give
-    acc_h = [_pinned_take((2,), torch.float32).zero_() for _ in range(slots)]
-    done = [torch.cuda.Event() for _ in range(slots)]
-    after = [torch.empty_like(flow.params) for _ in range(slots)]                    # parameters after the epoch
-    # (pinned staging from the process-wide free list: page-locking a buffer costs about a millisecond)
-    ts = _train_state(flow)
-    # Plain fits (one process, float32 engine, no penalty term, shuffled): ONE host-to-device copy per epoch carries both
-    # permutations AND the zeros of the two loss accumulators (two int64 words in front of the permutations in one staging
-    # buffer), and the parameters behind the epoch's last step are written by that step itself (pmc_adamw_t.snapshot) --
-    # three ~5 us launches fewer per epoch, of the ~75-120 us an epoch of the Sampler's fits takes.
-    fused = bool(shuffle) and not sharded and penalty is None and _wide_state(flow) is None
-    if fused:
-        n_stage = 2 + n_train + n_valid
-        h_stage = [_pinned_take((n_stage,), torch.int64) for _ in range(slots)]
-        for h_ in h_stage:
-            h_[:2] = 0
-        d_stage = [torch.zeros(n_stage, dtype=torch.int64, device=dev) for _ in range(slots)]
-        acc_d = [d[:1].view(torch.float32) for d in d_stage]           # [train loss, val loss] in the first word
-        view = lambda b, which: b[2:2 + n_train] if which == 0 else b[2 + n_train:n_stage]
-        h_perm, d_perm = [[], []], [[], []]
-    else:
-        h_perm = [[_pinned_take((max(n_train, 1),), torch.int64) for _ in range(slots)],
-                  [_pinned_take((max(n_valid, 1),), torch.int64) for _ in range(slots)]]
-        d_perm = [[torch.empty(max(n_train, 1), dtype=torch.int64, device=dev) for _ in range(slots)],
-                  [torch.empty(max(n_valid, 1), dtype=torch.int64, device=dev) for _ in range(slots)]]
-    if validation and not sharded and (getattr(ts, "logp_scratch", None) is None or ts.logp_scratch.numel() < n_valid):
-        ts.logp_scratch = torch.empty(int(n_valid), dtype=torch.float32, device=dev)
-    # The validation pass of epoch e only READS the parameters, and so do the loss / gradient launches of epoch e + 1's
-    # first batch; a batch's chain kernel occupies 32 of 256 compute units.  So the pass runs on a second stream, next to
-    # that batch, and only the first optimizer step of epoch e + 1 waits for it (pmc_maf_train_epoch_gated).  Float32
-    # engine, one process, no penalty term (those paths enqueue batch by batch from Python).
-    # It pays where the pass (two cross-stream hand-overs of ~16 us, the forward launch, the reduction, the copies: ~65 us
-    # at the Sampler's sizes) is SHORTER than the first batch's chain + weight-gradient launches it hides behind, and costs
-    # the host ~15 us per epoch: deep or spline flows (chain >= ~80 us) with a validation set of at most two batches' worth
-    # of rows -- the Sampler's regime (README example, nsf6: 152 -> 123 us per epoch).  Measured otherwise: maf3 at D = 10
-    # 76 -> 91 us (the epoch is bound by its ~120 us of enqueue, not by the device), the bench's fit (maf3 at D = 32, ten
-    # batches, 5000 validation rows whose 313 workgroups crowd the chain's 32) 0.95 -> 1.05 ms.
-    side = None
-    long_chain = flow.spec.n_transforms * (2 if flow.spec.univariate == "rqs" else 1) >= 6
-    if (validation and not sharded and penalty is None and _wide_state(flow) is None and long_chain
-            and n_valid <= 2 * int(batch_size)):
-        side = ts.side_stream
-    train_done = [torch.cuda.Event() for _ in range(slots)] if side is not None else None
-    main_h = torch.cuda.current_stream(dev).cuda_stream               # (looked up once: the fit stays on this stream)
-    gate = [None]                                                     # the event the next epoch's first update waits for
 
-    def upload_both(sl):
-        torch.randperm(n_train, out=view(h_stage[sl], 0))            # (the same draws in the same order as upload_perm)
-        if n_valid:
-            torch.randperm(n_valid, out=view(h_stage[sl], 1))
-        d_stage[sl].copy_(h_stage[sl], non_blocking=True)
-        return view(d_stage[sl], 0), (view(d_stage[sl], 1) if n_valid else None)
+class _FitSlots:
+    """The buffers of the epochs a fit has enqueued, one slot each (``_FitPlan.slots``), and ``gate``: the event the NEXT
+    epoch's first update waits for (the validation pass on the side stream)."""
 
-    def upload_perm(which, sl, n):
+    def __init__(self, flow, plan, x_train, x_valid, shuffle, noise, rank):
+        dev, k = flow.device, range(plan.slots)
+        self.flow, self.fused, self.shuffle, self.gate = flow, plan.fused_staging, bool(shuffle), None
+        self.noise, self.rank, self.n_train, self.n_valid = noise, rank, x_train.shape[0], plan.n_valid
+        n_train, n_valid = self.n_train, self.n_valid
+        # per slot ONE staging buffer, pinned and on the device: [the two losses in the first word, zeros on the host | training
+        # | validation permutation]  (pinned staging from the process-wide free list: page-locking a buffer costs ~1 ms)
+        self.h_stage = [_pinned_take((2 + n_train + n_valid,), torch.int64).zero_() for _ in k]
+        self.d_stage = [torch.zeros(2 + n_train + n_valid, dtype=torch.int64, device=dev) for _ in k]
+        self.h_perm = [[h[2:2 + n_train] for h in self.h_stage], [h[2 + n_train:] for h in self.h_stage]]   # [0 train | 1 valid][sl]
+        self.d_perm = [[d[2:2 + n_train] for d in self.d_stage], [d[2 + n_train:] for d in self.d_stage]]
+        self.acc_d = [d[:1].view(torch.float32) for d in self.d_stage]            # [train loss, val loss]
+        self.acc_train, self.acc_valid = [a[0:1] for a in self.acc_d], [a[1:2] for a in self.acc_d]
+        self.acc_h = [_pinned_take((2,), torch.float32).zero_() for _ in k]      # the losses on the host, complete at `done`
+        self.done = [torch.cuda.Event() for _ in k]
+        self.after = [torch.empty_like(flow.params) for _ in k]                  # parameters after the epoch
+        self.noisy = None if noise is None else [[torch.empty_like(x_train) for _ in k],
+                                                 [torch.empty_like(x_valid) if plan.validation else None for _ in k]]
+        self.main = torch.cuda.current_stream(dev)                    # (looked up once: the fit stays on this stream)
+        self.side = flow._train.side_stream if plan.valid_mode == "call_side" else None
+        self.train_done = [torch.cuda.Event() for _ in k] if self.side is not None else None
+
+    def upload(self, which, sl):
         # DataLoader(shuffle=...), flow.py:251-265: a fresh permutation per pass (pinned staging, no host sync)
-        torch.randperm(n, out=h_perm[which][sl][:n])
-        d_perm[which][sl][:n].copy_(h_perm[which][sl][:n], non_blocking=True)
-        return d_perm[which][sl][:n]
+        torch.randperm(self.h_perm[which][sl].numel(), out=self.h_perm[which][sl])
+        self.d_perm[which][sl].copy_(self.h_perm[which][sl], non_blocking=True)
+        return self.d_perm[which][sl]
 
-    noisy = None
-    if noise_scale is not None:
-        noisy = [[torch.empty_like(x_train) for _ in range(slots)],
-                 [torch.empty_like(x_valid) if validation else None for _ in range(slots)]]
+    def upload_perms(self, sl):
+        # zeroes the slot's losses, returns its training permutation (or None); fused: ONE copy with the zeros and both passes'
+        if not self.fused:
+            self.acc_d[sl].zero_()
+            return self.upload(0, sl) if self.shuffle else None
+        torch.randperm(self.n_train, out=self.h_perm[0][sl])          # (the same draws in the same order as unfused)
+        if self.n_valid:
+            torch.randperm(self.n_valid, out=self.h_perm[1][sl])
+        self.d_stage[sl].copy_(self.h_stage[sl], non_blocking=True)
+        return self.d_perm[0][sl]
 
-    def with_noise(which, sl, epoch, src):
+    def with_noise(self, which, sl, epoch, src):
         """Fresh noise on every row of a pass (the reference draws it per batch of every epoch, flow.py:305 / :334)."""
-        if noisy is None:
+        if self.noisy is None:
             return src
-        dst = noisy[which][sl]
-        with torch.cuda.device(dev):
+        dst, (scale, seed) = self.noisy[which][sl], self.noise
+        with torch.cuda.device(self.flow.device):
             # (a rank's shard draws the noise of ITS rows of the whole set: keyed by the global row)
-            row0 = (dist.get_rank(group) if sharded else 0) * src.shape[0]
-            _lib.check(flow.lib.pmc_add_noise_rows_f32(_lib.ptr(src), src.shape[0], n_dim, noise_scale, noise_seed,
-                                                       2 * epoch + which, row0, _lib.ptr(dst), _lib.stream_handle()),
-                       "pmc_add_noise_rows_f32")
+            _lib.check(self.flow.lib.pmc_add_noise_rows_f32(_lib.ptr(src), src.shape[0], src.shape[1], scale, seed,
+                                                            2 * epoch + which, self.rank * src.shape[0], _lib.ptr(dst),
+                                                            _lib.stream_handle()), "pmc_add_noise_rows_f32")
         return dst
 
-    def add_penalty(grad, loss, mult=1.0):
-        b, g, flags = penalty
-        with torch.cuda.device(dev):
-            _lib.check(flow.lib.pmc_weight_penalty(_lib.ptr(flow.params), _lib.ptr(flags), _lib.ptr(grad) if grad is not None else None,
-                                                   flow.params.numel(), b, g, float(mult), _lib.ptr(loss),
-                                                   _lib.ptr(ts.sq_partial), _lib.stream_handle()), "pmc_weight_penalty")
+    def release(self):
+        # a speculative epoch may still be copying its permutations / losses: wait before the staging goes back
+        if self.side is not None:
+            torch.cuda.current_stream(self.flow.device).wait_stream(self.side)
+            self.side.synchronize()
+        torch.cuda.current_stream().synchronize()
+        for t in self.acc_h + self.h_stage:
+            _pinned_give(t)
 
-    def penalised_epoch(xs, ws, perm, acc):
-        """Batch by batch (flow.py:301-321) with the penalty's gradient added before the clip (flow.py:314-318)."""
-        n = xs.shape[0]
-        for b0 in range(0, n, int(batch_size)):
-            nb = min(int(batch_size), n - b0)
-            idx = perm[b0:b0 + nb] if perm is not None else None
-            xb = xs if idx is not None else xs[b0:b0 + nb]
-            wb = None if ws is None else (ws if idx is not None else ws[b0:b0 + nb])
-            acc += loss_and_grad(flow, xb, wb, idx, refresh=False)
-            add_penalty(ts.grad, acc)
-            opt.step(clip_grad_norm)
 
-    def enqueue(epoch):
-        sl = epoch % slots
-        acc2 = acc_d[sl]
-        vperm_f = None
-        if fused:
-            perm, vperm_f = upload_both(sl)                          # (also zeroes acc2)
-        else:
-            acc2.zero_()
-            perm = upload_perm(0, sl, n_train) if shuffle else None
-        acc = acc2[0:1]
-        xs = with_noise(0, sl, epoch, x_train)
-        if sharded:
-            sharded_epoch(flow, opt, xs, w_train, perm, batch_size, clip_grad_norm, acc, group,
-                          penalty=add_penalty if penalty is not None else None)
-        elif penalty is not None:
-            penalised_epoch(xs, w_train, perm, acc)
-        elif side is not None:
-            opt.epoch(xs, w_train, perm, batch_size, clip_grad_norm, acc, gate=gate[0], stream=main_h,
-                      snapshot=after[sl] if fused else None)
-            if not fused:
-                after[sl].copy_(flow.params)                          # (the parameters after this epoch's last update)
-            main = torch.cuda.current_stream(dev)
-            train_done[sl].record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(train_done[sl])
-                x_valid_e = with_noise(1, sl, epoch, x_valid)
-                vperm = vperm_f if fused else (upload_perm(1, sl, n_valid) if shuffle else None)
-                with torch.cuda.device(dev):
-                    _lib.check(flow.lib.pmc_maf_valid_epoch(C.byref(flow._desc), _lib.ptr(x_valid_e),
-                                                            _lib.ptr(w_valid) if w_valid is not None else None,
-                                                            _lib.ptr(vperm) if vperm is not None else None,
-                                                            n_valid, int(batch_size), _lib.ptr(ts.logp_scratch),
-                                                            _lib.ptr(acc2[1:2]), C.c_void_p(side.cuda_stream)), "pmc_maf_valid_epoch")
-                acc_h[sl].copy_(acc2, non_blocking=True)
-                done[sl].record(side)
-            gate[0] = done[sl]
-            return
-        else:
-            opt.epoch(xs, w_train, perm, batch_size, clip_grad_norm, acc, stream=main_h, snapshot=after[sl] if fused else None)
-        vacc = acc2[1:2]
-        x_valid_e = with_noise(1, sl, epoch, x_valid) if validation else None
-        if validation and not sharded:
-            # the whole validation pass in one library call (batches of the reference's DataLoader, flow.py:327-348)
-            vperm = vperm_f if fused else (upload_perm(1, sl, n_valid) if shuffle else None)
-            with torch.cuda.device(dev):
-                _lib.check(flow.lib.pmc_maf_valid_epoch(C.byref(flow._desc), _lib.ptr(x_valid_e),
-                                                        _lib.ptr(w_valid) if w_valid is not None else None,
-                                                        _lib.ptr(vperm) if vperm is not None else None,
-                                                        n_valid, int(batch_size), _lib.ptr(ts.logp_scratch),
-                                                        _lib.ptr(vacc), _lib.stream_handle()), "pmc_maf_valid_epoch")
-        elif validation:
-            vb = max(1, batch_size // world)
-            for idx in _batches(n_valid, vb, shuffle):
-                idx = idx.to(dev)
-                vacc += batch_loss(flow, x_valid_e[idx].contiguous(),
-                                   None if w_valid is None else w_valid[idx].contiguous(), group, sharded)
-        if sharded:
-            # the validation loss is a sum over the ranks' shards (the training loss already is: it rode
-            # along with the gradients)
-            dist.all_reduce(acc2[1:2], group=group)
-        if validation and penalty is not None:
-            # flow.py:342-343: every validation batch's loss carries the penalty
-            vb = int(batch_size) if not sharded else max(1, int(batch_size) // world)
-            add_penalty(None, vacc, mult=-(-n_valid // vb))
-        if not fused:
-            after[sl].copy_(flow.params)
-        acc_h[sl].copy_(acc2, non_blocking=True)
-        done[sl].record()
+def _enqueue(slots, n_slots, train, validate, sum_ranks, valid_penalty, x_train, x_valid, epoch):
+    """One epoch on the device: staging, training pass, validation pass, the slot's tail -- on the main stream, or from the
+    validation pass on behind ``train_done`` on the side stream, whose ``done`` then gates the next epoch's first update."""
+    sl = epoch % n_slots
+    perm = slots.upload_perms(sl)
+    xs = slots.with_noise(0, sl, epoch, x_train)
+    keep = None if slots.fused else slots.after[sl]                  # (fused: the epoch's last step writes them itself)
+    if slots.side is None:
+        train[sl](xs, perm=perm)
+        if validate is not None:
+            validate(sl, slots.with_noise(1, sl, epoch, x_valid))
+        if sum_ranks is not None:            # a sum over the ranks' shards (the training loss rode along with the gradients)
+            sum_ranks(slots.acc_valid[sl])
+        if valid_penalty is not None:
+            valid_penalty(slots.acc_valid[sl])
+        if keep is not None:
+            keep.copy_(slots.flow.params)
+        slots.acc_h[sl].copy_(slots.acc_d[sl], non_blocking=True)
+        slots.done[sl].record()
+    else:                                                             # (a plain fit: one process, no penalty)
+        train[sl](xs, perm=perm, gate=slots.gate)
+        if keep is not None:
+            keep.copy_(slots.flow.params)
+        slots.train_done[sl].record(slots.main)
+        with torch.cuda.stream(slots.side):
+            slots.side.wait_event(slots.train_done[sl])
+            validate(sl, slots.with_noise(1, sl, epoch, x_valid))
+            slots.acc_h[sl].copy_(slots.acc_d[sl], non_blocking=True)
+            slots.done[sl].record(slots.side)
+        slots.gate = slots.done[sl]
 
+
+def _host_loop(flow, plan, slots, enqueue, sched, epochs, patience, verbose):
+    """The host's side of the epochs (flow.py:323-374): losses, scheduler, best-state snapshot, early stop."""
+    history = dict(loss=[], val_loss=[])
+    validation, pipelined, monitor = plan.validation, plan.pipelined, "val_loss" if plan.validation else "loss"
+    best_epoch, best_loss, best_model = 0, np.inf, flow.params.clone()
+    n_tr, n_va = (max(n * (plan.world if plan.sharded else 1), 1) for n in (slots.n_train, slots.n_valid))
+    start = time.time()
     if epochs > 0:
         enqueue(0)
     for epoch in range(epochs):
-        sl = epoch % slots
+        sl = epoch % plan.slots
         if pipelined and epoch + 1 < epochs:
             enqueue(epoch + 1)                                        # speculative: runs while we read this epoch's losses
-        done[sl].synchronize()                                        # the one wait of the epoch
-        both = acc_h[sl].numpy()
-        n_tr, n_va = (n_train * world, n_valid * world) if sharded else (n_train, n_valid)
-        train_loss = float(both[0]) / max(n_tr, 1)                   # flow.py:323
+        slots.done[sl].synchronize()                                  # the one wait of the epoch
+        both = slots.acc_h[sl].numpy()
+        train_loss = float(both[0]) / n_tr                            # flow.py:323
         history["loss"].append(train_loss)
         if validation:
-            val_loss = float(both[1]) / max(n_va, 1)                 # flow.py:348
+            val_loss = float(both[1]) / n_va                          # flow.py:348
             history["val_loss"].append(val_loss)
         if sched is not None:
             sched.step(val_loss if validation else train_loss)
@@ -686,10 +641,10 @@ def fit_flow(flow, x, weights=None, validation_split=0.0, epochs=1000, batch_siz
                   + (", val loss: %5.2f" % val_loss if validation else ""))
         if history[monitor][-1] < best_loss:                          # flow.py:364-367
             best_loss, best_epoch = history[monitor][-1], epoch
-            best_model.copy_(after[sl])
+            best_model.copy_(slots.after[sl])
         if epoch - best_epoch >= int(1.5 * patience):                 # flow.py:369-374
-            if side is not None:
-                torch.cuda.current_stream(dev).wait_stream(side)      # (a speculative validation pass still reads the images)
+            if slots.side is not None:                                # (a speculative validation pass still reads the images)
+                torch.cuda.current_stream(flow.device).wait_stream(slots.side)
             flow.params.copy_(best_model)
             flow.repack()
             if verbose > 0:
@@ -702,26 +657,71 @@ def fit_flow(flow, x, weights=None, validation_split=0.0, epochs=1000, batch_siz
         total = time.time() - start
         print("\nTime total:     %5.2f sec" % total)
         print("Time per epoch: %5.2f sec" % (total / epochs))
-    # a speculative epoch may still be copying its permutations / losses: wait before the staging goes back
-    if side is not None:
-        torch.cuda.current_stream(dev).wait_stream(side)
-        side.synchronize()
-    torch.cuda.current_stream().synchronize()
-    for t in acc_h + h_perm[0] + h_perm[1] + (h_stage if fused else []):
-        _pinned_give(t)
+    return history
+
+
+def _post_fit(flow, plan, x, history, group):
+    """The 16-bit images follow the trained float32 parameters, and the 16-bit inverse sweep is checked on them."""
     if getattr(flow, "_bf16", None) is not None or getattr(flow, "_lane16", None) is not None:
-        flow.repack()                              # the 16-bit images follow the trained float32 parameters
+        flow.repack()
     if getattr(flow, "_lane16", None) is not None:
         # the 16-bit sweep's safety net: compared with the float32 sweep on the latent image of the training rows
         # (what mcmc.py:88 inverts), float32 from here on if it is not an inverse within the bounds
         guard = flow.check_inverse_precision(theta=flow.forward(x[:4096])[0], rows=4096)
         if guard is not None:
-            if sharded:
+            if plan.sharded:
                 # every rank takes the same sweep: one rank's fallback is everybody's
-                flag = torch.tensor([0.0 if guard["passed"] else 1.0], device=dev)
+                flag = torch.tensor([0.0 if guard["passed"] else 1.0], device=flow.device)
                 dist.all_reduce(flag, group=group)
                 if float(flag.item()) > 0 and guard["passed"]:
                     flow._desc.lane16 = None
                     guard["passed"] = False
             history["inverse_guard"] = guard
+
+
+def fit_flow(flow, x, weights=None, validation_split=0.0, epochs=1000, batch_size=1000, patience=20,
+             learning_rate=1e-3, weight_decay=0, laplace_scale=None, gaussian_scale=None, annealing=True,
+             noise=None, shuffle=True, clip_grad_norm=1.0, verbose=0, group=None, sharded=None):
+    """``sharded`` (default: a ``torch.distributed`` group with more than one rank exists): ``x`` / ``weights`` are THIS rank's
+    shard of the training rows (equal shard sizes), ``batch_size`` is the global batch; gradients and losses are all-reduced
+    (RCCL on the GPUs) so that every rank takes the same optimizer steps and the same early-stopping decisions."""
+    x, (x_train, w_train, x_valid, w_valid) = _prepare_data(flow, x, weights, validation_split, shuffle)
+    penalty = None                                  # flow.py:304-307, :314-315: see pmc_weight_penalty in the header
+    if laplace_scale is not None or gaussian_scale is not None:
+        penalty = partial(_add_penalty, flow, (float(laplace_scale or 0.0), float(gaussian_scale or 0.0), _weight_flags(flow)))
+    plan = _FitPlan(flow, x_valid, batch_size, shuffle, penalty is not None, annealing, group, sharded)
+    noise = _noise_setup(flow, x, noise, plan, group)
+    opt = AdamW(flow, learning_rate, weight_decay)
+    sched = ReduceLROnPlateau(opt, patience) if annealing else None
+    _train_state(flow).repack(flow)
+    slots = _FitSlots(flow, plan, x_train, x_valid, shuffle, noise, dist.get_rank(group) if plan.sharded else 0)
+
+    # the mode's functions, bound once: an epoch of the Sampler's fits is 75-120 us and bound by the host's enqueue
+    if plan.train_mode == "sharded":
+        train = partial(_train_sharded, flow, opt, group=group, penalty=penalty)
+    elif plan.train_mode == "penalised":
+        train = partial(_train_penalised, flow, opt, penalty=penalty)
+    else:
+        train = partial(opt.epoch, stream=slots.main.cuda_stream)
+    train = [partial(train, w=w_train, batch_size=batch_size, max_norm=clip_grad_norm, loss_acc=a) for a in slots.acc_train]
+    if plan.fused_staging:                          # (the epoch's last step writes the parameters behind it itself)
+        train = [partial(t, snapshot=p) for t, p in zip(train, slots.after)]
+    validate = None
+    local_batch = max(1, int(batch_size) // plan.world) if plan.sharded else int(batch_size)
+    if plan.valid_mode == "sharded":
+        validate = partial(_valid_sharded, flow, slots, w_valid, local_batch, shuffle, group)
+    elif plan.valid_mode is not None:
+        if getattr(flow._train, "logp_scratch", None) is None or flow._train.logp_scratch.numel() < plan.n_valid:
+            flow._train.logp_scratch = torch.empty(plan.n_valid, dtype=torch.float32, device=flow.device)
+        stream = slots.side if plan.valid_mode == "call_side" else slots.main
+        validate = partial(_valid_epoch_call, flow, slots, w_valid, batch_size, C.c_void_p(stream.cuda_stream))
+    valid_penalty = None
+    if plan.validation and penalty is not None:     # flow.py:342-343: every validation batch's loss carries the penalty
+        valid_penalty = partial(penalty, None, mult=-(-plan.n_valid // local_batch))
+    enqueue = partial(_enqueue, slots, plan.slots, train, validate,
+                      partial(dist.all_reduce, group=group) if plan.sharded else None, valid_penalty, x_train, x_valid)
+
+    history = _host_loop(flow, plan, slots, enqueue, sched, epochs, patience, verbose)
+    slots.release()
+    _post_fit(flow, plan, x, history, group)
     return history
