@@ -751,6 +751,38 @@ int64_t pmc_column_medians_workspace_bytes(int64_t n, int32_t D, int32_t is_f32)
 int pmc_column_medians(const double* x, const float* x32, const int64_t* idx, int64_t n, int32_t D, double* med64,
                        float* med32, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The EM fit of a multivariate Student-t (location, scatter, degrees of freedom: what student.py:53-85 sets out to do) to
+ * the rows x[idx[r]], r < n (idx NULL: rows 0..n-1; rows float64 (x) or float32 (x32), widened on load), all in float64:
+ *   start: mu_io f64 [D], sigma_io f64 [D][D] as given (device), nu = 20, last_nu = 0; i = 0
+ *   while |last_nu - nu| > tol and i < max_iter:      (++i)
+ *     d_r = x_r - mu, delta_r = d_r^T Sigma^-1 d_r    (Cholesky factor of Sigma by one workgroup, then one lane per row)
+ *     last_nu = nu; nu <- root of
+ *         f(nu) = log(nu/2) - psi(nu/2) + mean(log w - w) + 1 + psi((nu+D)/2) - log((nu+D)/2),  w_r = (nu+D)/(nu+delta_r)
+ *       in [PMC_STUDENT_NU_LO, PMC_STUDENT_NU_HI] = [0.1, 1e4]: f(NU_HI) >= 0 -> nu = inf, stop, mu / Sigma as they are;
+ *       f(NU_LO) <= 0 -> nu = NU_LO; else a bracketed secant in log nu until the bracket is below 1e-13
+ *     Sigma <- sum_r w_r d_r d_r^T / n  (w at the new nu, d about the old mu);  mu <- sum_r w_r x_r / sum_r w_r
+ * mu_io / sigma_io hold the result (device).  result: HOST f64 [4] <- { nu (inf possible), iterations i, status
+ * (PMC_STUDENT_*), number of host reads }.  Every reduction has a fixed order (the same bits on every call and every
+ * device); convergence is decided on the device -- a done word in the workspace turns every later kernel of the call
+ * into a no-op -- and the host enqueues 8 iterations at a time and reads the 32-byte state in between (the call
+ * synchronises `stream`).  A Cholesky pivot that is <= 0 or not finite ends the fit with PMC_STUDENT_NOT_PD, a NaN in
+ * f with PMC_STUDENT_NONFINITE: mu_io / sigma_io then hold the last completed iteration's values.
+ * 1 <= D <= PMC_STUDENT_MAX_D (the packed factor and 64 rows' substitution vectors share the LDS), n > D, max_iter >= 1.
+ * workspace: pmc_student_em_workspace_bytes(n, D). */
+#define PMC_STUDENT_MAX_D 128
+#define PMC_STUDENT_NU_LO 0.1
+#define PMC_STUDENT_NU_HI 1e4
+#define PMC_STUDENT_CONVERGED 0
+#define PMC_STUDENT_MAX_ITER 1
+#define PMC_STUDENT_NU_INF 2
+#define PMC_STUDENT_LOWER_CLAMP 3   /* converged or out of iterations with nu == PMC_STUDENT_NU_LO */
+#define PMC_STUDENT_NOT_PD 4
+#define PMC_STUDENT_NONFINITE 5
+int64_t pmc_student_em_workspace_bytes(int64_t n, int32_t D);
+int pmc_student_em(const double* x, const float* x32, const int64_t* idx, int64_t n, int32_t D, double* mu_io,
+                   double* sigma_io, double tol, int32_t max_iter, double* result, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+
 /* The full affine map of Reparameterize(diagonal=False), scaler.py:288-292 / :308-313, on rows f64 [n][D]:
  * mode 0: out = mu + M in (M = L: _inverse_affine), mode 1: out = M (in - mu) (M = L^-1: _forward_affine).  in != out. */
 int pmc_affine_rows(const double* M, const double* mu, const double* in, double* out, int64_t n, int32_t D,

@@ -19,6 +19,13 @@ this scipy: psi and log agree to the last bit at 5e299).  The reference's t-fit 
 ``(median, start Sigma, inf)`` with ``t_nu`` replaced by 1e6 (``geometry.py:58-59``); a build whose libm made the
 constant negative would raise from ``bisect`` on every call.  This class reproduces exactly that: the start values from
 the device, the same constant test, the same error.
+
+That "always ``inf``" holds for ``Geometry(student="reference")``, the default.  ``Geometry(student="em")`` runs the fit
+the reference sets out to do (``student.py:53-85``) with a root finder for ``nu`` that works -- a bracket of
+``[0.1, 1e4]`` instead of ``[1e-300, 1e300]`` -- from the same start values, on the device (``pmc_student_em``,
+``csrc/student.hip``; the algorithm is stated in ``include/pocomc_amd.h``).  Gaussian rows leave it at the first
+iteration with ``nu = inf`` and the start values: the reference mode's result, bit for bit.  Heavy-tailed rows give the
+finite ``nu`` the t-preconditioned Crank-Nicolson step was written for.
 """
 from __future__ import annotations
 
@@ -93,10 +100,52 @@ def column_medians(x, idx=None):
     return med.cpu().numpy()
 
 
-class Geometry:
-    """``pocomc/geometry.py:5-59``."""
+STUDENT_MAX_D = 128                                                        # PMC_STUDENT_MAX_D
+STUDENT_STATUS = ("converged", "max_iter", "nu_inf", "lower_clamp", "not_pd", "nonfinite")     # PMC_STUDENT_*
 
-    def __init__(self):
+
+def student_em(x, idx, mu, sigma, tol=1e-6, max_iter=100):
+    """The EM fit of a multivariate Student-t to the rows ``x[idx]`` (device tensor, float64 or float32; ``idx`` int64
+    device tensor or None) from the start values ``mu`` [D], ``sigma`` [D, D] (numpy), on the device (``pmc_student_em``).
+    Returns ``(mu, sigma, info)``: float64 numpy arrays and ``dict(nu=, iterations=, status=, host_reads=)`` with
+    ``status`` one of ``STUDENT_STATUS`` and ``nu = inf`` for rows no heavier-tailed than a normal."""
+    lib = _lib.load()
+    n = int(idx.numel()) if idx is not None else int(x.shape[0])
+    D = int(x.shape[1])
+    if D > STUDENT_MAX_D:
+        raise ValueError(f"student_em: n_dim = {D} is above {STUDENT_MAX_D}, the largest the device fit supports")
+    if n <= D:
+        raise ValueError(f"student_em: {n} rows cannot fit a {D}-dimensional Student-t (more rows than dimensions needed)")
+    dev = x.device
+    start = np.concatenate([np.asarray(mu, dtype=np.float64).reshape(D), np.asarray(sigma, dtype=np.float64).reshape(D * D)])
+    io = torch.from_numpy(start).to(dev)
+    nbytes = int(lib.pmc_student_em_workspace_bytes(n, D))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    res = (C.c_double * 4)()
+    f32 = x.dtype == torch.float32
+    with torch.cuda.device(dev):
+        _lib.check(lib.pmc_student_em(None if f32 else _lib.ptr(x), _lib.ptr(x) if f32 else None,
+                                      _lib.ptr(idx) if idx is not None else None, n, D, _lib.ptr(io),
+                                      C.c_void_p(io.data_ptr() + 8 * D), float(tol), int(max_iter), res, _lib.ptr(ws), nbytes,
+                                      _lib.stream_handle()), "pmc_student_em")
+    out = io.cpu().numpy()
+    info = dict(nu=float(res[0]), iterations=int(res[1]), status=STUDENT_STATUS[int(res[2])], host_reads=int(res[3]))
+    return out[:D], out[D:].reshape(D, D), info
+
+
+class Geometry:
+    """``pocomc/geometry.py:5-59``.  ``student``: ``"reference"`` (default) reproduces the reference's t-fit, which always
+    ends at its start values with ``t_nu = 1e6``; ``"em"`` fits location, scatter and degrees of freedom by EM on the
+    device (module docstring) and records ``student_info = dict(iterations=, status=, nu=)``."""
+
+    student = "reference"                      # (objects unpickled from checkpoints older than the attribute)
+    student_info = None
+
+    def __init__(self, student="reference"):
+        if student not in ("reference", "em"):
+            raise ValueError(f"Invalid student {student}. Options are 'reference' or 'em'.")
+        self.student = student
+        self.student_info = None
         self.normal_mean = self.normal_cov = self.t_mean = self.t_cov = self.t_nu = None
 
     def fit(self, theta, weights=None):
@@ -104,6 +153,11 @@ class Geometry:
         from .tools import systematic_resample
         th = _as_device(theta)
         n, D = int(th.shape[0]), int(th.shape[1])
+        if self.student == "em":                                           # (before any launch)
+            if D > STUDENT_MAX_D:
+                raise ValueError(f"Geometry.fit: student='em' supports n_dim <= {STUDENT_MAX_D}, got {D}")
+            if n <= D:
+                raise ValueError(f"Geometry.fit: student='em' needs more rows than dimensions, got {n} rows of {D}")
         if weights is None:
             mean, S, _, _ = moments(th)
             self.normal_mean = mean                                        # np.mean(theta, axis=0)
@@ -122,7 +176,7 @@ class Geometry:
         if th.dtype == torch.float32:
             var = var.astype(np.float32)                                   # np.var of a float32 array is a float32
         sigma = Ss / n + (1 / n) * np.diag(var)                            # student.py:46-47: cov*(n-1)/n + diag(var)/n
-        if _func0_at_1e300(D) >= 0:                                        # student.py:39-40 -> :59-60
+        if self.student == "em" or _func0_at_1e300(D) >= 0:                # student.py:39-40 -> :59-60
             nu = np.inf
         else:
             raise RuntimeError("Failed to converge after 100 iterations (scipy.optimize.bisect(func0, 1e-300, 1e300), "
@@ -138,6 +192,15 @@ class Geometry:
             np.linalg.solve(sigma, np.eye(D))
         except np.linalg.LinAlgError:
             raise np.linalg.LinAlgError("Geometry.fit: the scatter matrix of theta is singular (student.py:70 solves with it)")
+        if self.student == "em":
+            med, sigma, info = student_em(th, idx, med, sigma)
+            if info["status"] == "not_pd":
+                raise np.linalg.LinAlgError(f"Geometry.fit: the scatter matrix of the Student-t fit is not positive definite "
+                                            f"(EM iteration {info['iterations']})")
+            if info["status"] == "nonfinite":
+                raise ValueError(f"Geometry.fit: non-finite values in the Student-t fit (EM iteration {info['iterations']})")
+            nu = info["nu"]
+            self.student_info = dict(iterations=info["iterations"], status=info["status"], nu=nu)
         self.t_mean, self.t_cov, self.t_nu = med, sigma, nu
         if not np.isfinite(self.t_nu):
             self.t_nu = 1e6                                                # geometry.py:58-59

@@ -145,7 +145,7 @@ class Sampler:
                  train_frequency=None, precondition=True, dynamic=True, metric="ess", n_prior=None,
                  sample="tpcn", n_steps=None, n_max_steps=None, resample="mult", output_dir=None,
                  output_label=None, random_state=None, n_ess=None, group=None, mcmc_options=None,
-                 device_likelihood=False, device_blobs=False, device_prior=False):
+                 device_likelihood=False, device_blobs=False, device_prior=False, student_fit="reference"):
         """Arguments and defaults of ``pocomc/sampler.py:154-185``, plus
 
         ``group``         a ``torch.distributed`` process group (default: the initialised default group): one process
@@ -175,6 +175,11 @@ class Sampler:
                           scipy factors (``Prior(dists)``, which the device evaluates from a table by itself).  The MCMC
                           steps then never hand x' to the host; warm-up and evidence call the same function on uploaded
                           rows.  Sharded: called on every rank with that rank's rows, the same function on every rank.
+        ``student_fit``   how the Student-t geometry of the MCMC step is fitted (``pocomc_amd/geometry.py``):
+                          ``"reference"`` (default) as the reference does, which always ends at ``nu = 1e6`` -- a Gaussian
+                          pCN step; ``"em"`` by EM on the device (``pmc_student_em``, ``n_dim <= 128``), which gives
+                          heavy-tailed pools the finite ``nu`` of the t-preconditioned step and Gaussian ones the
+                          reference's values.  Sharded: every rank fits the replicated pool and gets the same bits.
 
         Supported ``train_config`` keys: those of ``sampler.py:287-299`` (``validation_split, epochs, batch_size,
         patience, learning_rate, annealing, gaussian_scale, laplace_scale, noise, shuffle, clip_grad_norm, verbose``),
@@ -242,7 +247,8 @@ class Sampler:
             self.distribute = pool.map
 
         for name, value, allowed in (("transform", transform, ("probit", "logit")), ("metric", metric, ("ess", "uss")),
-                                     ("sample", sample, ("tpcn", "rwm")), ("resample", resample, ("mult", "syst"))):
+                                     ("sample", sample, ("tpcn", "rwm")), ("resample", resample, ("mult", "syst")),
+                                     ("student_fit", student_fit, ("reference", "em"))):
             if value not in allowed:
                 raise ValueError(f"Invalid {name} {value}. Options are {' or '.join(repr(a) for a in allowed)}.")
         self.metric, self.sample, self.resample, self.dynamic = metric, sample, resample, dynamic
@@ -264,7 +270,8 @@ class Sampler:
                                 else int(train_frequency))                                                       # :305
         self.flow_untrained = True
         self.scaler = Reparameterize(D, bounds=self.bounds, periodic=periodic, reflective=reflective, transform=transform)
-        self.u_geometry, self.theta_geometry = Geometry(), Geometry()
+        self.student_fit = student_fit
+        self.u_geometry, self.theta_geometry = Geometry(student_fit), Geometry(student_fit)
         self.proposal_scale = 2.38 / D ** 0.5                                                                    # :350
         self.dynamic_ratio = unique_sample_size(np.ones(self.n_effective), k=self.n_active) / self.n_active      # :340
         self.n_prior = (int(2 * np.maximum(self.n_effective // self.n_active, 1) * self.n_active) if n_prior is None
