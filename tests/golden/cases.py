@@ -157,6 +157,32 @@ BIG_GOLDEN_CASES = {
 }
 
 
+# tpCN steps at the degrees of freedom a Student-t EM fit hands over (Geometry(student="em")): the lower clamp 0.1, a
+# converged heavy-tailed fit (0.9057), a large-nu fit (588.26) and the upper end of the fit's bracket, 1e4.  Not golden
+# cases (no vectors from the reference: the oracle is the yardstick, tests/test_gpu_step_nu_range.py), so not in
+# MCMC_CASES.  Seeds: at nu = 0.1 with the "mixed" prior they are chosen so that the oracle rejects at least one proposal
+# outright (x' or its log-determinant not finite: exp() of a half-bounded coordinate overflows) while most stay finite -- the first of 100, 101, ...
+# that does (tests/test_student_em_cpu.py holds it).  With the box prior and with the spline flow no seed of 300 does: the
+# logit keeps x' in the box and its log-determinant finite for every finite u', and the splines' linear tails do not
+# amplify theta' as the affine flow's scales do.
+NU_RANGE_CASES = {}
+for _tag, _nu in (("0p1", 0.1), ("0p9057", 0.9057), ("588", 588.26), ("1e4", 1e4)):
+    for _N, _D in ((96, 2), (80, 5), (128, 10)):
+        for _prior in ("uniform", "mixed"):
+            NU_RANGE_CASES[f"tpcn_nu{_tag}_n{_N}_d{_D}_{_prior}"] = dict(
+                kind="preconditioned_pcn", N=_N, D=_D, T=3, beta=0.5, nu=_nu, prior=_prior, target="gauss",
+                seed=200 + len(NU_RANGE_CASES), n_max=3)
+NU_RANGE_CASES["tpcn_nu0p1_n96_d2_mixed"]["seed"] = 100
+NU_RANGE_CASES["tpcn_nu0p1_n80_d5_mixed"]["seed"] = 112
+NU_RANGE_CASES["tpcn_nu0p1_n128_d10_mixed"]["seed"] = 100
+NU_RANGE_CASES["tpcn_nu0p9057_n80_d5_reflect"] = dict(
+    kind="preconditioned_pcn", N=80, D=5, T=3, beta=0.5, nu=0.9057, prior="uniform", target="gauss", seed=230, n_max=3,
+    periodic=[0], reflective=[2])
+NU_RANGE_CASES["tpcn_nu0p1_n80_d5_nsf3"] = dict(
+    kind="preconditioned_pcn", N=80, D=5, T=3, beta=0.5, nu=0.1, prior="mixed", target="gauss", seed=231, n_max=3, flow="rqs")
+NU_RANGE_REJECTING = ("tpcn_nu0p1_n96_d2_mixed", "tpcn_nu0p1_n80_d5_mixed", "tpcn_nu0p1_n128_d10_mixed")
+
+
 def make_funnel(D):
     """Neal's funnel as a likelihood (SURVEY.md 8(d) cfg 5): x0 ~ N(0, 3^2), x_i ~ N(0, e^{x0})."""
     def f(x):
@@ -210,12 +236,15 @@ def find_case(name):
     raise KeyError(name)
 
 
-def build_case(name, scaler_cls):
+def build_case(name, scaler_cls, case=None):
     """Instantiate a case: returns ``(state_dict, function_dict, option_dict, aux)``.
 
     ``scaler_cls`` is the ``Reparameterize`` class to use (the reference's when
-    generating goldens, the oracle's / the product's in tests)."""
-    c = find_case(name)
+    generating goldens, the oracle's / the product's in tests).  ``case``: a case
+    dict that is in none of the tables (``name`` is then a label only); its optional
+    ``geometry`` (``t_mean, t_cov, t_nu, normal_cov``: a fitted ``Geometry``) replaces
+    the seeded one."""
+    c = find_case(name) if case is None else case
     N, D = c["N"], c["D"]
     rng = np.random.default_rng(1000 + c["seed"])
     prior = {"uniform": lambda: UniformPrior(-10.0, 10.0, D),
@@ -239,7 +268,7 @@ def build_case(name, scaler_cls):
     A = rng.normal(size=(D, D)) * 0.3
     cov = np.eye(D) * 1.3 + A @ A.T
     mean = rng.normal(size=D) * 0.2
-    geo = Geo(mean, cov, c["nu"], cov * 0.8)
+    geo = c["geometry"] if "geometry" in c else Geo(mean, cov, c["nu"], cov * 0.8)
     state = dict(u=u, x=x, logdetj=logdetj, logl=logl, logp=logp, beta=c["beta"], blobs=None)
     funcs = dict(loglike=lambda xx: (target(xx), None), logprior=prior.logpdf, scaler=scaler,
                  flow=None, theta_geometry=geo, u_geometry=geo)

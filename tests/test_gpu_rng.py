@@ -38,8 +38,9 @@ def fill(seed, step, offset, n, D, gamma_shape=0.0, want_uniform=True):
 
 
 # shape = (D + nu) / 2 (mcmc.py:80): D=32, nu=5 (bench) -> 18.5; nu clamped to 1e6 (geometry.py:58-59) -> 500016;
-# D=2, nu=1 -> 1.5; below one (Marsaglia-Tsang boost branch) 0.5 -- not reachable from mcmc.py (D >= 2), kept honest
-@pytest.mark.parametrize("shape", [18.5, 500016.0, 1.5, 21.0, 0.5])
+# D=2, nu=1 -> 1.5; below one (Marsaglia-Tsang boost branch) 0.5 -- not reachable from mcmc.py (D >= 2), kept honest;
+# the ends of a Student-t EM fit's nu (Geometry(student="em")): D=2 and D=5 at the lower clamp 0.1 -> 1.05, 2.55; D=10 at 1e4 -> 5005
+@pytest.mark.parametrize("shape", [18.5, 500016.0, 1.5, 21.0, 0.5, 1.05, 2.55, 5005.0])
 def test_gamma_draws_follow_the_gamma_law(shape):
     _, g, _ = fill(seed=20240928, step=3, offset=0, n=N, D=2, gamma_shape=shape)
     assert np.isfinite(g).all() and (g > 0).all()
