@@ -44,7 +44,8 @@ const char* pmc_build_id(void);
  * the host side (pocomc_amd/maf_spec.py) and filled by pmc_maf_pack(). */
 typedef struct pmc_maf {
     const float* packed;      /* packed weights, T * pk_per_transform floats */
-    const int32_t* meta;      /* [8 hdr][T*D feat_of_rank][T*D rank_of_feat][nQ quad meta] */
+    const int32_t* meta;      /* [8 hdr][T*D feat_of_rank][T*D rank_of_feat][nQ quad meta]; with PMC_MAF_TABLES: 16-byte aligned,
+                               * [zeros up to a multiple of 4 words][the two-wave affine sweep's tables] behind them */
     int32_t D, H, T;          /* features, hidden width, transforms */
     int32_t Hp, Dp;           /* padded hidden slots / ranks (multiples of 16) */
     int32_t nT, nXT, nOT;     /* hidden, input and output tiles */
@@ -56,11 +57,23 @@ typedef struct pmc_maf {
                                * operands and float32 accumulation -- an opt-in precision, see PMC_INVERSE_TRIANGULAR_LANE16 */
     int32_t lane16_fmt;       /* 1 bfloat16, 2 float16 (0: no image) */
     int32_t reserved;         /* 0, or PMC_MAF_VARIANT_* bits: schedule variants of the inverse sweeps that must agree with
-                               * the default bit for bit (the cross-checks of tests/test_gpu_flow.py) */
+                               * the default bit for bit (the cross-checks of tests/test_gpu_flow.py); PMC_MAF_TABLES */
 } pmc_maf_t;
 
 #define PMC_MAF_VARIANT_LEFT_LOOKING 1  /* two-wave spline sweep: the burst wave forms no output partials ahead of time */
 #define PMC_MAF_VARIANT_LANE_FOUR 2     /* lane-per-walker sweep of a flow of >= 16 hidden tiles: no fifth wavefront */
+/* meta carries the constant tables of the two-wave affine sweep (D <= 64) in the layout of the kernel's LDS, so that a
+ * workgroup copies them instead of deriving them from the quad meta words and the rank maps on every launch:
+ *   DGT [nT+2][16]  per hidden tile (two rows of "no groups" behind the last): words 0..3 the ranks its four degree groups
+ *                   produce (D: no group; word 0 also carries the quad pattern << 16), 4..7 the byte offset of each rank's
+ *                   x / y word (walker 0), 8..11 of its (shift, raw) pair in a staged output tile, 12..15 of its two rows in
+ *                   an output fragment record (0x40000000 for no group)
+ *   PRM [Dp]        feature of every rank of transform 0
+ *   YT  [T][nT+2][4]  byte offset of the y word of the rank a group produces in the x array of transform t + 1 (by that
+ *                   transform's ranks; the last transform: its own rank)
+ *   Y0T [T]         the same for rank 0; zeros up to a multiple of 4 words
+ * pocomc_amd/maf_spec.py (MAFSpec.sweep_tables) builds them.  Without the bit the kernel builds the same words itself. */
+#define PMC_MAF_TABLES 4
 
 #define PMC_INVERSE_AUTO 0
 #define PMC_INVERSE_TRIANGULAR 1   /* one sweep over the degree groups */
@@ -614,6 +627,13 @@ int pmc_propose_inverse(int kind, const float* cur32, const double* mu, const do
 
 /* mcmc.py:77-102 in one call: [H2D mu] -> propose -> flow inverse -> scaler inverse -> D2H x', finite. */
 int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream);
+/* pmc_step_pre in two parts, for a caller that enqueues the pre-steps of several row ranges back to back (pmc_pipeline
+ * does): pmc_step_pre_deferred is pmc_step_pre without the variates of step rng->step + 1 (pmc_step_t.rng_normal), which
+ * pmc_step_fill_next enqueues (and notes in *rng_ready) -- behind the last range's pre-step, so that no range's x' waits
+ * behind another range's fill.  pmc_step_fill_next does nothing when the step draws inline.  Every pmc_step_pre_deferred
+ * needs its pmc_step_fill_next before the same range's pmc_step_post. */
+int pmc_step_pre_deferred(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream);
+int pmc_step_fill_next(const pmc_step_t* s, const pmc_rng_t* rng, double nu, void* stream);
 /* mcmc.py:124-156 in one call: H2D logl', logp' -> accept + reductions -> [D2H sums, accept mask]. */
 int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask,
                   int copy_sums, void* stream);

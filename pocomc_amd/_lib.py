@@ -155,6 +155,8 @@ SIGNATURES = {
     "pmc_propose_inverse": (C.c_int, [C.c_int, c_p, c_p, c_p, c_p, f64, f64, f64, P(pmc_rng_t), c_p, c_p, c_p,
                                       P(pmc_maf_t), c_p, c_p, i64, c_p]),
     "pmc_step_pre": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, f64, c_p]),
+    "pmc_step_pre_deferred": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, f64, c_p]),
+    "pmc_step_fill_next": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, c_p]),
     "pmc_step_post": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, C.c_int, C.c_int, c_p]),
     "pmc_step_lik_rows": (C.c_int, [P(pmc_step_t), c_p]),
     "pmc_step_prior_rows": (C.c_int, [P(pmc_step_t), c_p, C.c_int, c_p]),

@@ -646,8 +646,25 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
         F.so[0] = tso.x; F.so[1] = tso.y; F.so[2] = tso.z; F.so[3] = tso.w;
     };
 
+    // The tables depend on the flow's shape alone.  PMC_MAF_TABLES: the host built them once, behind the quad meta words
+    // (maf_spec.py: sweep_tables, the arithmetic of fill_table and of the YT loop below) -- the chain wave takes the first
+    // tile's words straight from that image, so that its fragment requests leave at once, and the burst wave, which waits
+    // for the proposal anyway, copies the image into LDS.  Without the bit the chain wave builds them as before.
+    const bool tabs = (m.reserved & PMC_MAF_TABLES) != 0;
+    const int* tabg = m.meta + ((8 + 2 * T * D + 4 * nT + 3) & ~3);
+    const int tab_words = TRI5_TT_WORDS(&m) + Dp;               // DGT | PRM (a multiple of 16); YT | Y0T follow
     ChainFrags<MAXO> fA, fB;
-    if (wv < TRI5_NC) {
+    if (wv < TRI5_NC && tabs) {
+        const int4* tg4 = reinterpret_cast<const int4*>(tabg);
+        const int4 ty = *reinterpret_cast<const int4*>(tabg + tab_words + ((T - 1) * (nT + 2)) * 4);
+        const int4 tg = tg4[0], txy = tg4[1], tso = tg4[2], w0 = tg4[3], w1 = tg4[4 + 3];
+        fA.yo[0] = ty.x; fA.yo[1] = ty.y; fA.yo[2] = ty.z; fA.yo[3] = ty.w;
+        fA.g[0] = tg.x & 0xffff; fA.g[1] = tg.y; fA.g[2] = tg.z; fA.g[3] = tg.w;
+        fA.pat = tg.x >> 16;
+        fA.xy[0] = txy.x; fA.xy[1] = txy.y; fA.xy[2] = txy.z; fA.xy[3] = txy.w;
+        fA.so[0] = tso.x; fA.so[1] = tso.y; fA.so[2] = tso.z; fA.so[3] = tso.w;
+        static_for<16>([&](auto k_) { request(fA, k_, T - 1, 0, w0, w1); });
+    } else if (wv < TRI5_NC) {
         // the first tile's operands are on their way while the walkers are proposed / loaded
         fill_table();
         WAVE_LDS_FENCE();
@@ -669,6 +686,8 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
             take_table(fA, T - 1, 0);
             static_for<16>([&](auto k_) { request(fA, k_, T - 1, 0, w0, w1); });
         }
+    }
+    if (wv < TRI5_NC) {
         if constexpr (FM > 0) {
             for (int e = lane; e < (Dp - D) * 16; e += 64) Y[lidx(D + (e >> 4), e & 15)] = 0.0f;
             const double sg = pa.adapt ? pa.adapt[0] : pa.sigma, ca = pa.adapt ? pa.adapt[1] : pa.cn_a;
@@ -683,14 +702,27 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
         float4* z4 = reinterpret_cast<float4*>(H0);
         const int n4 = (2 * Hp * 16 + 2 * 256 + 2 * TRI5_STAGE_FLOATS(MAXO)) >> 2;
         for (int e = lane; e < n4; e += 64) z4[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tabs) {
+            const int4* src = reinterpret_cast<const int4*>(tabg);
+            for (int e = lane; e < tab_words >> 2; e += 64) reinterpret_cast<int4*>(DGT)[e] = src[e];
+            src = reinterpret_cast<const int4*>(tabg + tab_words);
+            for (int e = lane; e < (TRI5_YT_WORDS(&m) + 3) >> 2; e += 64) reinterpret_cast<int4*>(YT)[e] = src[e];
+            for (int tt = lane; tt < T; tt += 64) {
+                const float* b3 = m.packed + (size_t)tt * m.pk_per_transform + (oB3 >> 2);
+                B3T[2 * tt] = b3[0];
+                B3T[2 * tt + 1] = b3[1];
+            }
+        }
     }
     if (pa.prof && lane == 0 && blockIdx.x < 64)         // (measurement only: which SIMD / CU every wavefront landed on)
         pa.prof[(size_t)T * nT * 8 + blockIdx.x * 2 + wv] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-    for (int r = threadIdx.x; r < D; r += 64 * (TRI5_NC + 1)) PRM[r] = feat_of_rank[r];      // (the last transform's x is stored by feature)
-    for (int tt = threadIdx.x; tt < T; tt += 64 * (TRI5_NC + 1)) {
-        const float* b3 = m.packed + (size_t)tt * m.pk_per_transform + (oB3 >> 2);
-        B3T[2 * tt] = b3[0];
-        B3T[2 * tt + 1] = b3[1];
+    if (!tabs) {
+        for (int r = threadIdx.x; r < D; r += 64 * (TRI5_NC + 1)) PRM[r] = feat_of_rank[r];      // (the last transform's x is stored by feature)
+        for (int tt = threadIdx.x; tt < T; tt += 64 * (TRI5_NC + 1)) {
+            const float* b3 = m.packed + (size_t)tt * m.pk_per_transform + (oB3 >> 2);
+            B3T[2 * tt] = b3[0];
+            B3T[2 * tt + 1] = b3[1];
+        }
     }
     for (int e = threadIdx.x; e < (Dp * 16) >> 2; e += 64 * (TRI5_NC + 1)) {      // both x arrays start zeroed
         reinterpret_cast<float4*>(XA)[e] = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -196,36 +196,74 @@ __device__ __forceinline__ void scaler_epilogue_rows(const ScalerEpi& e, const d
                                                      bool cm_done) {
     const pmc_scaler_t& s = e.s;
     const int rows = (int)min((int64_t)16, n - row0);
-    if (tid < rows) {
-        double l = np_pairwise_sum(Jt + (size_t)tid * D, D);
-        if (s.scale) l = s.sum_log_sigma + l;
-        e.ldj_out[row0 + tid] = l;
-        const int fin = (rowfin[tid] && isfinite(l)) ? 1 : 0;
-        e.finite_out[row0 + tid] = fin;
-        if (e.finite_copy) e.finite_copy[row0 + tid] = fin;
-        bool clean = fin != 0;
-        if (e.have_prior) {
-            // Prior.logpdf of the finite rows (mcmc.py:105-107): the terms dimension after dimension
-            double lp = -INFINITY;
-            if (fin) {
-                lp = 0.0;
-                for (int j = 0; j < D; ++j) lp += Pt[tid * D + j];
-            }
-            e.logp_out[row0 + tid] = lp;
-            if (e.logp_copy) e.logp_copy[row0 + tid] = lp;
-            clean = clean && isfinite(lp);
+    // Eight lanes per walker (nthr = 128: all 16 walkers at once; 64: two passes).  Lane i of a walker's group keeps numpy's
+    // accumulator r_i of the pairwise sum (np_pairwise_leaf: a[i], a[i+8], ... in index order), the group combines them in
+    // numpy's tree ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and lane 0 adds the tail: the bits of np_pairwise_sum for D <= 128.
+    // Prior.logpdf's sum is sequential by definition: lane 4 walks it, its terms loaded eight at a time ahead of the adds.
+    const int n8 = D - (D % 8);
+    for (int rb = 0; rb < 16; rb += nthr >> 3) {
+        const int r = rb + (tid >> 3), i = tid & 7;
+        const bool live = r < rows;
+        const double* a = Jt + (size_t)r * D;
+        double acc = 0.0;
+        if (live && D >= 8) {
+            acc = a[i];
+            for (int k = i + 8; k < n8; k += 8) acc += a[k];
         }
-        if (e.bad_count && !clean) atomicAdd(e.bad_count, 1u);            // (rows that the host's masks would drop: rare)
-        if (e.fill_x) rowfin[tid] = clean ? 1 : 0;                              // (from here on: "the row reaches the likelihood")
+        double lps = 0.0;
+        if (live && e.have_prior && i == 4) {
+            const double* P = Pt + (size_t)r * D;
+            int j = 0;
+            for (; j + 8 <= D; j += 8) {
+                const double p0 = P[j], p1 = P[j + 1], p2 = P[j + 2], p3 = P[j + 3];
+                const double p4 = P[j + 4], p5 = P[j + 5], p6 = P[j + 6], p7 = P[j + 7];
+                lps += p0; lps += p1; lps += p2; lps += p3; lps += p4; lps += p5; lps += p6; lps += p7;
+            }
+            for (; j < D; ++j) lps += P[j];
+        }
+        // (every lane of the wavefront takes part in the exchanges; lane 0 of a group ends with numpy's operand order)
+        acc = acc + __shfl_xor(acc, 1, 8);
+        acc = acc + __shfl_xor(acc, 2, 8);
+        acc = acc + __shfl_xor(acc, 4, 8);
+        lps = __shfl(lps, 4, 8);
+        if (live && i == 0) {
+            double l;
+            if (D < 8) {
+                l = 0.0;
+                for (int k = 0; k < D; ++k) l += a[k];
+            } else {
+                l = acc;
+                for (int k = n8; k < D; ++k) l += a[k];
+            }
+            if (s.scale) l = s.sum_log_sigma + l;
+            e.ldj_out[row0 + r] = l;
+            const int fin = (rowfin[r] && isfinite(l)) ? 1 : 0;
+            e.finite_out[row0 + r] = fin;
+            if (e.finite_copy) e.finite_copy[row0 + r] = fin;
+            bool clean = fin != 0;
+            if (e.have_prior) {
+                // Prior.logpdf of the finite rows (mcmc.py:105-107): the terms dimension after dimension
+                const double lp = fin ? lps : -INFINITY;
+                e.logp_out[row0 + r] = lp;
+                if (e.logp_copy) e.logp_copy[row0 + r] = lp;
+                clean = clean && isfinite(lp);
+            }
+            if (e.bad_count && !clean) atomicAdd(e.bad_count, 1u);            // (rows that the host's masks would drop: rare)
+            if (e.fill_x) rowfin[r] = clean ? 1 : 0;                                // (from here on: "the row reaches the likelihood")
+        }
     }
     if (e.fill_x) __syncthreads();
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 2] = wall_clock64();
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 3] = wall_clock64();
     if (e.x_colmajor && !cm_done) {
+        // element el = j * rows + r; (j, r) step by nthr = dj * rows + dr without a division per element
+        const int dj = nthr / rows, dr = nthr - dj * rows;
+        int j = tid / rows, r = tid - j * rows;
         for (int el = tid; el < rows * D; el += nthr) {
-            const int j = el / rows, r = el - j * rows;
             // (a row that does not reach the likelihood: the walker's current x in the host copy, see scaler_inverse_kernel)
             e.x_colmajor[(size_t)j * n + row0 + r] = (e.fill_x && !rowfin[r]) ? e.fill_x[(row0 + r) * D + j] : Xt[j * 17 + r];
+            j += dj; r += dr;
+            if (r >= rows) { r -= rows; ++j; }
         }
     }
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 4] = wall_clock64();
@@ -266,9 +304,14 @@ __device__ __forceinline__ void scaler_epilogue(const ScalerEpi& e, const float*
     if (tid < 16) rowfin[tid] = 1;
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 0] = wall_clock64();
     __syncthreads();
-    for (int el = tid; el < rows * D; el += nthr) {
-        const int r = el / D, j = el - r * D;
-        scaler_epilogue_element(e, Jt, Pt, Xt, rowfin, X[lidx_of(rof[j], r)], r, j, row0, n, D, false);
+    {   // element el = r * D + j; (r, j) step by nthr = dr * D + dj without a division per element
+        const int dr = nthr / D, dj = nthr - dr * D;
+        int r = tid / D, j = tid - r * D;
+        for (int el = tid; el < rows * D; el += nthr) {
+            scaler_epilogue_element(e, Jt, Pt, Xt, rowfin, X[lidx_of(rof[j], r)], r, j, row0, n, D, false);
+            r += dr; j += dj;
+            if (j >= D) { j -= D; ++r; }
+        }
     }
     __syncthreads();
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 1] = wall_clock64();

@@ -22,8 +22,29 @@ static long long* g_epilogue_stamps = nullptr;       // pmc_debug_set_epilogue_s
 static int64_t g_epilogue_stamps_n = 0;
 #endif
 
-extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a,
-                            void* stream) {
+// the variates of step rng->step + 1 into the other parity's buffers (throughput mode, see pmc_step_t.rng_normal)
+static bool step_prefills(const pmc_step_t* s, const pmc_rng_t* rng) {
+    return s->rng_ready && s->rng_normal[0] && s->rng_normal[1] && s->rng_uniform[0] && s->rng_uniform[1] &&
+           (s->kind != PMC_KIND_TPCN || (s->rng_gamma[0] && s->rng_gamma[1])) && !rng->normal && !rng->gamma && !rng->uniform;
+}
+
+extern "C" int pmc_step_fill_next(const pmc_step_t* s, const pmc_rng_t* rng, double nu, void* stream) {
+    if (!s || !rng) return pmc_fail("pmc_step_fill_next: null argument");
+    if (!step_prefills(s, rng)) return 0;
+    const int rb = (int)(rng->step & 1);
+    const double gshape = (s->kind == PMC_KIND_TPCN) ? 0.5 * ((double)s->D + nu) : 0.0;      // mcmc.py:80
+    pmc_rng_t nx = *rng;
+    nx.step = rng->step + 1;
+    int rcf = pmc_rng_fill(&nx, gshape, s->rng_normal[rb ^ 1], s->rng_gamma[rb ^ 1], s->rng_uniform[rb ^ 1], s->n, s->D, stream);
+    if (rcf) return rcf;
+    *s->rng_ready = (int64_t)nx.step;
+    return 0;
+}
+
+// fill_next = false: the caller enqueues pmc_step_fill_next itself, behind whatever the host waits for first (the pipeline:
+// behind the last lane's pre-step)
+static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream,
+                    bool fill_next) {
     if (!s || !rng) return pmc_fail("pmc_step_pre: null argument");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = s->n;
@@ -31,9 +52,8 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
     const bool tpcn = (s->kind == PMC_KIND_TPCN);
     // throughput mode: this step's Philox variates were drawn ahead of time (see pmc_step_t.rng_normal)
     pmc_rng_t rr = *rng;
-    const bool prefill = s->rng_ready && s->rng_normal[0] && s->rng_normal[1] && s->rng_uniform[0] &&
-                         s->rng_uniform[1] && (!tpcn || (s->rng_gamma[0] && s->rng_gamma[1])) && !rng->normal &&
-                         !rng->gamma && !rng->uniform;
+    const bool prefill = step_prefills(s, rng);
+    const pmc_rng_t* rng_in = rng;
     const int rb = (int)(rng->step & 1);
     const double gshape = tpcn ? 0.5 * ((double)D + nu) : 0.0;             // mcmc.py:80
     if (prefill) {
@@ -48,15 +68,7 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
     // what follows the last kernel whose results the host waits for
     auto finish = [&]() -> int {
         if (s->ev_pre_done) (void)hipEventRecord((hipEvent_t)s->ev_pre_done, st);
-        if (prefill) {
-            pmc_rng_t nx = *rng;
-            nx.normal = nullptr; nx.gamma = nullptr; nx.uniform = nullptr;
-            nx.step = rng->step + 1;
-            int rcf = pmc_rng_fill(&nx, gshape, s->rng_normal[rb ^ 1], s->rng_gamma[rb ^ 1], s->rng_uniform[rb ^ 1], n, D,
-                                   stream);
-            if (rcf) return rcf;
-            *s->rng_ready = (int64_t)nx.step;
-        }
+        if (prefill && fill_next) return pmc_step_fill_next(s, rng_in, nu, stream);
         return 0;
     };
     // host_direct: the kernels read mu from / write x', finite, logp' to pinned host memory themselves
@@ -167,6 +179,16 @@ extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu
         hipMemcpyAsync(s->h_fin, s->p_fin, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess)
         return pmc_fail("pmc_step_pre: D2H");
     return finish();
+}
+
+extern "C" int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a,
+                            void* stream) {
+    return step_pre(s, rng, nu, sigma, cn_a, stream, true);
+}
+
+extern "C" int pmc_step_pre_deferred(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a,
+                                     void* stream) {
+    return step_pre(s, rng, nu, sigma, cn_a, stream, false);
 }
 
 // A device likelihood's input behind a host prior (pmc_step_lik_rows): one thread per walker, x' or the current x of its
@@ -444,10 +466,16 @@ static int pipeline_enqueue_pre(pmc_pipeline* p, int64_t step, double nu) {
         pmc_step_t s = *p->lanes[k];
         s.adapt_mode = 1;                                   // (pre: any non-zero mode = read sigma, cn_a, mu from adapt_state)
         p->rng[k].step = (uint64_t)step;
-        const int rc = pmc_step_pre(&s, &p->rng[k], nu, 0.0, 0.0, p->stream);
+        const int rc = step_pre(&s, &p->rng[k], nu, 0.0, 0.0, p->stream, false);
         if (rc) return rc;
         if (p->prefetcher)                                  // helper threads read x' once as soon as its completion word shows up
             (void)pmc_prefetcher_submit(p->prefetcher, s.h_done, step + 1, s.h_x, (int64_t)s.n * s.D * 8, p->timeout > 0 ? p->timeout : 1.0);
+    }
+    // the variates of step + 1 behind the LAST lane's pre-step: they write the other parity's buffers, nothing reads them
+    // before the next step, and no lane's x' waits behind another lane's fill
+    for (int k = 0; k < p->n_lanes; ++k) {
+        const int rc = pmc_step_fill_next(p->lanes[k], &p->rng[k], nu, p->stream);
+        if (rc) return rc;
     }
     return 0;
 }

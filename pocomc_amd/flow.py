@@ -24,6 +24,8 @@ import torch
 from . import _lib
 from .maf_spec import MAFSpec, SPEC_BY_NAME, NSF_BY_NAME, spec_by_name
 
+PMC_MAF_TABLES = 4             # pmc_maf_t.reserved: the metadata carries the two-wave affine sweep's table image
+
 
 def torch_double_to_float(x: torch.Tensor, warn: bool = True) -> torch.Tensor:
     """``pocomc/tools.py:295-316``."""
@@ -97,7 +99,8 @@ class Flow:
             packed=self._packed.data_ptr(), meta=self._meta.data_ptr(),
             D=spec.n_dim, H=spec.hidden, T=spec.n_transforms, Hp=spec.Hp, Dp=spec.Dp,
             nT=spec.nT, nXT=spec.nXT, nOT=spec.nOT, pk_per_transform=spec.pk_per_transform,
-            tri_ok=int(spec.tri_ok), n_out=spec.n_out)
+            tri_ok=int(spec.tri_ok), n_out=spec.n_out,
+            reserved=PMC_MAF_TABLES if spec.has_sweep_tables else 0)
         self.inverse_algo = 0          # PMC_INVERSE_AUTO
         if precision not in ("f32", "bf16"):
             raise ValueError("precision must be 'f32' or 'bf16'")

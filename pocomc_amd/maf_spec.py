@@ -401,6 +401,72 @@ class MAFSpec:
             out.append(g)
         return out
 
+    @property
+    def has_sweep_tables(self) -> bool:
+        """The flows the two-wave affine sweep (``csrc/maf_inverse_tri4.hip``: ``maf_inverse_tri5_kernel``) covers: their
+        metadata carries the sweep's table image (:meth:`sweep_tables`)."""
+        return bool(self.n_out == 2 and self.tri_ok and self.nOT <= 8 and self.n_dim <= 64)
+
+    def sweep_tables(self) -> np.ndarray:
+        """The constant tables of the two-wave affine sweep in the layout of its LDS, so that a workgroup copies them instead
+        of deriving them (``pmc_maf_t.reserved & PMC_MAF_TABLES``; the kernel's own construction -- ``fill_table`` and the
+        ``YT`` loop, the same integer arithmetic -- stays for an image without them):
+
+        ``DGT [(nT+2)][16]``  per hidden tile (two rows of "no groups" behind the last): the ranks its four degree groups
+                              produce (word 0 also: the quad pattern << 16), the byte offsets of each rank's x / y word, of
+                              its (shift, raw) pair in a staged output tile and of its two rows in an output fragment record
+        ``PRM [Dp]``          feature of every rank of transform 0
+        ``YT  [T][nT+2][4]``  byte offset of the y word of the rank a group produces, in the x array of transform t + 1
+        ``Y0T [T]``           the same for rank 0; zeros up to a multiple of 4 words
+        """
+        D, T, nT, Dp = self.n_dim, self.n_transforms, self.nT, self.Dp
+        oob = 0x40000000
+        f_o_r = [np.argsort(o) for o in self.orders]
+        r_o_f = self.orders
+        deg = (self.quad_meta & 0xffff).astype(np.int64)
+        dgt = np.zeros((nT + 2, 16), dtype=np.int64)
+        for tile in range(nT + 2):
+            g4, pat = [D] * 4, 1
+            if tile < nT:
+                x, y, z, w = (int(v) for v in deg[4 * tile:4 * tile + 4])
+                ny, nz, nw = y != x, z != y, w != z
+                pat = 1 | (ny << 1) | (nz << 2) | (nw << 3)
+                g1 = y if ny else (z if nz else (w if nw else D))
+                g2 = (z if nz else (w if nw else D)) if ny else (w if (nz and nw) else D)
+                g3 = w if (ny and nz and nw) else D
+                g4 = [x, g1, g2, g3]
+            for k in range(16):
+                i = k & 3
+                g = g4[i]
+                live = g < D
+                gg = g if live else 0
+                if k < 4:
+                    v = g | ((pat << 16) if i == 0 else 0)
+                elif k < 8:
+                    v = 4 * (((gg >> 4) << 8) + ((gg & 3) << 6) + ((gg >> 2) & 3))
+                elif k < 12:
+                    v = 4 * ((gg >> 3) * 256 + 2 * (gg & 7))
+                else:
+                    v = (((((gg >> 3) * nT) << 6) + 2 * (gg & 7)) << 4) if live else oob
+                dgt[tile, k] = v
+        woff = lambda r: 4 * (((r >> 4) << 8) + ((r & 3) << 6) + ((r >> 2) & 3))
+
+        def src_rank(tt, g):                              # where rank g of transform tt sits in its input array
+            if g >= D:
+                return 0
+            return g if tt == T - 1 else int(r_o_f[tt + 1][f_o_r[tt][g]])
+        yt = np.zeros((T, nT + 2, 4), dtype=np.int64)
+        for tt in range(T):
+            for tile in range(nT + 2):
+                for i in range(4):
+                    yt[tt, tile, i] = woff(src_rank(tt, int(dgt[tile, i]) & 0xffff))
+        y0t = np.array([woff(src_rank(tt, 0)) for tt in range(T)], dtype=np.int64)
+        prm = np.zeros(Dp, dtype=np.int64)
+        prm[:D] = f_o_r[0]
+        tail = np.concatenate([yt.reshape(-1), y0t])
+        tail = np.concatenate([tail, np.zeros(-len(tail) % 4, dtype=np.int64)])
+        return np.concatenate([dgt.reshape(-1), prm, tail]).astype(np.int32)
+
     def device_meta(self) -> np.ndarray:
         """int32 metadata consumed by the kernels.
 
@@ -408,6 +474,7 @@ class MAFSpec:
         ``[8:8+T*D]``        feature index of every rank, per transform
         ``[8+T*D:8+2*T*D]``  rank of every feature, per transform
         ``[8+2*T*D: +nQ]``   quad meta words (degree | last<<16), shared by all transforms
+        behind them, from the next multiple of 4 words: :meth:`sweep_tables` (``has_sweep_tables``)
         """
         D, T = self.n_dim, self.n_transforms
         live = int(np.sum((self.quad_deg.reshape(-1, 4) < D).any(axis=1)))      # hidden tiles with a degree group (the padding tiles trail)
@@ -415,7 +482,10 @@ class MAFSpec:
                         self.pk_per_transform, live], dtype=np.int32)
         f_o_r = np.concatenate([np.argsort(o) for o in self.orders]).astype(np.int32)
         r_o_f = np.concatenate(self.orders).astype(np.int32)
-        return np.concatenate([hdr, f_o_r, r_o_f, self.quad_meta]).astype(np.int32)
+        meta = np.concatenate([hdr, f_o_r, r_o_f, self.quad_meta]).astype(np.int32)
+        if self.has_sweep_tables:
+            meta = np.concatenate([meta, np.zeros(-len(meta) % 4, dtype=np.int32), self.sweep_tables()])
+        return meta
 
     # ------------------------------------------------------- bf16 forward image
     def bf16_layout(self):

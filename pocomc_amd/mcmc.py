@@ -678,10 +678,11 @@ class StepEngine:
         self._step.adapt_state = self.adapt_state.data_ptr()
         self.device_adapt = True
 
-    def propose(self, sigma, nu=0.0, replay=None, step=None):
+    def propose(self, sigma, nu=0.0, replay=None, step=None, defer_fill=False):
         """propose -> flow inverse -> scaler inverse (-> prior), x' on its way to the host: one ``pmc_step_pre``.
         ``step``: the step number the launch belongs to when it is enqueued ahead of time
-        (``LanedEngine.step_pipelined``), default: the current one."""
+        (``LanedEngine.step_pipelined``), default: the current one.  ``defer_fill``: leave the next step's variates to
+        :meth:`fill_next`, which the caller enqueues behind the last lane's pre-step."""
         if self._instrumented():
             return self._propose_instrumented(sigma, nu, replay)
         if replay is not None:
@@ -696,12 +697,19 @@ class StepEngine:
         else:
             cn_a = float((1.0 - sigma ** 2.0) ** 0.5) if self.tpcn else 0.0    # mcmc.py:85
         self._stream = self.stream.cuda_stream if self.stream is not None else _lib.stream_handle()
-        _lib.check(self.lib.pmc_step_pre(C.byref(self._step), C.byref(self._rng_cur), float(nu), float(sigma), cn_a,
-                                         self._stream), "pmc_step_pre")
+        pre = self.lib.pmc_step_pre_deferred if defer_fill else self.lib.pmc_step_pre
+        _lib.check(pre(C.byref(self._step), C.byref(self._rng_cur), float(nu), float(sigma), cn_a, self._stream), "pmc_step_pre")
         if self.prefetcher is not None and self._direct_now:
             # helper threads read x' once as soon as the completion word of this pre-step shows up
             self.lib.pmc_prefetcher_submit(self.prefetcher, self.h_done.data_ptr(), int(self._rng_cur.step) + 1,
                                            self.h_x.data_ptr(), self.n * self.D * 8, self.wait_timeout)
+
+    def fill_next(self, nu=0.0):
+        """The variates of the step after the one just proposed with ``defer_fill`` (``pmc_step_fill_next``)."""
+        if self._instrumented():                     # (one launch per stage: those draw inline)
+            return
+        _lib.check(self.lib.pmc_step_fill_next(C.byref(self._step), C.byref(self._rng_cur), float(nu), self._stream),
+                   "pmc_step_fill_next")
 
     def _propose_instrumented(self, sigma, nu, replay):
         """:meth:`propose` as one launch per stage, HIP events between them (``_cur_ev``), then the copies of x', the finite
@@ -1124,9 +1132,16 @@ class LanedEngine:
                 _lib.check(self.lib.pmc_pipeline_set_comm(self._pipe, comm), "pmc_pipeline_set_comm")
             _lib.check(self.lib.pmc_pipeline_start(self._pipe, float(nu), int(first.step_idx)), "pmc_pipeline_start")
             return
+        self._propose_lanes(nu)
+
+    def _propose_lanes(self, nu, ahead=0):
+        """The pre-steps of all lanes, then the lanes' variates of the step after (the order of the C pipeline: no lane's
+        x' waits behind another lane's fill)."""
         for e in self.lanes:
             e.host_timers = self.host_timers
-            e.propose(None, nu)
+            e.propose(None, nu, step=e.step_idx + ahead, defer_fill=True)
+        for e in self.lanes:
+            e.fill_next(nu)
 
     def resume_pipeline(self, nu):
         """Pre-steps of the next step into the queue of a pipeline whose last step enqueued none (``more=False``): what
@@ -1136,9 +1151,7 @@ class LanedEngine:
         if self._pipe:
             _lib.check(self.lib.pmc_pipeline_start(self._pipe, float(nu), int(first.step_idx)), "pmc_pipeline_start")
             return
-        for e in self.lanes:
-            e.host_timers = self.host_timers
-            e.propose(None, nu, step=e.step_idx)
+        self._propose_lanes(nu)
 
     def pipeline_stats(self, reset=True):
         """Host seconds the C pipeline spent {waiting for x', waiting for the sums, enqueuing accepts, enqueuing
@@ -1210,8 +1223,7 @@ class LanedEngine:
                                             c_mu, cap, float(n_total), C.byref(done), stream), "pmc_adapt_update")
         t1 = clock() if tm is not None else 0.0
         if more:
-            for e in self.lanes:
-                e.propose(None, nu, step=e.step_idx + 1)
+            self._propose_lanes(nu, ahead=1)
         t2 = clock() if tm is not None else 0.0
         if sharded:
             _lib.check(lib.pmc_wait_flag(self._h_flag.data_ptr(), self._flag_value, self.lanes[0].wait_timeout), "pmc_wait_flag")
