@@ -305,7 +305,10 @@ typedef struct pmc_scaler {
  * u_out f64 [n][D] (u', re-derived from x' when boundary conditions apply), x f64 [n][D],
  * logdetj f64 [n], finite int32 [n] (1 = logdetj and every x finite).
  * x_colmajor: optional second copy of x as f64 [D][n] (what the host likelihood reads as an (n, D)
- * Fortran-ordered array: numpy's inner loops then run over n instead of over D), or NULL. */
+ * Fortran-ordered array: numpy's inner loops then run over n instead of over D), or NULL.
+ * Width limit: a block keeps the Jacobian terms of its 64 rows in LDS (64 * D * 8 + 256 bytes of 160 KiB): D <= 319;
+ * with x_colmajor (or the fused prior of pmc_scaler_inverse_prior) x' stays there as well (another D * 65 * 8 bytes):
+ * D <= 158.  A wider call fails with "n_dim too large" before anything is launched or written. */
 int pmc_scaler_inverse(const pmc_scaler_t* s, const float* u_in, const double* u_in64, double* u_out,
                        double* x, double* x_colmajor, double* logdetj, int32_t* finite, int64_t n, void* stream);
 
@@ -384,6 +387,7 @@ void pmc_prefetcher_destroy(void* prefetcher);
  * latency-bound kernels; each launch costs ~15-20 us end to end): additionally
  * logp f64 [n] <- Prior.logpdf(x') on the finite rows, -inf elsewhere (mcmc.py:105-107).
  * prior == NULL and logp == NULL: exactly pmc_scaler_inverse.
+ * The fused prior keeps x' in LDS like x_colmajor does: D <= 158 (pmc_scaler_inverse has the arithmetic).
  * finite_copy / logp_copy: optional second destinations.  Together with x_colmajor they may point into
  * PINNED HOST memory (device-accessible, e.g. hipHostMalloc): the kernel then writes what the host
  * callbacks read straight over PCIe while it computes, and no device-to-host copy follows it. */
@@ -416,7 +420,10 @@ typedef struct pmc_rng {
  * Outputs: prop64 f64 [n][D], prop32 f32 [n][D] (what the flow consumes, tools.py:344),
  * quad f64 [n] = diff^T inv_cov diff (current), quad_prop f64 [n] (proposed); the last
  * two may be NULL for RWM.  cn_a = (1 - sigma**2)**0.5, evaluated by the caller exactly as
- * mcmc.py:85 does (ignored for RWM). */
+ * mcmc.py:85 does (ignored for RWM).
+ * Width limit: D <= 128 runs on the f64 matrix cores (instances for D <= 16 / 32 / 64 / 128), 128 < D <= 157 on an
+ * LDS-staged kernel (2 * D * 65 * 8 bytes of 160 KiB); D >= 158 fails with "n_dim too large" before anything is launched
+ * or written. */
 int pmc_propose(int kind, const float* cur32, const double* cur64, const double* mu,
                 const double* inv_cov, const double* chol, double nu, double sigma, double cn_a,
                 const pmc_rng_t* rng, double* prop64, float* prop32, double* quad,
@@ -451,7 +458,9 @@ typedef struct pmc_proposal {
  * kind: PMC_KIND_TPCN adds the Student-t terms -A+B (mcmc.py:124-129); preconditioned != 0 adds the
  * flow log-determinants and moves theta (preconditioned_pcn / preconditioned_rwm), otherwise u is the
  * moved variable (pcn / rwm).
- * alpha_out f64 [n] and accept_out int32 [n] may be NULL.  workspace: pmc_accept_workspace_bytes(). */
+ * alpha_out f64 [n] and accept_out int32 [n] may be NULL.  workspace: pmc_accept_workspace_bytes().
+ * Width limit: none for pmc_accept / pmc_accept_armed (D + 4 > 256 folds the sums in a second pass over the columns);
+ * the device-side adaptation and the sums of other row ranges (pmc_step_t.adapt_*) need D <= 256 and fail above. */
 int64_t pmc_accept_workspace_bytes(int64_t n, int32_t D);
 int pmc_accept(int kind, int preconditioned, pmc_state_t* cur, const pmc_proposal_t* prop, double beta, double nu,
                const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums,

@@ -513,7 +513,9 @@ def test_philox_mode_statistics():
     assert 0.0 <= sums[0] / N <= 1.0
 
 
-@pytest.mark.parametrize("D,N,kind", [(4, 100, 0), (10, 333, 0), (32, 1000, 0), (50, 77, 0), (6, 64, 1)])
+@pytest.mark.parametrize("D,N,kind", [(4, 100, 0), (10, 333, 0), (32, 1000, 0), (50, 77, 0), (6, 64, 1),
+                                      # the edges of the proposal's instances (D <= 16 / 32 / 64) with partial walker sets
+                                      (15, 33, 0), (16, 33, 0), (17, 33, 0), (33, 17, 0), (63, 40, 0), (64, 81, 0), (64, 20, 1)])
 def test_fused_proposal_and_inverse_equal_the_two_launches(D, N, kind):
     """pmc_propose_inverse (the proposal as prologue of the flow-inverse kernel) gives bit for bit the
     theta', quadratic forms, u' and log-determinant of pmc_propose followed by pmc_maf_inverse."""
