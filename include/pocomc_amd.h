@@ -812,6 +812,25 @@ int pmc_student_em(const double* x, const float* x32, const int64_t* idx, int64_
                    double* sigma_io, double tol, int32_t max_iter, double* result, void* workspace,
                    int64_t workspace_bytes, void* stream);
 
+/* The same fit with a weight per row, w f64 [n] (device), w_r >= 0, not necessarily normalised; rows 0..n-1 (no idx), for
+ * the whole width of the MCMC step.  With P = { r : w_r > 0 }, W = sum_P w_r and pi_r = w_r / W the iteration of
+ * pmc_student_em reads
+ *     f(nu) = [log(nu/2) - psi(nu/2)] - [log((nu+D)/2) - psi((nu+D)/2)] + sum_P pi_r (log w_r - w_r + 1)    (w_r as above)
+ *     Sigma <- sum_P pi_r w_r d_r d_r^T   (no division by n);   mu <- sum_P pi_r w_r x_r / sum_P pi_r w_r
+ * with the same start (nu = 20), bracket, root finder, stop rule and status codes; integer weights give the fit of the
+ * repeated rows.  A row of weight zero is not read beyond its weight: a NaN or inf in it reaches no sum.  One
+ * single-workgroup kernel ahead of the loop forms W, sum w^2, |P| and a bad-weight flag in a fixed order, and the host
+ * reads that record once: a negative, NaN or inf weight, or |P| <= D, fails the call before any EM kernel is launched
+ * (mu_io / sigma_io untouched).  result: HOST f64 [6] <- { nu, iterations, status, host reads = 1 + ceil(iterations / 8),
+ * |P|, the Kish effective sample size W^2 / sum w^2 }.  Fixed-order sums, no atomics: the same bits on every call.
+ * 1 <= D <= PMC_STUDENT_W_MAX_D; above PMC_STUDENT_MAX_D the row pass takes 32 rows per workgroup instead of 64 (140,672
+ * bytes of LDS at D = 157), with the same arithmetic per row.  workspace: pmc_student_em_weighted_workspace_bytes(n, D). */
+#define PMC_STUDENT_W_MAX_D 157
+int64_t pmc_student_em_weighted_workspace_bytes(int64_t n, int32_t D);
+int pmc_student_em_weighted(const double* x, const float* x32, const double* w, int64_t n, int32_t D, double* mu_io,
+                            double* sigma_io, double tol, int32_t max_iter, double* result, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* The full affine map of Reparameterize(diagonal=False), scaler.py:288-292 / :308-313, on rows f64 [n][D]:
  * mode 0: out = mu + M in (M = L: _inverse_affine), mode 1: out = M (in - mu) (M = L^-1: _forward_affine).  in != out. */
 int pmc_affine_rows(const double* M, const double* mu, const double* in, double* out, int64_t n, int32_t D,

@@ -10,6 +10,9 @@
 // All state lives in the workspace; state->done turns every later kernel of the call into a no-op.  It is written by
 // single-workgroup kernels only and read by the kernels behind them: no kernel waits for another.  Every sum has a fixed
 // order (no atomics): the same rows give the same bits on every call and every device.
+// pmc_student_em_weighted runs the same kernels with a weight per row (the WT = true instances): pi_r = w_r / sum w in
+// place of 1 / n in every sum, rows of weight zero never read, em_weights_kernel ahead of the loop; above D = 128 its row
+// pass takes 32 rows per workgroup.  The WT = false instances are the code pmc_student_em ran before the weights came.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -19,12 +22,20 @@
 
 #define EM_CHUNKS 64          // row chunks of the weighted sums (pool.hip: MOM_CHUNKS)
 #define EM_ROWS 64            // rows of one em_delta_kernel workgroup: one wavefront
+#define EM_ROWS_WIDE 32       // the same above PMC_STUDENT_MAX_D (pmc_student_em_weighted): half the substitution vectors
+#define EM_W_THREADS 256
 #define EM_NU_THREADS 1024
 #define EM_HOST_CHUNK 8       // iterations enqueued between two reads of the state
 
 struct EmState {
     double nu, last_nu;
     int32_t iter, status, done, pad;
+};
+
+struct EmWeights {            // em_weights_kernel's record, at byte 128 of the workspace
+    double sum, sum2;         // W = sum of the positive weights, sum of their squares
+    int64_t positive;         // rows with w_r > 0
+    int32_t bad, pad;         // a weight that is negative, NaN or inf
 };
 
 // log(a) - psi(a), a > 0, formed directly: psi(a) = psi(a + 1) - 1/a gives
@@ -41,6 +52,32 @@ __host__ __device__ static inline double log_minus_psi(double a) {
 
 __global__ void em_init_kernel(EmState* __restrict__ st) {
     st->nu = 20.0; st->last_nu = 0.0; st->iter = 0; st->status = PMC_STUDENT_MAX_ITER; st->done = 0; st->pad = 0;
+}
+
+// W, sum w^2, the number of positive weights and the bad-weight flag: one workgroup, thread t takes rows t, t + 256, ...
+// in ascending order, then a tree over the threads
+__global__ __launch_bounds__(EM_W_THREADS) void em_weights_kernel(const double* __restrict__ w, int64_t n, EmWeights* __restrict__ out) {
+    __shared__ double s1[EM_W_THREADS], s2[EM_W_THREADS];
+    __shared__ int64_t cnt[EM_W_THREADS];
+    __shared__ int32_t bad[EM_W_THREADS];
+    double a = 0.0, b = 0.0;
+    int64_t c = 0;
+    int32_t f = 0;
+    for (int64_t r = threadIdx.x; r < n; r += EM_W_THREADS) {
+        const double v = w[r];
+        if (!(v >= 0.0) || !(v < __builtin_inf())) f = 1;
+        else if (v > 0.0) { a += v; b += v * v; c += 1; }
+    }
+    s1[threadIdx.x] = a; s2[threadIdx.x] = b; cnt[threadIdx.x] = c; bad[threadIdx.x] = f;
+    __syncthreads();
+    for (int h = EM_W_THREADS / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            s1[threadIdx.x] += s1[threadIdx.x + h]; s2[threadIdx.x] += s2[threadIdx.x + h];
+            cnt[threadIdx.x] += cnt[threadIdx.x + h]; bad[threadIdx.x] |= bad[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { out->sum = s1[0]; out->sum2 = s2[0]; out->positive = cnt[0]; out->bad = bad[0]; out->pad = 0; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -84,24 +121,26 @@ __global__ __launch_bounds__(256) void em_chol_kernel(const double* __restrict__
 
 // ---------------------------------------------------------------------------------------------------------------
 // delta_r = |L^-1 (x_r - mu)|^2: one lane per row, the factor and mu in LDS (read at the same address by every lane),
-// the lane's substitution vector y in LDS as y[j][lane]
+// the lane's substitution vector y in LDS as y[j][lane].  WT: a row of weight zero is not read, its delta is 0
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(EM_ROWS) void em_delta_kernel(const T* __restrict__ x, const int64_t* __restrict__ idx, int64_t n, int D,
-                                                           const double* __restrict__ mu, const double* __restrict__ Lp,
-                                                           const EmState* __restrict__ st, double* __restrict__ delta) {
+template <typename T, int ROWS, bool WT>
+__global__ __launch_bounds__(ROWS) void em_delta_kernel(const T* __restrict__ x, const int64_t* __restrict__ idx,
+                                                        const double* __restrict__ wts, int64_t n, int D,
+                                                        const double* __restrict__ mu, const double* __restrict__ Lp,
+                                                        const EmState* __restrict__ st, double* __restrict__ delta) {
     extern __shared__ __attribute__((aligned(16))) double em_lds[];
     if (st->done) return;
     const int np = D * (D + 1) / 2;
     double* L = em_lds;                          // [np]
     double* m = L + np;                          // [D]
-    double* y = m + D;                           // [D][EM_ROWS]
+    double* y = m + D;                           // [D][ROWS]
     const int lane = threadIdx.x;
-    for (int e = lane; e < np; e += EM_ROWS) L[e] = Lp[e];
-    for (int e = lane; e < D; e += EM_ROWS) m[e] = mu[e];
+    for (int e = lane; e < np; e += ROWS) L[e] = Lp[e];
+    for (int e = lane; e < D; e += ROWS) m[e] = mu[e];
     __syncthreads();
-    const int64_t r = (int64_t)blockIdx.x * EM_ROWS + lane;
+    const int64_t r = (int64_t)blockIdx.x * ROWS + lane;
     if (r >= n) return;
+    if (WT && !(wts[r] > 0.0)) { delta[r] = 0.0; return; }
     const T* row = x + (idx ? idx[r] : r) * D;
     double dl = 0.0;
     for (int i = 0; i < D; ++i) {
@@ -109,14 +148,14 @@ __global__ __launch_bounds__(EM_ROWS) void em_delta_kernel(const T* __restrict__
         double s0 = (double)row[i] - m[i], s1 = 0.0, s2 = 0.0, s3 = 0.0;
         int j = 0;
         for (; j + 4 <= i; j += 4) {
-            s0 -= Li[j] * y[j * EM_ROWS + lane];
-            s1 -= Li[j + 1] * y[(j + 1) * EM_ROWS + lane];
-            s2 -= Li[j + 2] * y[(j + 2) * EM_ROWS + lane];
-            s3 -= Li[j + 3] * y[(j + 3) * EM_ROWS + lane];
+            s0 -= Li[j] * y[j * ROWS + lane];
+            s1 -= Li[j + 1] * y[(j + 1) * ROWS + lane];
+            s2 -= Li[j + 2] * y[(j + 2) * ROWS + lane];
+            s3 -= Li[j + 3] * y[(j + 3) * ROWS + lane];
         }
-        for (; j < i; ++j) s0 -= Li[j] * y[j * EM_ROWS + lane];
+        for (; j < i; ++j) s0 -= Li[j] * y[j * ROWS + lane];
         const double yi = ((s0 + s1) + (s2 + s3)) / Li[i];
-        y[i * EM_ROWS + lane] = yi;
+        y[i * ROWS + lane] = yi;
         dl += yi * yi;
     }
     delta[r] = dl;
@@ -126,12 +165,18 @@ __global__ __launch_bounds__(EM_ROWS) void em_delta_kernel(const T* __restrict__
 // the nu update.  f(nu) = [log(nu/2) - psi(nu/2)] - [log((nu+D)/2) - psi((nu+D)/2)] + mean(log w - w + 1) with
 // log w - w + 1 = log1p(u) - u near w = 1 and log(w) - u away from it, u = w - 1 = (D - delta) / (nu + delta).  Every
 // thread holds the same root-finder state: the sum comes back through LDS, so all of them take the same branches.
+// WT: sum_r pi_r (log w_r - w_r + 1) over the rows of positive weight, pi_r = wts_r / W, in place of the mean.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ static double em_f(double nu, const double* __restrict__ delta, int64_t n, int D, double* part) {
+template <bool WT>
+__device__ static double em_f(double nu, const double* __restrict__ delta, const double* __restrict__ wts, double W, int64_t n, int D,
+                              double* part) {
     double s = 0.0;
     for (int64_t e = threadIdx.x; e < n; e += EM_NU_THREADS) {
+        if (WT && !(wts[e] > 0.0)) continue;
         const double dl = delta[e], den = nu + dl, u = ((double)D - dl) / den;     // u = w - 1
-        s += fabs(u) < 0.5 ? log1p(u) - u : log((nu + (double)D) / den) - u;       // (a far row: w << 1, 1 + u cancels)
+        const double v = fabs(u) < 0.5 ? log1p(u) - u : log((nu + (double)D) / den) - u;   // (a far row: w << 1, 1 + u cancels)
+        if (WT) s += (wts[e] / W) * v;
+        else s += v;
     }
     part[threadIdx.x] = s;
     __syncthreads();
@@ -141,22 +186,25 @@ __device__ static double em_f(double nu, const double* __restrict__ delta, int64
     }
     const double total = part[0];
     __syncthreads();
-    return (log_minus_psi(0.5 * nu) - log_minus_psi(0.5 * (nu + D))) + total / (double)n;
+    return (log_minus_psi(0.5 * nu) - log_minus_psi(0.5 * (nu + D))) + (WT ? total : total / (double)n);
 }
 
-__global__ __launch_bounds__(EM_NU_THREADS) void em_nu_kernel(const double* __restrict__ delta, int64_t n, int D,
+template <bool WT>
+__global__ __launch_bounds__(EM_NU_THREADS) void em_nu_kernel(const double* __restrict__ delta, const double* __restrict__ wts,
+                                                              const EmWeights* __restrict__ ew, int64_t n, int D,
                                                               EmState* __restrict__ st) {
     __shared__ double part[EM_NU_THREADS];
     if (st->done) return;
+    const double W = WT ? ew->sum : 0.0;
     const double nu_old = st->nu;
     __syncthreads();                                   // (thread 0 writes st->nu at the end)
     double nu = 0.0;
     int status = -1;                                   // -1: the iteration goes on
-    const double fhi = em_f(PMC_STUDENT_NU_HI, delta, n, D, part);
+    const double fhi = em_f<WT>(PMC_STUDENT_NU_HI, delta, wts, W, n, D, part);
     if (fhi != fhi) status = PMC_STUDENT_NONFINITE;
     else if (fhi >= 0.0) { nu = __builtin_inf(); status = PMC_STUDENT_NU_INF; }
     else {
-        const double flo = em_f(PMC_STUDENT_NU_LO, delta, n, D, part);
+        const double flo = em_f<WT>(PMC_STUDENT_NU_LO, delta, wts, W, n, D, part);
         if (flo != flo) status = PMC_STUDENT_NONFINITE;
         else if (flo <= 0.0) nu = PMC_STUDENT_NU_LO;
         else {
@@ -177,7 +225,7 @@ __global__ __launch_bounds__(EM_NU_THREADS) void em_nu_kernel(const double* __re
                     if (!(t >= lo + 3e-14)) t = lo + 3e-14;
                     if (!(t <= hi - 3e-14)) t = hi - 3e-14;
                 }
-                const double ft = em_f(exp(t), delta, n, D, part);
+                const double ft = em_f<WT>(exp(t), delta, wts, W, n, D, part);
                 if (ft != ft) { status = PMC_STUDENT_NONFINITE; break; }
                 ta = tb; fa = fb; tb = t; fb = ft;
                 w3 = w2; w2 = w1; w1 = hi - lo;
@@ -195,21 +243,25 @@ __global__ __launch_bounds__(EM_NU_THREADS) void em_nu_kernel(const double* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// weighted sums with w_r = (nu + D) / (nu + delta_r): pool.hip's mom1 / mom2 partials and their ordered finals
+// weighted sums with w_r = (nu + D) / (nu + delta_r): pool.hip's mom1 / mom2 partials and their ordered finals.
+// WT: w_r = pi_r (nu + D) / (nu + delta_r), and a row of weight zero adds nothing and is not read
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool WT>
 __global__ __launch_bounds__(256) void em_mom1_kernel(const T* __restrict__ x, const int64_t* __restrict__ idx,
+                                                      const double* __restrict__ wts, const EmWeights* __restrict__ ew,
                                                       const double* __restrict__ delta, const EmState* __restrict__ st, int64_t n,
                                                       int D, double* __restrict__ part /* [EM_CHUNKS][D + 1] */) {
     if (st->done) return;
     const double nu = st->nu, num = nu + (double)D;
+    const double W = WT ? ew->sum : 0.0;
     const int c = blockIdx.x;
     const int64_t per = (n + EM_CHUNKS - 1) / EM_CHUNKS;
     const int64_t lo = c * per, hi = lo + per < n ? lo + per : n;
     for (int j = threadIdx.x; j < D + 1; j += 256) {
         double s = 0.0;
         for (int64_t r = lo; r < hi; ++r) {
-            const double wr = num / (nu + delta[r]);
+            if (WT && !(wts[r] > 0.0)) continue;
+            const double wr = WT ? (wts[r] / W) * (num / (nu + delta[r])) : num / (nu + delta[r]);
             if (j < D) { const int64_t row = idx ? idx[r] : r; s += wr * (double)x[row * D + j]; }
             else s += wr;
         }
@@ -218,14 +270,16 @@ __global__ __launch_bounds__(256) void em_mom1_kernel(const T* __restrict__ x, c
 }
 
 // grid (EM_CHUNKS, tiles_i * tiles_j): a 16 x 16 tile of sum w d d^T over one row chunk, d = x - mu (the old mu)
-template <typename T>
+template <typename T, bool WT>
 __global__ __launch_bounds__(256) void em_mom2_kernel(const T* __restrict__ x, const int64_t* __restrict__ idx,
+                                                      const double* __restrict__ wts, const EmWeights* __restrict__ ew,
                                                       const double* __restrict__ delta, const EmState* __restrict__ st,
                                                       const double* __restrict__ mu, int64_t n, int D,
                                                       double* __restrict__ part /* [EM_CHUNKS][D][D] */) {
     __shared__ double xi[16][17], xj[16][17], wr[16];
     if (st->done) return;
     const double nu = st->nu, num = nu + (double)D;
+    const double W = WT ? ew->sum : 0.0;
     const int c = blockIdx.x, nt = (D + 15) / 16;
     const int ti = blockIdx.y / nt, tj = blockIdx.y % nt;
     if (tj < ti) return;                                            // symmetric: upper tiles only
@@ -238,12 +292,12 @@ __global__ __launch_bounds__(256) void em_mom2_kernel(const T* __restrict__ x, c
         {
             const int64_t r = r0 + a;
             double vi = 0.0, vj = 0.0;
-            if (r < hi) {
+            if (r < hi && !(WT && !(wts[r] > 0.0))) {
                 const int64_t row = idx ? idx[r] : r;
                 const int ci = 16 * ti + b, cj = 16 * tj + b;
                 if (ci < D) vi = (double)x[row * D + ci] - mu[ci];
                 if (cj < D) vj = (double)x[row * D + cj] - mu[cj];
-                if (b == 0) wr[a] = num / (nu + delta[r]);
+                if (b == 0) wr[a] = WT ? (wts[r] / W) * (num / (nu + delta[r])) : num / (nu + delta[r]);
             } else if (b == 0) wr[a] = 0.0;
             xi[a][b] = vi; xj[a][b] = vj;
         }
@@ -255,7 +309,8 @@ __global__ __launch_bounds__(256) void em_mom2_kernel(const T* __restrict__ x, c
     if (i < D && j < D) part[((size_t)c * D + i) * D + j] = s;
 }
 
-// Sigma = sum_c part / n
+// Sigma = sum_c part / n (WT: the weights pi_r are in the partials already)
+template <bool WT>
 __global__ __launch_bounds__(256) void em_sigma_kernel(const double* __restrict__ part, const EmState* __restrict__ st, int64_t n,
                                                        int D, double* __restrict__ sigma) {
     if (st->done) return;
@@ -264,7 +319,7 @@ __global__ __launch_bounds__(256) void em_sigma_kernel(const double* __restrict_
         const int ii = i <= j ? i : j, jj = i <= j ? j : i;           // the upper triangle was computed
         double s = 0.0;
         for (int c = 0; c < EM_CHUNKS; ++c) s += part[((size_t)c * D + ii) * D + jj];
-        sigma[e] = s / (double)n;
+        sigma[e] = WT ? s : s / (double)n;
     }
 }
 
@@ -289,7 +344,7 @@ __global__ __launch_bounds__(128) void em_step_kernel(const double* __restrict__
     }
 }
 
-// workspace: state | packed factor | delta [n] | mom1 partials | mom2 partials
+// workspace: state (the weight record at byte 128) | packed factor | delta [n] | mom1 partials | mom2 partials
 static inline size_t em_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" int64_t pmc_student_em_workspace_bytes(int64_t n, int32_t D) {
@@ -299,45 +354,66 @@ extern "C" int64_t pmc_student_em_workspace_bytes(int64_t n, int32_t D) {
                      + em_align(8 * EM_CHUNKS * d * d));
 }
 
-template <typename T>
-static int em_run(const T* x, const int64_t* idx, int64_t n, int D, double* mu, double* sigma, double tol, int max_iter,
-                  double* result, char* ws, hipStream_t st) {
+extern "C" int64_t pmc_student_em_weighted_workspace_bytes(int64_t n, int32_t D) { return pmc_student_em_workspace_bytes(n, D); }
+
+// WT = false: pmc_student_em (wts == NULL, result [4]); WT = true: pmc_student_em_weighted (idx == NULL, result [6])
+template <typename T, bool WT>
+static int em_run(const char* name, const T* x, const int64_t* idx, const double* wts, int64_t n, int D, double* mu, double* sigma,
+                  double tol, int max_iter, double* result, char* ws, hipStream_t st) {
     const size_t d = (size_t)D;
     EmState* state = (EmState*)ws;
+    const EmWeights* ew = (const EmWeights*)(ws + 128);
     double* Lp = (double*)(ws + 256);
     double* delta = (double*)((char*)Lp + em_align(8 * d * (d + 1) / 2));
     double* p1 = (double*)((char*)delta + em_align(8 * (size_t)n));
     double* p2 = (double*)((char*)p1 + em_align(8 * EM_CHUNKS * (d + 1)));
+    const bool wide = WT && D > PMC_STUDENT_MAX_D;         // 32 rows per workgroup: 140,672 bytes of LDS at D = 157
     const size_t lds_chol = 8 * (d * (d + 1) / 2 + d);
-    const size_t lds_delta = 8 * (d * (d + 1) / 2 + d + d * EM_ROWS);
+    const size_t lds_delta = 8 * (d * (d + 1) / 2 + d + d * (size_t)(wide ? EM_ROWS_WIDE : EM_ROWS));
+    EmWeights hw = {};
+    int reads = 0;
+    if (WT) {
+        hipLaunchKernelGGL(em_weights_kernel, dim3(1), dim3(EM_W_THREADS), 0, st, wts, n, (EmWeights*)(ws + 128));
+        int rc = pmc_check_launch(name);
+        if (rc) return rc;
+        hipError_t e = hipMemcpyAsync(&hw, ew, sizeof(EmWeights), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return pmc_fail_hip(e, "pmc_student_em_weighted: reading the weight record");
+        ++reads;
+        if (hw.bad) return pmc_fail("pmc_student_em_weighted: weights must be finite and non-negative");
+        if (hw.positive <= (int64_t)D) return pmc_fail("pmc_student_em_weighted: needs more rows of positive weight than dimensions");
+    }
     if (lds_chol > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(em_chol_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_chol);
         if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(em_chol_kernel)");
     }
+    void (*delta_kernel)(const T*, const int64_t*, const double*, int64_t, int, const double*, const double*, const EmState*, double*)
+        = em_delta_kernel<T, EM_ROWS, WT>;
+    if constexpr (WT) if (wide) delta_kernel = em_delta_kernel<T, EM_ROWS_WIDE, true>;
+    const int rows = wide ? EM_ROWS_WIDE : EM_ROWS;
     if (lds_delta > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(em_delta_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_delta);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(delta_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_delta);
         if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(em_delta_kernel)");
     }
     const int nt = (D + 15) / 16;
     // (the lower tiles of em_mom2_kernel write nothing and em_sigma_kernel reads the upper triangle only: no memset)
     hipLaunchKernelGGL(em_init_kernel, dim3(1), dim3(1), 0, st, state);
     EmState h = {};
-    int reads = 0;
     for (int it = 0; it < max_iter && !h.done;) {
         for (int k = 0; k < EM_HOST_CHUNK && it < max_iter; ++k, ++it) {
             hipLaunchKernelGGL(em_chol_kernel, dim3(1), dim3(256), lds_chol, st, (const double*)sigma, D, state, Lp);
-            hipLaunchKernelGGL(em_delta_kernel<T>, dim3((unsigned)((n + EM_ROWS - 1) / EM_ROWS)), dim3(EM_ROWS), lds_delta, st, x, idx, n,
-                               D, (const double*)mu, (const double*)Lp, (const EmState*)state, delta);
-            hipLaunchKernelGGL(em_nu_kernel, dim3(1), dim3(EM_NU_THREADS), 0, st, (const double*)delta, n, D, state);
-            hipLaunchKernelGGL(em_mom1_kernel<T>, dim3(EM_CHUNKS), dim3(256), 0, st, x, idx, (const double*)delta, (const EmState*)state,
-                               n, D, p1);
-            hipLaunchKernelGGL(em_mom2_kernel<T>, dim3(EM_CHUNKS, nt * nt), dim3(256), 0, st, x, idx, (const double*)delta,
+            hipLaunchKernelGGL(delta_kernel, dim3((unsigned)((n + rows - 1) / rows)), dim3(rows), lds_delta, st, x, idx, wts, n, D,
+                               (const double*)mu, (const double*)Lp, (const EmState*)state, delta);
+            hipLaunchKernelGGL(em_nu_kernel<WT>, dim3(1), dim3(EM_NU_THREADS), 0, st, (const double*)delta, wts, ew, n, D, state);
+            hipLaunchKernelGGL((em_mom1_kernel<T, WT>), dim3(EM_CHUNKS), dim3(256), 0, st, x, idx, wts, ew, (const double*)delta,
+                               (const EmState*)state, n, D, p1);
+            hipLaunchKernelGGL((em_mom2_kernel<T, WT>), dim3(EM_CHUNKS, nt * nt), dim3(256), 0, st, x, idx, wts, ew, (const double*)delta,
                                (const EmState*)state, (const double*)mu, n, D, p2);
-            hipLaunchKernelGGL(em_sigma_kernel, dim3((D * D + 255) / 256), dim3(256), 0, st, (const double*)p2, (const EmState*)state,
+            hipLaunchKernelGGL(em_sigma_kernel<WT>, dim3((D * D + 255) / 256), dim3(256), 0, st, (const double*)p2, (const EmState*)state,
                                n, D, sigma);
             hipLaunchKernelGGL(em_step_kernel, dim3(1), dim3(128), 0, st, (const double*)p1, D, tol, max_iter, state, mu);
         }
-        int rc = pmc_check_launch("pmc_student_em");
+        int rc = pmc_check_launch(name);
         if (rc) return rc;
         hipError_t e = hipMemcpyAsync(&h, state, sizeof(EmState), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -346,6 +422,7 @@ static int em_run(const T* x, const int64_t* idx, int64_t n, int D, double* mu, 
     }
     if (!h.done) return pmc_fail("pmc_student_em: the fit did not end (internal error)");
     result[0] = h.nu; result[1] = (double)h.iter; result[2] = (double)h.status; result[3] = (double)reads;
+    if (WT) { result[4] = (double)hw.positive; result[5] = hw.sum * hw.sum / hw.sum2; }
     return 0;
 }
 
@@ -358,6 +435,23 @@ extern "C" int pmc_student_em(const double* x, const float* x32, const int64_t* 
     if (D > PMC_STUDENT_MAX_D) return pmc_fail("pmc_student_em: D > 128 (the packed Cholesky factor and 64 rows' substitution vectors share the LDS)");
     if (n <= D) return pmc_fail("pmc_student_em: needs more rows than dimensions");
     if (workspace_bytes < pmc_student_em_workspace_bytes(n, D)) return pmc_fail("pmc_student_em: workspace too small");
-    if (x32) return em_run<float>(x32, idx, n, (int)D, mu_io, sigma_io, tol, (int)max_iter, result, (char*)workspace, (hipStream_t)stream);
-    return em_run<double>(x, idx, n, (int)D, mu_io, sigma_io, tol, (int)max_iter, result, (char*)workspace, (hipStream_t)stream);
+    if (x32) return em_run<float, false>("pmc_student_em", x32, idx, nullptr, n, (int)D, mu_io, sigma_io, tol, (int)max_iter, result,
+                                         (char*)workspace, (hipStream_t)stream);
+    return em_run<double, false>("pmc_student_em", x, idx, nullptr, n, (int)D, mu_io, sigma_io, tol, (int)max_iter, result,
+                                 (char*)workspace, (hipStream_t)stream);
+}
+
+// the same fit with a weight per row: x rows 0..n-1, w f64 [n] >= 0 (device); result: host f64 [6]
+extern "C" int pmc_student_em_weighted(const double* x, const float* x32, const double* w, int64_t n, int32_t D, double* mu_io,
+                                       double* sigma_io, double tol, int32_t max_iter, double* result, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+    if ((!x && !x32) || !w || !mu_io || !sigma_io || !result || !workspace || n < 1 || D < 1 || max_iter < 1 || !(tol >= 0.0))
+        return pmc_fail("pmc_student_em_weighted: bad argument");
+    if (D > PMC_STUDENT_W_MAX_D) return pmc_fail("pmc_student_em_weighted: D > 157 (the widest MCMC step)");
+    if (n <= D) return pmc_fail("pmc_student_em_weighted: needs more rows of positive weight than dimensions");
+    if (workspace_bytes < pmc_student_em_weighted_workspace_bytes(n, D)) return pmc_fail("pmc_student_em_weighted: workspace too small");
+    if (x32) return em_run<float, true>("pmc_student_em_weighted", x32, nullptr, w, n, (int)D, mu_io, sigma_io, tol, (int)max_iter, result,
+                                        (char*)workspace, (hipStream_t)stream);
+    return em_run<double, true>("pmc_student_em_weighted", x, nullptr, w, n, (int)D, mu_io, sigma_io, tol, (int)max_iter, result,
+                                (char*)workspace, (hipStream_t)stream);
 }

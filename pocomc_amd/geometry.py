@@ -26,6 +26,12 @@ the reference sets out to do (``student.py:53-85``) with a root finder for ``nu`
 ``csrc/student.hip``; the algorithm is stated in ``include/pocomc_amd.h``).  Gaussian rows leave it at the first
 iteration with ``nu = inf`` and the start values: the reference mode's result, bit for bit.  Heavy-tailed rows give the
 finite ``nu`` the t-preconditioned Crank-Nicolson step was written for.
+
+``Geometry(student="em_weighted")`` fits on the weights themselves (``pmc_student_em_weighted``): every row enters each sum
+of the EM with ``w_r / sum w`` instead of through one systematic resample, so the fit draws no random number, needs no
+second moments pass and no medians, and is the same on every call.  It starts from the weighted mean and the weighted
+scatter ``S / V1`` of the moments pass that forms ``normal_mean`` / ``normal_cov``, and runs up to ``n_dim = 157``, the
+width of the MCMC step.
 """
 from __future__ import annotations
 
@@ -133,17 +139,59 @@ def student_em(x, idx, mu, sigma, tol=1e-6, max_iter=100):
     return out[:D], out[D:].reshape(D, D), info
 
 
+STUDENT_W_MAX_D = 157                                                      # PMC_STUDENT_W_MAX_D
+
+
+def student_em_weighted(x, w, mu, sigma, tol=1e-6, max_iter=100):
+    """The EM fit of a multivariate Student-t to the rows ``x`` (device tensor, float64 or float32) with the weights ``w``
+    (float64 device tensor [n], ``>= 0``, any scale) from the start values ``mu`` [D], ``sigma`` [D, D] (numpy), on the
+    device (``pmc_student_em_weighted``).  Returns ``(mu, sigma, info)`` like :func:`student_em`; ``info`` also holds
+    ``rows_positive`` (rows with ``w > 0``: the others are never read) and ``ess`` (Kish, ``(sum w)^2 / sum w^2``).
+    Weights that are negative or not finite, or no more rows of positive weight than dimensions: ``ValueError``."""
+    lib = _lib.load()
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if D > STUDENT_W_MAX_D:
+        raise ValueError(f"student_em_weighted: n_dim = {D} is above {STUDENT_W_MAX_D}, the largest the device fit supports")
+    if n <= D:
+        raise ValueError(f"student_em_weighted: {n} rows cannot fit a {D}-dimensional Student-t (more rows of positive "
+                         "weight than dimensions needed)")
+    if w.dtype != torch.float64 or int(w.numel()) != n:
+        raise ValueError("student_em_weighted: w must be a float64 tensor with one weight per row")
+    dev = x.device
+    start = np.concatenate([np.asarray(mu, dtype=np.float64).reshape(D), np.asarray(sigma, dtype=np.float64).reshape(D * D)])
+    io = torch.from_numpy(start).to(dev)
+    nbytes = int(lib.pmc_student_em_weighted_workspace_bytes(n, D))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    res = (C.c_double * 6)()
+    f32 = x.dtype == torch.float32
+    with torch.cuda.device(dev):
+        rc = lib.pmc_student_em_weighted(None if f32 else _lib.ptr(x), _lib.ptr(x) if f32 else None, _lib.ptr(w), n, D,
+                                         _lib.ptr(io), C.c_void_p(io.data_ptr() + 8 * D), float(tol), int(max_iter), res,
+                                         _lib.ptr(ws), nbytes, _lib.stream_handle())
+    if rc != 0:
+        msg = (lib.pmc_last_error() or b"").decode()
+        if "weights must be" in msg or "rows of positive weight" in msg:       # (the weight check: the caller's input)
+            raise ValueError(msg)
+        _lib.check(rc, "pmc_student_em_weighted")
+    out = io.cpu().numpy()
+    info = dict(nu=float(res[0]), iterations=int(res[1]), status=STUDENT_STATUS[int(res[2])], host_reads=int(res[3]),
+                rows_positive=int(res[4]), ess=float(res[5]))
+    return out[:D], out[D:].reshape(D, D), info
+
+
 class Geometry:
     """``pocomc/geometry.py:5-59``.  ``student``: ``"reference"`` (default) reproduces the reference's t-fit, which always
     ends at its start values with ``t_nu = 1e6``; ``"em"`` fits location, scatter and degrees of freedom by EM on the
-    device (module docstring) and records ``student_info = dict(iterations=, status=, nu=)``."""
+    device (module docstring) and records ``student_info = dict(iterations=, status=, nu=)``; ``"em_weighted"`` runs that
+    fit on the weights themselves instead of on a resample (no random number, ``n_dim <= 157``) and adds ``rows_positive=``
+    and ``ess=`` to ``student_info``."""
 
     student = "reference"                      # (objects unpickled from checkpoints older than the attribute)
     student_info = None
 
     def __init__(self, student="reference"):
-        if student not in ("reference", "em"):
-            raise ValueError(f"Invalid student {student}. Options are 'reference' or 'em'.")
+        if student not in ("reference", "em", "em_weighted"):
+            raise ValueError(f"Invalid student {student}. Options are 'reference', 'em' or 'em_weighted'.")
         self.student = student
         self.student_info = None
         self.normal_mean = self.normal_cov = self.t_mean = self.t_cov = self.t_nu = None
@@ -153,6 +201,8 @@ class Geometry:
         from .tools import systematic_resample
         th = _as_device(theta)
         n, D = int(th.shape[0]), int(th.shape[1])
+        if self.student == "em_weighted":
+            return self._fit_weighted(th, weights)
         if self.student == "em":                                           # (before any launch)
             if D > STUDENT_MAX_D:
                 raise ValueError(f"Geometry.fit: student='em' supports n_dim <= {STUDENT_MAX_D}, got {D}")
@@ -204,3 +254,40 @@ class Geometry:
         self.t_mean, self.t_cov, self.t_nu = med, sigma, nu
         if not np.isfinite(self.t_nu):
             self.t_nu = 1e6                                                # geometry.py:58-59
+
+    def _fit_weighted(self, th, weights):
+        """``student="em_weighted"``: one moments pass, then the EM on the weights (``None``: ones).  The fields are set
+        together at the end: a fit that raises leaves the geometry as it was."""
+        n, D = int(th.shape[0]), int(th.shape[1])
+        if D > STUDENT_W_MAX_D:                                            # (before any launch)
+            raise ValueError(f"Geometry.fit: student='em_weighted' supports n_dim <= {STUDENT_W_MAX_D}, got {D}")
+        if n <= D:
+            raise ValueError(f"Geometry.fit: student='em_weighted' needs more rows of positive weight than dimensions, "
+                             f"got {n} rows of {D}")
+        if weights is None:
+            w = torch.ones(n, dtype=torch.float64, device=th.device)
+            mean, S, v1, v2 = moments(th)
+            normal_cov = S / (n - 1)                                       # np.cov(theta.T)
+        else:
+            w = _as_device(weights, keep32=False)
+            mean, S, v1, v2 = moments(th, None, w)
+            normal_cov = S / (v1 - v2 / v1)                                # np.cov(theta.T, aweights=weights): ddof = 1
+        sigma = S / v1                                                     # the ML-normalised weighted scatter
+        if not (np.isfinite(mean).all() and np.isfinite(sigma).all()):
+            raise ValueError("Geometry.fit: non-finite values in theta or the weights (weighted mean / scatter matrix are "
+                             "not finite)")
+        try:
+            np.linalg.solve(sigma, np.eye(D))
+        except np.linalg.LinAlgError:
+            raise np.linalg.LinAlgError("Geometry.fit: the weighted scatter matrix of theta is singular")
+        mu, sigma, info = student_em_weighted(th, w, mean, sigma)
+        if info["status"] == "not_pd":
+            raise np.linalg.LinAlgError(f"Geometry.fit: the scatter matrix of the Student-t fit is not positive definite "
+                                        f"(EM iteration {info['iterations']})")
+        if info["status"] == "nonfinite":
+            raise ValueError(f"Geometry.fit: non-finite values in the Student-t fit (EM iteration {info['iterations']})")
+        self.normal_mean, self.normal_cov = mean, normal_cov
+        self.student_info = dict(iterations=info["iterations"], status=info["status"], nu=info["nu"],
+                                 rows_positive=info["rows_positive"], ess=info["ess"])
+        self.t_mean, self.t_cov = mu, sigma
+        self.t_nu = info["nu"] if np.isfinite(info["nu"]) else 1e6         # geometry.py:58-59

@@ -179,7 +179,9 @@ class Sampler:
                           ``"reference"`` (default) as the reference does, which always ends at ``nu = 1e6`` -- a Gaussian
                           pCN step; ``"em"`` by EM on the device (``pmc_student_em``, ``n_dim <= 128``), which gives
                           heavy-tailed pools the finite ``nu`` of the t-preconditioned step and Gaussian ones the
-                          reference's values.  Sharded: every rank fits the replicated pool and gets the same bits.
+                          reference's values; ``"em_weighted"`` the same EM on the pool's trimmed weights themselves
+                          instead of on one systematic resample of them (``pmc_student_em_weighted``, ``n_dim <= 157``):
+                          no random number is drawn.  Sharded: every rank fits the replicated pool and gets the same bits.
 
         Supported ``train_config`` keys: those of ``sampler.py:287-299`` (``validation_split, epochs, batch_size,
         patience, learning_rate, annealing, gaussian_scale, laplace_scale, noise, shuffle, clip_grad_norm, verbose``),
@@ -248,7 +250,7 @@ class Sampler:
 
         for name, value, allowed in (("transform", transform, ("probit", "logit")), ("metric", metric, ("ess", "uss")),
                                      ("sample", sample, ("tpcn", "rwm")), ("resample", resample, ("mult", "syst")),
-                                     ("student_fit", student_fit, ("reference", "em"))):
+                                     ("student_fit", student_fit, ("reference", "em", "em_weighted"))):
             if value not in allowed:
                 raise ValueError(f"Invalid {name} {value}. Options are {' or '.join(repr(a) for a in allowed)}.")
         self.metric, self.sample, self.resample, self.dynamic = metric, sample, resample, dynamic
