@@ -118,6 +118,33 @@ int pmc_maf_inverse_auto_is_duo(const pmc_maf_t* m, int64_t n);
 int pmc_maf_inverse_auto_is_lane(const pmc_maf_t* m);
 int pmc_maf_inverse_auto_is_nsf2(const pmc_maf_t* m);
 
+/* The whole choice behind pmc_maf_inverse and the MCMC step (csrc/inverse_plan.hip): which kernel instance a call of n
+ * rows with `algo` launches for this flow.  A pure host function: it reads the descriptor's layout fields only (no
+ * pointer is followed, no device is touched).
+ *   sweep      PMC_SWEEP_*
+ *   fused      the instance starts with the proposal (pmc_step_pre); epilogue: it ends with the scaler (+ prior)
+ *   maxo       output tiles held in registers by the register-chain sweeps (4 / 8), 0 elsewhere
+ *   fm         feature tiles of the fused proposal (4 / 8 / 16 quads: D <= 16 / 32 / 64), 0 unfused
+ *   subsets, waves, helper_fmt   lane-per-walker sweep: walker subsets per workgroup (1 / 2 / 4), wavefronts (4 / 5),
+ *              helper operands (0 float32, 1 bfloat16, 2 float16); 0 elsewhere
+ *   lds_bytes  dynamic LDS of the launch
+ * The descriptor is taken as one pmc_maf_inverse accepts (its consistency checks are not repeated here).
+ * fused = 0: returns non-zero (pmc_last_error), with the same message, where pmc_maf_inverse refuses (flow, n, algo).
+ * fused = 1: which fused proposal + inverse instance pmc_step_pre launches (algo AUTO or TRIANGULAR; the scaler taken as
+ * eligible for the epilogue); sweep = PMC_SWEEP_NONE, return 0: none -- the step launches its stages one by one. */
+#define PMC_SWEEP_NONE 0
+#define PMC_SWEEP_DPASS_AFFINE 1
+#define PMC_SWEEP_DPASS_SPLINE 2
+#define PMC_SWEEP_SOLO 3
+#define PMC_SWEEP_DUO 4
+#define PMC_SWEEP_LANE 5
+#define PMC_SWEEP_NSF_SOLO 6
+#define PMC_SWEEP_NSF_DUO 7
+typedef struct pmc_inverse_plan {
+    int32_t sweep, fused, epilogue, maxo, fm, subsets, waves, helper_fmt, lds_bytes;
+} pmc_inverse_plan_t;
+int pmc_maf_inverse_plan(const pmc_maf_t* m, int64_t n, int algo, int fused, pmc_inverse_plan_t* plan);
+
 /* 16-bit helper image of the lane-per-walker inverse sweep (Flow.inverse of the wide flows, flow.py:116-132, in the opt-in
  * precision of BASELINE config 5): image u16 [pmc_maf_lane16_elems(m)], derived on the device from m->packed (call again
  * after every pmc_maf_pack); fmt 1 = bfloat16, 2 = float16, round to nearest even.  Attach it as m->lane16 / lane16_fmt. */

@@ -25,6 +25,11 @@ class pmc_maf_t(C.Structure):
                 ("lane16", c_p), ("lane16_fmt", C.c_int32), ("reserved", C.c_int32)]
 
 
+class pmc_inverse_plan_t(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("sweep", "fused", "epilogue", "maxo", "fm", "subsets", "waves", "helper_fmt",
+                                         "lds_bytes")]
+
+
 class pmc_maf_train_t(C.Structure):
     _fields_ = [("packedT", c_p), ("gmap", c_p), ("pkT_per_transform", C.c_int64),
                 ("gmap_per_transform", C.c_int64),
@@ -112,6 +117,7 @@ SIGNATURES = {
     "pmc_maf_inverse_auto_is_duo": (C.c_int, [C.POINTER(pmc_maf_t), C.c_int64]),
     "pmc_maf_inverse_auto_is_lane": (C.c_int, [C.POINTER(pmc_maf_t)]),
     "pmc_maf_inverse_auto_is_nsf2": (C.c_int, [C.POINTER(pmc_maf_t)]),
+    "pmc_maf_inverse_plan": (C.c_int, [C.POINTER(pmc_maf_t), C.c_int64, C.c_int, C.c_int, C.POINTER(pmc_inverse_plan_t)]),
     "pmc_maf_train_waves": (C.c_int, [C.POINTER(pmc_maf_t)]),
     "pmc_abi_version": (C.c_int, []),
     "pmc_build_id": (C.c_char_p, []),

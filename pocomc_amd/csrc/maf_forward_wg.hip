@@ -13,6 +13,7 @@
 // (rank, row) evaluates its spline.  UNI: 0 = affine, else the number of bins (4, 8, 16).
 #include <stdlib.h>
 #include "maf_wg.h"
+#include "inverse_lds.h"
 #include "rqs.h"
 
 #define PANEL_TILES(UNI) RQS_NOUT_OF(UNI)   // 16 ranks x (3 K - 1) outputs = 3 K - 1 tiles of 16 rows
@@ -166,8 +167,7 @@ __global__ __launch_bounds__(64 * NW) void maf_forward_wg_kernel(pmc_maf_t m, co
 template <int NW, int UNI, int MODE>
 static int launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob, int64_t n,
                              hipStream_t st, const int64_t* idx = nullptr) {
-    const size_t lds = (size_t)(2 * m->Dp * 16 + 3 * m->Hp * 16 + 16 * NW + (UNI ? PANEL_TILES(UNI) * 256 : 0) +
-                                (MODE ? m->Dp * 16 : 0)) * sizeof(float);
+    const size_t lds = pmc_lds_wg(m, NW, UNI ? PANEL_TILES(UNI) : 0, MODE);
     if (lds > 160 * 1024) return pmc_fail("pmc_maf_forward: flow too wide for 160 KB of LDS");
     static size_t lds_set = 0;
     if (lds > 48 * 1024 && lds > lds_set) {
@@ -198,7 +198,10 @@ int pmc_launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* l
 
 // D-pass inverse through the same workgroup kernel (the only inverse of the spline flows until the
 // triangular sweep learns the spline; a cross-check for the affine flows)
-int pmc_launch_inverse_dpass_wg(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t st) {
+int pmc_launch_inverse_dpass_wg(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
+                                float* x, float* ladj, int64_t n, hipStream_t st) {
+    if (plan->sweep != PMC_SWEEP_DPASS_SPLINE || pa || (size_t)plan->lds_bytes != pmc_lds_wg(m, 8, m->n_out == 2 ? 0 : m->n_out, 1))
+        return pmc_fail("pmc_launch_inverse_dpass_wg: not this sweep's plan");
     if (m->n_out == RQS_NOUT_OF(8)) return launch_forward_wg<8, 8, 1>(m, z, x, ladj, nullptr, n, st);
     if (m->n_out == RQS_NOUT_OF(4)) return launch_forward_wg<8, 4, 1>(m, z, x, ladj, nullptr, n, st);
     if (m->n_out == RQS_NOUT_OF(16)) return launch_forward_wg<8, 16, 1>(m, z, x, ladj, nullptr, n, st);

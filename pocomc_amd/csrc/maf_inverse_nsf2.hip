@@ -18,32 +18,13 @@
 //     Round 4: the output partials of the last two live tiles start at steps 2 - 4 (eager partials, NSF2_EAGER_OK): the two
 //     wavefronts are within 10 % of each other at every barrier (barrier stamps: docs/LAB_NOTEBOOK.md).
 // One LDS-only barrier per tile: E(Tt) = "tile Tt is final, the staging of tile Tt+1 is complete".
-#include <stdlib.h>
 #include "maf_chain_rot.h"
 #include "rqs.h"
 #include "propose_body.h"
+#include "inverse_lds.h"
 
-#define NSF2_PK 10                 // K tiles of the hidden bursts held in registers; the static burst tile covers flows of <= NSF2_PK + 1 live tiles
 #define NSF2_PX 4                  // x tiles of the layer-0 product held in registers (D <= 64)
-#define NSF2_OOB 0x40000000        // a lane offset beyond every image: the bounds-checked load returns zeros
-#define NSF2_STAGE_FLOATS (3 * 256)                 // hidden staging S0 | S1 | S2 (transposed, [lane][4])
-#define NSF2_PART_FLOATS (4 * 2 * 256)              // output staging [group][half][lane][4]
-#define NSF2_TT_WORDS(m) (((m)->nT + 2) * 8)        // per-tile table: ranks (word 0 also the pattern), x / y byte offsets
-#define NSF2_YT_WORDS(m) ((m)->T * (((m)->nT + 2) * 4 + 1))   // per transform: the y offsets of every tile's groups, of rank 0
-#define NSF2_LDS_BASE_FLOATS(m) (3 * (m)->Dp * 16 + 3 * (m)->Hp * 16 + 2 * NSF2_STAGE_FLOATS + 2 * NSF2_PART_FLOATS + 16 * 32 + \
-                                 ((NSF2_TT_WORDS(m) + (m)->Dp + NSF2_YT_WORDS(m) + 3) & ~3))
-// EAGER PARTIALS (round 4).  The burst wave's work for tile T1 grows with T1 (40 (T1 - 1) MFMAs at 32 cycles each against a
-// chain that takes ~9 k cycles per tile whatever the tile): from the seventh tile on the chain waited for it (barrier
-// stamps, docs/LAB_NOTEBOOK.md: 0.5 / 2.1 / 3.1 k cycles at tiles 5 - 7 of a nine-tile flow) while on tiles 1 - 4 the burst wave waited
-// 2 - 4 k cycles for the chain.  The output partials of the LAST TWO live tiles therefore start early: their ranks' products
-// against h2 tiles 0, 1, 2 (last tile) and 0, 1 (the one before) are formed at steps 2, 3, 4 -- in the burst wave's idle
-// time -- into two more partial buffers in LDS that only the burst wave touches; the two tiles' own steps start from those
-// and run K = 3 .. / 2 .. only (nsf_burst_tile<T1, KS>).  Flows of >= 8 live tiles on the static path whose LDS stays within
-// half a CU's (two workgroups per CU).
-#define NSF2_EAGER_FLOATS (2 * NSF2_PART_FLOATS)
-#define NSF2_EAGER_OK(m) ((m)->nT >= 8 && (m)->nT <= NSF2_PK + 1 && \
-                          (size_t)(NSF2_LDS_BASE_FLOATS(m) + NSF2_EAGER_FLOATS) * sizeof(float) <= 80 * 1024)
-#define NSF2_LDS_FLOATS(m) (NSF2_LDS_BASE_FLOATS(m) + (NSF2_EAGER_OK(m) ? NSF2_EAGER_FLOATS : 0))
+// (the LDS layout words NSF2_*: inverse_lds.h)
 
 __device__ __forceinline__ f32x4 as_acc(const float4& v) { f32x4 r; r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; return r; }
 
@@ -1013,62 +994,22 @@ __global__ __launch_bounds__(128) void maf_inverse_nsf2_kernel(pmc_maf_t m, cons
     }
 }
 
-// Covered: spline flows whose degree groups fit a hidden tile (tri_ok), D <= 64 (NSF2_PX x tiles), one buffer resource
-// over the whole image.  -1: not covered (the caller launches the lone-wave sweep / the separate kernels).
-// pa == nullptr: plain inverse of z; else the fused proposal (+ scaler epilogue when pa->epi.on).
-static int launch_nsf2(const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream) {
-    static const int mode = pmc_env_int("PMC_INVERSE_NSF_DUO", -1);
-    if (mode == 0) return -1;
-    if (m->n_out != 23 || !m->tri_ok || m->D > 64 || m->D < 2) return -1;
-    if (m->pk_per_transform * 4 * m->T >= (int64_t)NSF2_OOB) return -1;
-    const size_t lds = (size_t)NSF2_LDS_FLOATS(m) * sizeof(float);
-    if (lds > 160 * 1024) return -1;
-    const ProposeArgs none{};
+// The instance the plan names (inverse_plan.hip: PMC_SWEEP_NSF_DUO; fm -1: the profiled instance).  pa == nullptr: plain
+// inverse of z; else the fused proposal (+ scaler epilogue when pa->epi.on).
+int pmc_launch_nsf2(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream) {
+    const int fm = plan->fm;
+    if (plan->sweep != PMC_SWEEP_NSF_DUO || (fm != 0 && !pa)) return pmc_fail("pmc_launch_nsf2: not this sweep's plan");
     // PMC_MAF_VARIANT_LEFT_LOOKING: the burst wave's left-looking schedule without the eager partials (the two must agree
     // bit for bit: every partial receives its K tiles in ascending order either way; tests/test_gpu_flow.py)
     pmc_maf_t mk = *m;
     mk.reserved = (m->reserved & PMC_MAF_VARIANT_LEFT_LOOKING) ? 1 : 0;
-#define LAUNCHN(FMV)                                                                                              \
-    {                                                                                                             \
-        if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_nsf2_kernel<FMV>),       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-            if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_nsf2_kernel)");          \
-        }                                                                                                         \
-        hipLaunchKernelGGL(maf_inverse_nsf2_kernel<FMV>, dim3((unsigned)((n + 15) / 16)), dim3(128), lds, stream, mk, z, x, \
-                           ladj, n, pa ? pa->prof : (long long*)nullptr, pa ? *pa : none);                        \
-    }
-    if (pa && pa->prof) LAUNCHN(-1)
-    else if (!pa || !pa->cur32) LAUNCHN(0)
-    else if (m->D <= 16) LAUNCHN(4)
-    else if (m->D <= 32) LAUNCHN(8)
-    else LAUNCHN(16)
-#undef LAUNCHN
+    const auto k = fm == -1 ? maf_inverse_nsf2_kernel<-1> : fm == 0 ? maf_inverse_nsf2_kernel<0> : fm == 4 ? maf_inverse_nsf2_kernel<4>
+                 : fm == 8 ? maf_inverse_nsf2_kernel<8> : maf_inverse_nsf2_kernel<16>;
+    if (int e = pmc_launch_lds(k, "hipFuncSetAttribute(maf_inverse_nsf2_kernel)", dim3((unsigned)((n + 15) / 16)), dim3(128),
+                               (size_t)plan->lds_bytes, stream, mk, z, x, ladj, n, pa ? pa->prof : (long long*)nullptr,
+                               pa ? *pa : ProposeArgs{})) return e;
     return pmc_check_launch("maf_inverse_nsf2_kernel");
-}
-
-// whether PMC_INVERSE_AUTO launches this kernel for the flow (bench.py names the kernel it times with it)
-extern "C" int pmc_maf_inverse_auto_is_nsf2(const pmc_maf_t* m) {
-    static const int mode = pmc_env_int("PMC_INVERSE_NSF_DUO", -1);
-    if (!m || mode == 0 || m->n_out != 23 || !m->tri_ok || m->D > 64 || m->D < 2) return 0;
-    if (m->pk_per_transform * 4 * m->T >= (int64_t)NSF2_OOB) return 0;
-    return (size_t)NSF2_LDS_FLOATS(m) * sizeof(float) <= 160 * 1024 ? 1 : 0;
-}
-
-int pmc_launch_inverse_nsf2(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream) {
-    return launch_nsf2(nullptr, m, z, x, ladj, n, stream);
-}
-
-// the spline flows' instance of pmc_launch_propose_inverse_tri4 (same contract; called from there)
-int pmc_launch_propose_inverse_nsf2(ProposeArgs* pa, const ScalerEpi* epi, int* epi_done, const pmc_maf_t* m, float* x, float* ladj,
-                                    int64_t n, hipStream_t stream) {
-    if (epi_done) *epi_done = 0;
-    // the scaler as the sweep's epilogue: its scratch aliases the three activation arrays of the walker set
-    const bool epi_ok = epi && epi_done && epi->s.D == m->D && scaler_epilogue_lds_bytes(m->D) <= (size_t)3 * m->Hp * 16 * sizeof(float);
-    if (epi_ok) { pa->epi = *epi; pa->epi.on = 1; }
-    const int rc = launch_nsf2(pa, m, nullptr, x, ladj, n, stream);
-    if (rc == 0 && epi_ok) *epi_done = 1;
-    return rc;
 }
 
 #ifdef PMC_DEBUG_HOOKS
@@ -1076,6 +1017,10 @@ int pmc_launch_propose_inverse_nsf2(ProposeArgs* pa, const ScalerEpi* epi, int* 
 extern "C" int pmc_debug_nsf2_profile(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, long long* prof, void* stream) {
     ProposeArgs pa{};
     pa.prof = prof;
-    return launch_nsf2(&pa, m, z, x, ladj, n, (hipStream_t)stream) < 0 ? pmc_fail("pmc_debug_nsf2_profile: flow not covered") : 0;
+    pmc_inverse_plan_t plan;
+    if (m->n_out == 2 || pmc_plan_inverse(m, n, PMC_INVERSE_TRIANGULAR_DUO, PMC_FUSED_NO, 0, 0, &plan))
+        return pmc_fail("pmc_debug_nsf2_profile: flow not covered");
+    plan.fm = -1;
+    return pmc_launch_nsf2(&plan, &pa, m, z, x, ladj, n, (hipStream_t)stream);
 }
 #endif

@@ -11,15 +11,9 @@
 //     (tens of MFMAs) hide their latency -- no second register set, no copies;
 //   * keeps the prefetch of the NEXT tile's burst fragments issued right after the bursts.
 
-#include <stdlib.h>
 #include "maf_chain_rot.h"
 
-#define DG_WORDS(m) ((m)->nT * 4 + 8)      // LDS words of the tiles' degree table (4 per tile, padded)
-// + the two-wave sweep's permutation / rank-0 tables and its second x array (with alignment slack)
-#define TRI5_TT_WORDS(m) (((m)->nT + 2) * 16)  // the two-wave sweep's per-tile table (16 words per hidden tile, two rows of "no groups" behind)
-#define TRI5_YT_WORDS(m) ((m)->T * (((m)->nT + 2) * 4 + 1))   // per transform: the y offsets of every tile's groups, of rank 0
-#define TRI5_TABLE_WORDS(m) (((TRI5_TT_WORDS(m) + (m)->Dp + 2 * (m)->T + 3) & ~3) + (m)->Dp * 16 + ((TRI5_YT_WORDS(m) + 3) & ~3))
-#define TRI5_LDS_FLOATS(m, maxo) (2 * (m)->Dp * 16 + 2 * (m)->Hp * 16 + 2 * 256 + 2 * (3 + (maxo)) * 256 + TRI5_TABLE_WORDS(m))
+#include "inverse_lds.h"
 #include "propose_body.h"
 
 #define PX4 2
@@ -384,97 +378,20 @@ __global__ __launch_bounds__(64) void maf_inverse_tri4_kernel(pmc_maf_t m, const
     }
 }
 
-static bool tri5_wanted(const pmc_maf_t* m, int64_t n);
-static int launch_tri5(const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n,
-                       hipStream_t stream);
-
-// PMC_INVERSE_LANE=1: AUTO takes the lane-per-walker sweep (maf_inverse_tri6.hip) wherever it covers the flow (A/B
-// runs).  Default: the register-chain sweeps of this file for flows of < 16 hidden tiles (maf3 @ D = 32: 61-64 us
-// against 66-83 us for up to 8192 rows), the lane-per-walker sweep for the wider ones (pmc_tri6_preferred: D = 50 / maf6
-// 314 against 650 us, D = 128 / 8 transforms 0.69 ms per round) and for everything with more than 8 output tiles.
-static bool lane_sweep_enabled() {
-    static const bool on = pmc_env_int("PMC_INVERSE_LANE", 0) != 0;
-    return on;
-}
-
-int pmc_launch_inverse_tri4(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream,
-                            int variant) {
-    if (variant < 0 && (lane_sweep_enabled() || pmc_tri6_preferred(m))) {
-        const int rc = pmc_launch_tri6(nullptr, m, z, x, ladj, n, stream);
-        if (rc >= 0) return rc;
-    }
-    if (variant == 1) return launch_tri5(nullptr, m, z, x, ladj, n, stream);
-    if (variant < 0 && tri5_wanted(m, n)) {
-        const int rc = launch_tri5(nullptr, m, z, x, ladj, n, stream);
-        if (rc >= 0) return rc;
-    }
-    if (m->pk_per_transform * 4 > 0x7fffffffLL) return -1;         // 32-bit buffer offsets
-    const int maxo = m->nOT <= 4 ? 4 : 8;
-    const size_t lds = (size_t)(2 * m->Dp * 16 + 2 * m->Hp * 16 + 3 * 256 + maxo * 256 + DG_WORDS(m)) * sizeof(float);
-    if (m->nOT > 8 || lds > 160 * 1024) {
-        // wide flows (D > 64): lane-per-walker sweep; -1 if that does not cover the flow either (caller falls back)
-        return variant < 0 ? pmc_launch_tri6(nullptr, m, z, x, ladj, n, stream) : -1;
-    }
-#define LAUNCH(MO)                                                                                               \
-    {                                                                                                            \
-        if (lds > 48 * 1024) {                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri4_kernel<MO>),       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-            if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri4_kernel)");         \
-        }                                                                                                        \
-        hipLaunchKernelGGL((maf_inverse_tri4_kernel<MO>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds,        \
-                           stream, *m, z, x, ladj, n, ProposeArgs{});                                            \
-    }
-    if (maxo == 4) LAUNCH(4) else LAUNCH(8)
-#undef LAUNCH
-    return pmc_check_launch("maf_inverse_tri4_kernel");
-}
-
-// Proposal (mcmc.py:77-85) + flow inverse (mcmc.py:88) in one launch; -1 when this flow / size is not covered by
-// the fused instances (the caller then launches pmc_propose and pmc_maf_inverse).
-int pmc_launch_propose_inverse_tri4(int kind, const float* cur32, const double* mu, const double* inv_cov,
-                                    const double* chol, double nu, double sigma, double cn_a, const pmc_rng_t* rng,
-                                    double* prop64, double* quad, double* quad_prop, const pmc_maf_t* m, float* x,
-                                    float* ladj, int64_t n, hipStream_t stream, const double* adapt,
-                                    const ScalerEpi* epi, int* epi_done) {
-    if (epi_done) *epi_done = 0;
-    if (m->n_out == 23) {                                  // spline flows: the two-wave spline sweep has the fused instances
-        ProposeArgs pan{kind, cur32, mu, inv_cov, chol, nu, sigma, cn_a, *rng, prop64, quad, quad_prop, adapt};
-        return pmc_launch_propose_inverse_nsf2(&pan, epi, epi_done, m, x, ladj, n, stream);
-    }
-    if (m->n_out != 2 || !m->tri_ok || m->nOT > 8 || m->D > 64) return -1;
-    if (m->pk_per_transform * 4 > 0x7fffffffLL) return -1;
-    const int maxo = m->nOT <= 4 ? 4 : 8;
-    const size_t lds = (size_t)(2 * m->Dp * 16 + 2 * m->Hp * 16 + 3 * 256 + maxo * 256 + DG_WORDS(m)) * sizeof(float);
-    if (lds > 160 * 1024) return -1;
-    ProposeArgs pa{kind, cur32, mu, inv_cov, chol, nu, sigma, cn_a, *rng, prop64, quad, quad_prop, adapt};
-    // the scaler as the sweep's epilogue: its scratch aliases the two activation arrays of the walker set
-    const bool epi_ok = epi && epi_done && epi->s.D == m->D && !lane_sweep_enabled() &&
-                        scaler_epilogue_lds_bytes(m->D) <= (size_t)2 * m->Hp * 16 * sizeof(float);
-    if (epi_ok) { pa.epi = *epi; pa.epi.on = 1; *epi_done = 1; }
-    if (lane_sweep_enabled()) {
-        const int rc = pmc_launch_tri6(&pa, m, nullptr, x, ladj, n, stream);
-        if (rc >= 0) return rc;
-    }
-    if (tri5_wanted(m, n)) {
-        const int rc = launch_tri5(&pa, m, nullptr, x, ladj, n, stream);
-        if (rc >= 0) return rc;
-    }
-#define LAUNCHF(MO, FMV)                                                                                          \
-    {                                                                                                             \
-        if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri4_kernel<MO, FMV>),   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-            if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri4_kernel)");          \
-        }                                                                                                         \
-        hipLaunchKernelGGL((maf_inverse_tri4_kernel<MO, FMV>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds,    \
-                           stream, *m, (const float*)nullptr, x, ladj, n, pa);                                    \
-    }
-    if (m->D <= 16) { if (maxo == 4) LAUNCHF(4, 4) else LAUNCHF(8, 4) }
-    else if (m->D <= 32) { if (maxo == 4) LAUNCHF(4, 8) else LAUNCHF(8, 8) }
-    else { if (maxo == 4) LAUNCHF(4, 16) else LAUNCHF(8, 16) }
-#undef LAUNCHF
-    return pmc_check_launch("maf_inverse_tri4_kernel<fused proposal>");
+// The instance the plan names (inverse_plan.hip: PMC_SWEEP_SOLO); pa == nullptr: plain inverse of z, else proposal
+// (mcmc.py:77-85) + flow inverse (mcmc.py:88) in one launch, with the scaler as epilogue when pa->epi.on
+int pmc_launch_tri4(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream) {
+    if (plan->sweep != PMC_SWEEP_SOLO || (plan->fm != 0) != (pa != nullptr)) return pmc_fail("pmc_launch_tri4: not this sweep's plan");
+    const bool o4 = plan->maxo == 4;
+    const int fm = plan->fm;
+    const auto k = fm == 0 ? (o4 ? maf_inverse_tri4_kernel<4, 0> : maf_inverse_tri4_kernel<8, 0>)
+                 : fm == 4 ? (o4 ? maf_inverse_tri4_kernel<4, 4> : maf_inverse_tri4_kernel<8, 4>)
+                 : fm == 8 ? (o4 ? maf_inverse_tri4_kernel<4, 8> : maf_inverse_tri4_kernel<8, 8>)
+                           : (o4 ? maf_inverse_tri4_kernel<4, 16> : maf_inverse_tri4_kernel<8, 16>);
+    if (int e = pmc_launch_lds(k, "hipFuncSetAttribute(maf_inverse_tri4_kernel)", dim3((unsigned)((n + 15) / 16)), dim3(64),
+                               (size_t)plan->lds_bytes, stream, *m, z, x, ladj, n, pa ? *pa : ProposeArgs{})) return e;
+    return pmc_check_launch(pa ? "maf_inverse_tri4_kernel<fused proposal>" : "maf_inverse_tri4_kernel");
 }
 
 // ============================================================================================================
@@ -508,7 +425,6 @@ int pmc_launch_propose_inverse_tri4(int kind, const float* cur32, const double* 
 #define PXB 4                      // x tiles of the layer-0 product held in registers (D <= 64)
 #define TRI5_STAGE_FLOATS(MO) ((3 + (MO)) * 256)                 // one staging buffer: S0 | S1 | S2 (transposed, [lane][4]) | SO[MO] (natural)
 #define TRI5_SET_FLOATS(Dp, Hp, MO) (2 * (Dp) * 16 + 2 * (Hp) * 16 + 2 * 256 + 2 * TRI5_STAGE_FLOATS(MO))
-#define OOB_VOFF 0x40000000        // a lane offset beyond every image: the bounds-checked load returns zeros
 
 template <int MAXO, int FM>
 __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pmc_maf_t m, const float* __restrict__ in,
@@ -1018,54 +934,20 @@ __global__ __launch_bounds__(64 * (TRI5_NC + 1)) void maf_inverse_tri5_kernel(pm
     }
 }
 
-// -1: automatic (by size), 0: never, 1: always
-static int tri5_mode() {
-    static const int mode = pmc_env_int("PMC_INVERSE_DUO", -1);
-    return mode;
-}
-
-static bool tri5_wanted(const pmc_maf_t* m, int64_t n) {
-    const int mode = tri5_mode();
-    if (mode >= 0) return mode != 0;
-    // The right-looking two-wave sweep takes ~0.55 of the lone wave's time per round, and a launch beyond the 512
-    // resident walker sets simply runs its surplus workgroups as they find a CU: it is taken whenever its LDS fits.
-    (void)n;
-    const int maxo = m->nOT <= 4 ? 4 : 8;
-    return (size_t)TRI5_LDS_FLOATS(m, maxo) * sizeof(float) <= 160 * 1024;
-}
-
-// which of the two D <= 64 sweeps PMC_INVERSE_AUTO launches for n rows (bench.py names the kernel it times with it)
-extern "C" int pmc_maf_inverse_auto_is_duo(const pmc_maf_t* m, int64_t n) {
-    if (!m || m->n_out != 2 || !m->tri_ok || m->nOT > 8 || m->D > 64) return 0;
-    return tri5_wanted(m, n) ? 1 : 0;
-}
-
-// same contract as pmc_launch_propose_inverse_tri4 / pmc_launch_inverse_tri4 (pa == nullptr: plain inverse of z)
-static int launch_tri5(const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n,
-                       hipStream_t stream) {
-    if (m->n_out != 2 || !m->tri_ok || m->nOT > 8 || m->D > 64) return -1;
-    if (m->pk_per_transform * 4 * m->T >= (int64_t)OOB_VOFF) return -1;       // one buffer resource over the whole image
-    const int maxo = m->nOT <= 4 ? 4 : 8;
-    const size_t lds = (size_t)TRI5_LDS_FLOATS(m, maxo) * sizeof(float);
-    if (lds > 160 * 1024) return -1;
-    const ProposeArgs none{};
+// The instance the plan names (PMC_SWEEP_DUO); pa as for pmc_launch_tri4 (pa without a walker state: the profile entry)
+int pmc_launch_tri5(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream) {
+    if (plan->sweep != PMC_SWEEP_DUO || (plan->fm != 0 && !pa)) return pmc_fail("pmc_launch_tri5: not this sweep's plan");
+    const bool o4 = plan->maxo == 4;
+    const int fm = plan->fm;
+    const auto k = fm == 0 ? (o4 ? maf_inverse_tri5_kernel<4, 0> : maf_inverse_tri5_kernel<8, 0>)
+                 : fm == 4 ? (o4 ? maf_inverse_tri5_kernel<4, 4> : maf_inverse_tri5_kernel<8, 4>)
+                 : fm == 8 ? (o4 ? maf_inverse_tri5_kernel<4, 8> : maf_inverse_tri5_kernel<8, 8>)
+                           : (o4 ? maf_inverse_tri5_kernel<4, 16> : maf_inverse_tri5_kernel<8, 16>);
     const int64_t nsets = (n + 15) / 16;
-    const unsigned grid = (unsigned)((nsets + TRI5_NC - 1) / TRI5_NC);
-#define LAUNCH5(MO, FMV)                                                                                          \
-    {                                                                                                             \
-        if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri5_kernel<MO, FMV>),   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-            if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri5_kernel)");          \
-        }                                                                                                         \
-        hipLaunchKernelGGL((maf_inverse_tri5_kernel<MO, FMV>), dim3(grid), dim3(64 * (TRI5_NC + 1)), lds,          \
-                           stream, *m, z, x, ladj, n, pa ? *pa : none);                                           \
-    }
-    if (!pa || !pa->cur32) { if (maxo == 4) LAUNCH5(4, 0) else LAUNCH5(8, 0) }       // (pa without a walker state: the profile entry)
-    else if (m->D <= 16) { if (maxo == 4) LAUNCH5(4, 4) else LAUNCH5(8, 4) }
-    else if (m->D <= 32) { if (maxo == 4) LAUNCH5(4, 8) else LAUNCH5(8, 8) }
-    else { if (maxo == 4) LAUNCH5(4, 16) else LAUNCH5(8, 16) }
-#undef LAUNCH5
+    if (int e = pmc_launch_lds(k, "hipFuncSetAttribute(maf_inverse_tri5_kernel)", dim3((unsigned)((nsets + TRI5_NC - 1) / TRI5_NC)),
+                               dim3(64 * (TRI5_NC + 1)), (size_t)plan->lds_bytes, stream, *m, z, x, ladj, n,
+                               pa ? *pa : ProposeArgs{})) return e;
     return pmc_check_launch("maf_inverse_tri5_kernel");
 }
 
@@ -1075,6 +957,9 @@ extern "C" int pmc_debug_tri5_profile(const pmc_maf_t* m, const float* z, float*
                                       void* stream) {
     ProposeArgs pa{};
     pa.prof = prof;
-    return launch_tri5(&pa, m, z, x, ladj, n, (hipStream_t)stream) < 0 ? pmc_fail("pmc_debug_tri5_profile: flow not covered") : 0;
+    pmc_inverse_plan_t plan;
+    if (m->n_out != 2 || pmc_plan_inverse(m, n, PMC_INVERSE_TRIANGULAR_DUO, PMC_FUSED_NO, 0, 0, &plan))
+        return pmc_fail("pmc_debug_tri5_profile: flow not covered");
+    return pmc_launch_tri5(&plan, &pa, m, z, x, ladj, n, (hipStream_t)stream);
 }
 #endif

@@ -37,10 +37,10 @@
 // it is needed.
 //
 // Same arithmetic as the other sweeps up to the order of additions (float32; parity vs oracle 1e-5 relative).
-#include <stdlib.h>
 #include <type_traits>
 #include "maf_chain.h"
 #include "propose_body.h"
+#include "inverse_lds.h"
 
 typedef unsigned int u32x2_t6 __attribute__((ext_vector_type(2)));
 
@@ -187,7 +187,8 @@ __device__ __forceinline__ void wait_for(const int* flags, int which, int value)
     asm volatile("" ::: "memory");
 }
 
-constexpr int SPAD = 20;                                  // floats per walker row of a staging tile (16 + 4: conflict-free b128)
+constexpr int SPAD = TRI6_SPAD;                           // floats per walker row of a staging tile (inverse_lds.h)
+static_assert(F_COUNT == TRI6_FLAG_WORDS, "inverse_lds.h sizes the flag words");
 
 struct ChainState {
     f32x4 a0[4], a0n[4], acc1[4], acc2[4], o[2];
@@ -1026,98 +1027,23 @@ _Pragma("unroll") \
     }
 }
 
-static int tri6_hb(const pmc_maf_t* m) { return (m->lane16 && (m->lane16_fmt == 1 || m->lane16_fmt == 2)) ? m->lane16_fmt : 0; }
-
-static size_t tri6_lds_bytes(const pmc_maf_t* m, int ns, int hb = 0) {
-    const int h_floats = hb ? ((m->nT + 1) >> 1) * 256 : m->nT * 256;       // (Ops<HB>::act_floats: one activation array of a subset)
-    const int x_floats = hb ? m->Dp * 16 + ((m->nXT + 1) >> 1) * 256 : 2 * m->Dp * 16;   // y, x by rank (16-bit helpers: x over y in place + the helper's copy)
-    return (size_t)(ns * (x_floats + 3 * h_floats) + 3 * 2 * ns * 16 * tri6::SPAD + 2 * 2 * 16 * ns * tri6::SPAD) * sizeof(float)
-           + (tri6::F_COUNT + 8) * sizeof(int);          // (+ 8: the wavefronts' SIMD ids of the five-wave variant)
-}
-
-// walker subsets per workgroup: as few as keep the launch in one round (a chain wavefront takes the same time for 16
-// and for 64 walkers; the helpers' share grows with the subsets), as many as the LDS admits otherwise
-static int tri6_five_min() {
-    static const int v = pmc_env_int("PMC_TRI6_FIVE_MIN", 16);   // (A/B runs)
-    return v;
-}
-// the five-wavefront variant: plain float32 inverse of a flow with >= 16 hidden tiles, one or two subsets (the kernel must
-// stay within 256 registers: two wavefronts share a SIMD, and only one such workgroup fits a CU).  With 16-bit helper
-// operands the helpers are an order of magnitude below the chain: four wavefronts, a SIMD each.
-static bool tri6_five(const pmc_maf_t* m, bool fused, int hb = 0) {
-    return !fused && !hb && m->nT >= tri6_five_min() && !(m->reserved & PMC_MAF_VARIANT_LANE_FOUR);
-}
-static int tri6_subsets(const pmc_maf_t* m, int64_t n, bool fused, int hb = 0) {
-    static const int forced = pmc_env_int("PMC_TRI6_SUBSETS", 0);
-    const bool five = tri6_five(m, fused, hb);
-    int best = 0;
-    for (int ns = 1; ns <= (five ? 2 : 4); ns *= 2) {
-        const size_t lds = tri6_lds_bytes(m, ns, hb);
-        if (lds > 160 * 1024) break;
-        if (forced == ns) return ns;
-        best = ns;
-        // one workgroup per CU: the five-wave variant by construction, the four-wave instances by their registers (264-416)
-        if (!forced && (n + 16 * ns - 1) / (16 * ns) <= 256) break;
-    }
-    return best;
-}
-
-// AUTO's choice between this sweep and the register-chain sweeps of maf_inverse_tri4.hip for the flows both cover
-// (D <= 64): with >= 16 hidden tiles the five-wavefront variant is faster -- D = 50 / maf6 (25 tiles): 314 us per round
-// of <= 4096 walkers against 645-650 us of the two-wave sweep for <= 8192; D = 64 / maf3 (17 tiles): 120 against 160 us --
-// below that the two-wave sweep is (D = 32 / maf3, 9 tiles: 61-64 against 66-83 us).  The step then launches the
-// proposal and the scaler on their own (the fused instances of this kernel need more than 256 registers).
-bool pmc_tri6_preferred(const pmc_maf_t* m) {
-    if (m->n_out != 2 || !m->tri_ok || m->pk_per_transform * 4 > 0x7fffffffLL) return false;
-    const int hb = tri6_hb(m);
-    if (hb) return m->nT >= tri6_five_min() && tri6_lds_bytes(m, 1, hb) <= 160 * 1024;
-    return tri6_five(m, false) && tri6_lds_bytes(m, 1) <= 160 * 1024;
-}
-
-// same contract as pmc_launch_inverse_tri4 / pmc_launch_propose_inverse_tri4 (pa == nullptr: plain inverse of z);
-// -1: this flow is not covered (spline flows, degree groups wider than a tile, tiles beyond the LDS).
-// m->lane16 (pmc_maf_pack_lane16): the helpers multiply with 16-bit operands (Ops above).
-int pmc_launch_tri6(const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n,
-                    hipStream_t stream) {
-    if (m->n_out != 2 || !m->tri_ok) return -1;
-    if (m->pk_per_transform * 4 > 0x7fffffffLL) return -1;
-    if (pa && m->D > 64) return -1;
-    if (m->nT > 64) return -1;                           // (a lane per hidden tile holds its rank words)
-    const int hb = tri6_hb(m);
-    const int ns = tri6_subsets(m, n, pa != nullptr, hb);
-    if (ns == 0) return -1;
-    if (hb && m->Dp * 16 > 3 * ((m->nT + 1) >> 1) * 256) return -1;   // (the in-place re-rank parks x in the activation arrays)
-    const size_t lds = tri6_lds_bytes(m, ns, hb);
-    const ProposeArgs none{};
-    const unsigned grid = (unsigned)((n + 16 * ns - 1) / (16 * ns));
-    // wide flows (helpers saturated: their work grows with the hidden tiles, the chain's does not) get a fifth wavefront for
-    // the layer-0 partials; it needs the kernel in 256 registers (two wavefronts on one SIMD): plain inverse, one subset
-    const bool five = tri6_five(m, pa != nullptr, hb) && ns <= 2;
-#define LAUNCH6(NSV, FMV, NWV, HBV)                                                                                \
-    {                                                                                                              \
-        if (lds > 48 * 1024) {                                                                                     \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri6_kernel<NSV, FMV, NWV, HBV>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-            if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_inverse_tri6_kernel)");           \
-        }                                                                                                          \
-        hipLaunchKernelGGL((maf_inverse_tri6_kernel<NSV, FMV, NWV, HBV>), dim3(grid), dim3(64 * NWV), lds, stream, *m, z, x, \
-                           ladj, n, pa ? *pa : none);                                                              \
-    }
-#define LAUNCH6F(FMV)                                                                                              \
-    { if (ns == 1) LAUNCH6(1, FMV, 4, 0) else if (ns == 2) LAUNCH6(2, FMV, 4, 0) else LAUNCH6(4, FMV, 4, 0) }
-#define LAUNCH6H(HBV)                                                                                              \
-    { if (ns == 1) LAUNCH6(1, 0, 4, HBV) else if (ns == 2) LAUNCH6(2, 0, 4, HBV) else LAUNCH6(4, 0, 4, HBV) }
-    if (hb && pa) return -1;                             // (no fused instance with 16-bit helpers yet)
-    if (hb == 1) LAUNCH6H(1)
-    else if (hb == 2) LAUNCH6H(2)
-    else if (five) { if (ns == 1) LAUNCH6(1, 0, 5, 0) else LAUNCH6(2, 0, 5, 0) }
-    else if (!pa) LAUNCH6F(0)
-    else if (m->D <= 16) LAUNCH6F(4)
-    else if (m->D <= 32) LAUNCH6F(8)
-    else LAUNCH6F(16)
-#undef LAUNCH6H
-#undef LAUNCH6F
-#undef LAUNCH6
+// The instance the plan names (inverse_plan.hip: PMC_SWEEP_LANE -- subsets, wavefronts, helper operands, fused proposal);
+// pa == nullptr: plain inverse of z.  helper_fmt 1 / 2: the helpers multiply with the 16-bit operands of m->lane16
+// (pmc_maf_pack_lane16; Ops above).
+int pmc_launch_tri6(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream) {
+    const int ns = plan->subsets, hb = plan->helper_fmt, fm = plan->fm;
+    if (plan->sweep != PMC_SWEEP_LANE || (fm != 0 && (!pa || hb || plan->waves == 5)) || (hb && !m->lane16))
+        return pmc_fail("pmc_launch_tri6: not this sweep's plan");
+#define BY_SUBSETS(FMV, HBV) (ns == 1 ? maf_inverse_tri6_kernel<1, FMV, 4, HBV> : ns == 2 ? maf_inverse_tri6_kernel<2, FMV, 4, HBV> \
+                                                                                        : maf_inverse_tri6_kernel<4, FMV, 4, HBV>)
+    const auto k = hb == 1 ? BY_SUBSETS(0, 1) : hb == 2 ? BY_SUBSETS(0, 2)
+                 : plan->waves == 5 ? (ns == 1 ? maf_inverse_tri6_kernel<1, 0, 5, 0> : maf_inverse_tri6_kernel<2, 0, 5, 0>)
+                 : fm == 0 ? BY_SUBSETS(0, 0) : fm == 4 ? BY_SUBSETS(4, 0) : fm == 8 ? BY_SUBSETS(8, 0) : BY_SUBSETS(16, 0);
+#undef BY_SUBSETS
+    if (int e = pmc_launch_lds(k, "hipFuncSetAttribute(maf_inverse_tri6_kernel)", dim3((unsigned)((n + 16 * ns - 1) / (16 * ns))),
+                               dim3(64 * plan->waves), (size_t)plan->lds_bytes, stream, *m, z, x, ladj, n,
+                               pa ? *pa : ProposeArgs{})) return e;
     return pmc_check_launch("maf_inverse_tri6_kernel");
 }
 
@@ -1172,12 +1098,6 @@ extern "C" int pmc_maf_pack_lane16(const pmc_maf_t* m, int fmt, uint16_t* image,
     return pmc_check_launch("pack_lane16_kernel");
 }
 
-// whether PMC_INVERSE_AUTO (and with it the MCMC step) takes this sweep for the flow (bench.py names the kernel it times)
-extern "C" int pmc_maf_inverse_auto_is_lane(const pmc_maf_t* m) {
-    if (!m || m->n_out != 2 || !m->tri_ok) return 0;
-    return (m->nOT > 8 || pmc_tri6_preferred(m)) ? 1 : 0;
-}
-
 #ifdef PMC_DEBUG_HOOKS
 // measurement only (scripts/profile_tri6.py): cycle stamps of workgroup 0 -- prof[transform * nT + tile][wave 0..3][4]
 extern "C" int pmc_debug_tri6_profile(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, long long* prof,
@@ -1185,23 +1105,10 @@ extern "C" int pmc_debug_tri6_profile(const pmc_maf_t* m, const float* z, float*
     ProposeArgs pa{};
     pa.prof = prof;
     // (FM = 0 instances read nothing else of pa)
-    const int hb = tri6_hb(m);
-    const int ns = tri6_subsets(m, n, false, hb);
-    if (ns == 0 || m->n_out != 2 || !m->tri_ok) return pmc_fail("pmc_debug_tri6_profile: flow not covered");
-    const size_t lds = tri6_lds_bytes(m, ns, hb);
-    const unsigned grid = (unsigned)((n + 16 * ns - 1) / (16 * ns));
-    const bool five = tri6_five(m, false, hb) && ns <= 2;
-#define LP(NSV, NWV, HBV)                                                                                          \
-    {                                                                                                              \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri6_kernel<NSV, 0, NWV, HBV>), \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-        hipLaunchKernelGGL((maf_inverse_tri6_kernel<NSV, 0, NWV, HBV>), dim3(grid), dim3(64 * NWV), lds, (hipStream_t)stream, *m, z, \
-                           x, ladj, n, pa);                                                                        \
-    }
-    if (hb == 1) { if (ns == 1) LP(1, 4, 1) else if (ns == 2) LP(2, 4, 1) else LP(4, 4, 1) }
-    else if (hb == 2) { if (ns == 1) LP(1, 4, 2) else if (ns == 2) LP(2, 4, 2) else LP(4, 4, 2) }
-    else if (five) { if (ns == 1) LP(1, 5, 0) else LP(2, 5, 0) } else if (ns == 1) LP(1, 4, 0) else if (ns == 2) LP(2, 4, 0) else LP(4, 4, 0)
-#undef LP
-    return pmc_check_launch("maf_inverse_tri6_kernel<profile>");
+    pmc_inverse_plan_t plan;
+    const bool h16 = m->lane16 && (m->lane16_fmt == 1 || m->lane16_fmt == 2);
+    if (pmc_plan_inverse(m, n, h16 ? PMC_INVERSE_TRIANGULAR_LANE16 : PMC_INVERSE_TRIANGULAR_LANE, PMC_FUSED_NO, 0, 0, &plan))
+        return pmc_fail("pmc_debug_tri6_profile: flow not covered");
+    return pmc_launch_tri6(&plan, &pa, m, z, x, ladj, n, (hipStream_t)stream);
 }
 #endif

@@ -214,10 +214,11 @@ __global__ __launch_bounds__(64) void maf_inverse_tri_nsf_kernel(pmc_maf_t m, co
     if (ladj_out && lane < 16 && row0 + p < n) ladj_out[row0 + p] = ladj;
 }
 
-int pmc_launch_inverse_tri_nsf(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n,
-                               hipStream_t stream) {
-    const size_t lds = (size_t)(2 * m->Dp * 16 + 3 * m->Hp * 16 + 16 * 32 + 16 * 24) * sizeof(float);
-    if (lds > 160 * 1024) return pmc_fail("pmc_maf_inverse: flow too wide for one wave's LDS budget (160 KiB)");
+// The lone-wave spline sweep (inverse_plan.hip: PMC_SWEEP_NSF_SOLO)
+int pmc_launch_inverse_tri_nsf(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
+                               float* x, float* ladj, int64_t n, hipStream_t stream) {
+    if (plan->sweep != PMC_SWEEP_NSF_SOLO || pa) return pmc_fail("pmc_launch_inverse_tri_nsf: not this sweep's plan");
+    const size_t lds = (size_t)plan->lds_bytes;
     static size_t lds_set = 0;
     if (lds > 48 * 1024 && lds > lds_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_inverse_tri_nsf_kernel),

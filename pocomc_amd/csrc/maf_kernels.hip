@@ -28,6 +28,7 @@
 
 #include "maf_common.h"
 #include "propose_body.h"
+#include "inverse_lds.h"
 
 // ---------------------------------------------------------------------------
 // Dense pass of the hyper-network of one transform for 16 particles:
@@ -153,21 +154,6 @@ __global__ void maf_pack_kernel(const float* __restrict__ flat, const int32_t* _
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static size_t maf_lds_bytes(const pmc_maf_t& m, int n_rank_arrays) {
-    return (size_t)(n_rank_arrays * m.Dp * 16 + 3 * m.Hp * 16) * sizeof(float);
-}
-
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-    if (bytes > 160 * 1024) return pmc_fail("MAF too wide for one wave's LDS budget (160 KiB)");
-    if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    return 0;
-}
-
 extern "C" int pmc_maf_pack(const float* flat, const int32_t* pack_idx, float* packed, int64_t n_packed,
                             void* stream) {
     if (!flat || !pack_idx || !packed || n_packed <= 0) return pmc_fail("pmc_maf_pack: bad argument");
@@ -201,68 +187,40 @@ extern "C" int pmc_debug_forward_lone_wave(const pmc_maf_t* m, const float* x, f
                                            int64_t n, void* stream) {
     if (int e = check_maf(m)) return e;
     if (n == 0) return 0;
-    const size_t lds = maf_lds_bytes(*m, 3);
-    if (int e = set_lds(maf_dense_kernel<0>, lds)) return e;
-    hipLaunchKernelGGL(maf_dense_kernel<0>, dim3((unsigned)((n + 15) / 16)), dim3(64), lds, (hipStream_t)stream,
-                       *m, x, z, ladj, log_prob, n);
+    const size_t lds = pmc_lds_dense(m, 3);
+    if (lds > PMC_LDS_CAP) return pmc_fail("MAF too wide for one wave's LDS budget (160 KiB)");
+    if (int e = pmc_launch_lds(maf_dense_kernel<0>, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", dim3((unsigned)((n + 15) / 16)),
+                               dim3(64), lds, (hipStream_t)stream, *m, x, z, ladj, log_prob, n)) return e;
     return pmc_check_launch("maf_dense_kernel<forward>");
 }
 #endif
+
+// launches the instance a plan names (inverse_plan.hip)
+int pmc_launch_inverse(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                       float* ladj, int64_t n, hipStream_t stream) {
+    switch (plan->sweep) {
+        case PMC_SWEEP_SOLO: return pmc_launch_tri4(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_DUO: return pmc_launch_tri5(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_LANE: return pmc_launch_tri6(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_NSF_DUO: return pmc_launch_nsf2(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_NSF_SOLO: return pmc_launch_inverse_tri_nsf(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_DPASS_SPLINE: return pmc_launch_inverse_dpass_wg(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_DPASS_AFFINE: if (pa) break;
+            if (int e = pmc_launch_lds(maf_dense_kernel<1>, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", dim3((unsigned)((n + 15) / 16)),
+                                       dim3(64), (size_t)plan->lds_bytes, stream, *m, z, x, ladj, (float*)nullptr, n)) return e;
+            return pmc_check_launch("maf_dense_kernel<naive inverse>");
+    }
+    return pmc_fail("pmc_launch_inverse: the plan names no such instance");
+}
 
 extern "C" int pmc_maf_inverse(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n,
                                int algo, void* stream) {
     if (int e = check_maf(m)) return e;
     if (n == 0) return 0;
     if (!z || !x || n < 0) return pmc_fail("pmc_maf_inverse: bad argument");
-    if (m->n_out != 2) {
-        // spline flows: triangular sweep, or the D-pass algorithm of the reference (zuko) as cross-check
-        // and for layouts whose degree groups exceed a tile
-        // (the sweeps are built for the reference's 8 bins; other bin counts take zuko's own D-pass algorithm)
-        if (algo == PMC_INVERSE_AUTO) algo = (m->tri_ok && m->n_out == 23) ? PMC_INVERSE_TRIANGULAR : PMC_INVERSE_NAIVE;
-        if (algo == PMC_INVERSE_TRIANGULAR || algo == PMC_INVERSE_TRIANGULAR_SOLO || algo == PMC_INVERSE_TRIANGULAR_DUO) {
-            if (!m->tri_ok) return pmc_fail("pmc_maf_inverse: triangular sweep needs degree groups <= one tile");
-            if (m->n_out != 23) return pmc_fail("pmc_maf_inverse: the spline sweeps are built for 8 bins (PMC_INVERSE_NAIVE covers the others)");
-            // two wavefronts per 16 rows (D <= 64), else / on request the lone-wave sweep
-            if (algo != PMC_INVERSE_TRIANGULAR_SOLO) {
-                const int rc = pmc_launch_inverse_nsf2(m, z, x, ladj, n, (hipStream_t)stream);
-                if (rc >= 0) return rc;
-                if (algo == PMC_INVERSE_TRIANGULAR_DUO) return pmc_fail("pmc_maf_inverse: the two-wave spline sweep needs D <= 64 and its tiles in 160 KiB of LDS");
-            }
-            return pmc_launch_inverse_tri_nsf(m, z, x, ladj, n, (hipStream_t)stream);
-        }
-        if (algo == PMC_INVERSE_NAIVE) return pmc_launch_inverse_dpass_wg(m, z, x, ladj, n, (hipStream_t)stream);
-        return pmc_fail("pmc_maf_inverse: spline flows know PMC_INVERSE_TRIANGULAR (_SOLO, _DUO) and PMC_INVERSE_NAIVE");
-    }
-    const int asked = algo;
-    if (algo == PMC_INVERSE_AUTO) algo = m->tri_ok ? PMC_INVERSE_TRIANGULAR : PMC_INVERSE_NAIVE;
-    if (algo == PMC_INVERSE_TRIANGULAR) {
-        if (!m->tri_ok) return pmc_fail("pmc_maf_inverse: triangular sweep needs degree groups <= one tile");
-        // register-chain sweeps for output tiles <= 8 (D <= 64), the lane-per-walker sweep for the wider flows
-        const int rc = pmc_launch_inverse_tri4(m, z, x, ladj, n, (hipStream_t)stream);
-        if (rc >= 0) return rc;
-        if (asked != PMC_INVERSE_AUTO) return pmc_fail("pmc_maf_inverse: the triangular sweeps need their tiles in 160 KiB of LDS");
-        algo = PMC_INVERSE_NAIVE;                                   // (AUTO: the D-pass algorithm covers what is left)
-    } else if (algo == PMC_INVERSE_TRIANGULAR_SOLO || algo == PMC_INVERSE_TRIANGULAR_DUO) {
-        if (!m->tri_ok) return pmc_fail("pmc_maf_inverse: triangular sweep needs degree groups <= one tile");
-        if (m->nOT > 8) return pmc_fail("pmc_maf_inverse: this sweep needs D <= 64 and its tiles in 160 KiB of LDS");
-        const int rc = pmc_launch_inverse_tri4(m, z, x, ladj, n, (hipStream_t)stream, algo == PMC_INVERSE_TRIANGULAR_DUO);
-        if (rc >= 0) return rc;
-        return pmc_fail("pmc_maf_inverse: this sweep needs D <= 64 and its tiles in 160 KiB of LDS");
-    } else if (algo == PMC_INVERSE_TRIANGULAR_LANE || algo == PMC_INVERSE_TRIANGULAR_LANE16) {
-        pmc_maf_t mf = *m;
-        if (algo == PMC_INVERSE_TRIANGULAR_LANE) mf.lane16 = nullptr;       // (the float32 helpers, whatever is attached)
-        else if (!m->lane16 || (m->lane16_fmt != 1 && m->lane16_fmt != 2))
-            return pmc_fail("pmc_maf_inverse: PMC_INVERSE_TRIANGULAR_LANE16 needs pmc_maf_t.lane16 (pmc_maf_pack_lane16)");
-        const int rc = pmc_launch_tri6(nullptr, &mf, z, x, ladj, n, (hipStream_t)stream);
-        if (rc >= 0) return rc;
-        return pmc_fail("pmc_maf_inverse: the lane-per-walker sweep needs an affine flow whose degree groups fit a tile");
-    }
-    if (algo == PMC_INVERSE_NAIVE) {
-        const size_t lds = maf_lds_bytes(*m, 3);
-        if (int e = set_lds(maf_dense_kernel<1>, lds)) return e;
-        hipLaunchKernelGGL(maf_dense_kernel<1>, dim3((unsigned)((n + 15) / 16)), dim3(64), lds,
-                           (hipStream_t)stream, *m, z, x, ladj, (float*)nullptr, n);
-        return pmc_check_launch("maf_dense_kernel<naive inverse>");
-    }
-    return pmc_fail("pmc_maf_inverse: unknown algo");
+    pmc_inverse_plan_t plan;
+    if (int e = pmc_plan_inverse(m, n, algo, PMC_FUSED_NO, 0, 0, &plan)) return e;
+    pmc_maf_t mf = *m;
+    if (algo == PMC_INVERSE_TRIANGULAR_LANE) mf.lane16 = nullptr;       // (the float32 helpers, whatever is attached)
+    return pmc_launch_inverse(&plan, nullptr, &mf, z, x, ladj, n, (hipStream_t)stream);
 }

@@ -19,16 +19,30 @@ int pmc_check_launch(const char* what);
 
 int pmc_launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob, int64_t n,
                           hipStream_t stream, const int64_t* idx = nullptr);
-int pmc_launch_inverse_dpass_wg(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream);
-int pmc_launch_inverse_tri_nsf(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream);
-int pmc_launch_inverse_nsf2(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream);   // -1: not covered
-int pmc_launch_inverse_tri4(const pmc_maf_t* m, const float* z, float* x, float* ladj, int64_t n, hipStream_t stream, int variant = -1);   // variant: -1 by size, 0 solo, 1 duo
-bool pmc_tri6_preferred(const pmc_maf_t* m);     // AUTO takes the lane-per-walker sweep for this flow (maf_inverse_tri6.hip)
-int pmc_launch_propose_inverse_tri4(int kind, const float* cur32, const double* mu, const double* inv_cov,
-                                    const double* chol, double nu, double sigma, double cn_a, const pmc_rng_t* rng,
-                                    double* prop64, double* quad, double* quad_prop, const pmc_maf_t* m, float* x,
-                                    float* ladj, int64_t n, hipStream_t stream, const double* adapt = nullptr,
-                                    const struct ScalerEpi* epi = nullptr, int* epi_done = nullptr);   // (scaler_body.h)
+// The flow inverse (inverse_plan.hip): ONE function decides which kernel instance a call launches; the launchers below
+// launch what its plan names (pa: the fused proposal's arguments, propose_body.h; NULL for the plain inverse of z).
+// fused: PMC_FUSED_NO -- the plan of pmc_maf_inverse(algo), or non-zero with that call's error message; PMC_FUSED_STEP --
+// the fused proposal + inverse instance of the step, or sweep = PMC_SWEEP_NONE (return 0) when the stages are launched one
+// by one; epilogue: the scaler runs inside it (want_epilogue: the caller's scaler / prior qualify; scaler_D: their width);
+// PMC_FUSED_ANY -- the same for pmc_propose_inverse, which names the fused launch itself: AUTO's preference of the
+// lane-per-walker sweep (the proposal as a launch of its own) does not apply.
+enum { PMC_FUSED_NO = 0, PMC_FUSED_STEP = 1, PMC_FUSED_ANY = 2 };
+struct ProposeArgs;
+int pmc_plan_inverse(const pmc_maf_t* m, int64_t n, int algo, int fused, int want_epilogue, int scaler_D, pmc_inverse_plan_t* out);
+int pmc_launch_inverse(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                       float* ladj, int64_t n, hipStream_t stream);     // one switch over plan->sweep (maf_kernels.hip)
+int pmc_launch_tri4(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream);
+int pmc_launch_tri5(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream);
+int pmc_launch_tri6(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream);
+int pmc_launch_nsf2(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z, float* x,
+                    float* ladj, int64_t n, hipStream_t stream);
+int pmc_launch_inverse_tri_nsf(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
+                               float* x, float* ladj, int64_t n, hipStream_t stream);
+int pmc_launch_inverse_dpass_wg(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
+                                float* x, float* ladj, int64_t n, hipStream_t stream);
 int pmc_launch_propose_mfma(int kind, const float* cur32, const double* cur64, const double* mu,
                             const double* inv_cov, const double* chol, double nu, double sigma, double cn_a,
                             const pmc_rng_t* rng, double* prop64, float* prop32, double* quad, double* quad_prop,

@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <time.h>
 #include "pmc_internal.h"
-#include "scaler_body.h"
+#include "propose_body.h"
 
 #ifdef PMC_DEBUG_HOOKS                               // measurement builds only (make DEBUG_HOOKS=1): not in the product library
 static long long* g_epilogue_stamps = nullptr;       // pmc_debug_set_epilogue_stamps
@@ -98,22 +98,24 @@ static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double
     double* lp2 = (direct && pr && !devlik) ? s->h_logp_out : nullptr;
     pmc_done_t dn{s->h_done, (int64_t)rng->step + 1, s->done_ticket};
     const pmc_done_t* done = (direct && !devlik && s->h_done && s->done_ticket) ? &dn : nullptr;
-    if (s->preconditioned && !(s->no_fuse & 1) && !pmc_tri6_preferred(s->maf) &&
-        (s->inverse_algo == PMC_INVERSE_AUTO || s->inverse_algo == PMC_INVERSE_TRIANGULAR)) {
-        // proposal + flow inverse (+ scaler) in one launch (affine flows, D <= 64, fewer than 16 hidden tiles).  The wider
-        // flows take the lane-per-walker sweep with the proposal and the scaler as launches of their own: round 5 built the
-        // fused instances of that sweep (proposal prologue up to D = 128, scaler / prior / x' epilogue, float32 and 16-bit
-        // helpers) and measured them -- the proposal (~90 us per wavefront at D = 128) and the scaler (~40 us) are latency
-        // chains that cost the same inside the sweep's launch as in their own, and the float32 five-wavefront instance has
-        // no registers for them: config 5 255 (fused) against 300 steps/s, 16-bit helpers 420 against 415 (DESIGN.md
-        // appendix A); no_fuse & 2 keeps the scaler apart
-        ScalerEpi epi{};
-        const bool want_epi = !(s->no_fuse & 2) && s->scaler && s->scaler->low && s->scaler->high && s->scaler->kind &&
-                              s->scaler->log_width && (!s->scaler->scale || (s->scaler->mu && s->scaler->sigma)) &&
-                              (!pr || (pr->family && pr->loc && pr->scale && pr->D == D && pr->n_extended == 0));
-        // (the epilogues evaluate uniform / normal factors only: a prior with a factor of another family keeps the scaler
-        //  launch of its own, which counts, fills and hands over x' the same way)
-        if (want_epi) {
+    // proposal + flow inverse (+ scaler) in one launch where the plan has such an instance (inverse_plan.hip: affine flows of
+    // D <= 64 and < 16 hidden tiles, spline flows of D <= 64); no_fuse & 1 keeps the stages apart, no_fuse & 2 the scaler
+    const bool want_epi = s->preconditioned && !(s->no_fuse & 3) && s->scaler && s->scaler->low && s->scaler->high &&
+                          s->scaler->kind && s->scaler->log_width && (!s->scaler->scale || (s->scaler->mu && s->scaler->sigma)) &&
+                          (!pr || (pr->family && pr->loc && pr->scale && pr->D == D && pr->n_extended == 0));
+    // (the epilogues evaluate uniform / normal factors only: a prior with a factor of another family keeps the scaler
+    //  launch of its own, which counts, fills and hands over x' the same way)
+    pmc_inverse_plan_t plan{};
+    if (s->preconditioned && !(s->no_fuse & 1)) {
+        rc = pmc_plan_inverse(s->maf, n, s->inverse_algo, PMC_FUSED_STEP, want_epi, want_epi ? s->scaler->D : 0, &plan);
+        if (rc) return rc;
+    }
+    if (plan.sweep != PMC_SWEEP_NONE) {
+        ProposeArgs pa{s->kind, s->cur.theta32, mu, s->inv_cov, s->chol, nu, sigma, cn_a, *rng, s->p_theta64,
+                       tpcn ? s->quad : nullptr, tpcn ? s->p_quad : nullptr, adapt};
+        if (plan.epilogue) {
+            ScalerEpi& epi = pa.epi;
+            epi.on = 1;
             epi.s = *s->scaler;
             epi.have_prior = pr ? 1 : 0;
             if (pr) epi.pr = pmc_prior_un_t{pr->family, pr->loc, pr->scale, pr->D, pr->reserved};
@@ -131,13 +133,11 @@ static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double
             if (devlik) { epi.bad_count = s->clean_count; epi.bad_flag = nullptr; epi.fill_x = s->cur.x; }
         }
         if (s->ev_inv0) (void)hipEventRecord((hipEvent_t)s->ev_inv0, st);
-        rc = pmc_launch_propose_inverse_tri4(s->kind, s->cur.theta32, mu, s->inv_cov, s->chol, nu, sigma, cn_a, rng,
-                                             s->p_theta64, tpcn ? s->quad : nullptr, tpcn ? s->p_quad : nullptr, s->maf,
-                                             s->p_u32, s->p_ldjf, n, st, adapt, want_epi ? &epi : nullptr, &scaled);
-        if (rc > 0) return rc;
-        fused = (rc == 0);
-        if (!fused) scaled = 0;
-        if (fused && s->ev_inv1) (void)hipEventRecord((hipEvent_t)s->ev_inv1, st);
+        rc = pmc_launch_inverse(&plan, &pa, s->maf, nullptr, s->p_u32, s->p_ldjf, n, st);
+        if (rc) return rc;
+        fused = true;
+        scaled = plan.epilogue;
+        if (s->ev_inv1) (void)hipEventRecord((hipEvent_t)s->ev_inv1, st);
     }
     if (!fused) {
         rc = pmc_propose_adapt(s->kind, s->preconditioned ? s->cur.theta32 : nullptr,
@@ -258,10 +258,11 @@ extern "C" int pmc_propose_inverse(int kind, const float* cur32, const double* m
     if (kind == PMC_KIND_TPCN && (!mu || !inv_cov || !quad || !quad_prop))
         return pmc_fail("pmc_propose_inverse: tpCN needs mu, inv_cov and the quadratic-form outputs");
     if (n == 0) return 0;
-    const int rc = pmc_launch_propose_inverse_tri4(kind, cur32, mu, inv_cov, chol, nu, sigma, cn_a, rng, prop64, quad,
-                                                   quad_prop, maf, u_out, ladj, n, (hipStream_t)stream);
-    if (rc < 0) return pmc_fail("pmc_propose_inverse: only the affine flows with D <= 64 have a fused instance");
-    return rc;
+    pmc_inverse_plan_t plan;
+    if (int e = pmc_plan_inverse(maf, n, PMC_INVERSE_AUTO, PMC_FUSED_ANY, 0, 0, &plan)) return e;
+    if (plan.sweep == PMC_SWEEP_NONE) return pmc_fail("pmc_propose_inverse: only the affine flows with D <= 64 have a fused instance");
+    const ProposeArgs pa{kind, cur32, mu, inv_cov, chol, nu, sigma, cn_a, *rng, prop64, quad, quad_prop, nullptr};
+    return pmc_launch_inverse(&plan, &pa, maf, nullptr, u_out, ladj, n, (hipStream_t)stream);
 }
 
 extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask,
