@@ -400,6 +400,25 @@ typedef struct pmc_done {
 /* spin until *flag == value; non-zero return after timeout_s seconds */
 int pmc_wait_flag(const int64_t* flag, int64_t value, double timeout_s);
 
+/* Where the scaler (the launch of its own, or the epilogue of the fused sweep) leaves x', the finite mask and logp' next
+ * to the device arrays it always writes, and how it says so.  Every field may be NULL / 0: an all-zero hand-over writes the
+ * device arrays only.  pmc_step_handover returns the one pmc_step_pre uses. */
+typedef struct pmc_handover {
+    double* x_colmajor;       /* second copy of x' as f64 [D][n]: device (p_xT, lik_x) or pinned host (h_x) */
+    int32_t* finite_copy;     /* pinned host [n] */
+    double* logp_copy;        /* pinned host [n]; only with a device prior */
+    uint32_t* done_ticket;    /* completion word (pmc_done_t): device ticket, ... */
+    int64_t* done_flag;       /* ... pinned host word, ... */
+    int64_t done_value;       /* ... and what the last workgroup stores there */
+    uint32_t* bad_count;      /* device word, zero between launches: rows that do not reach the likelihood (x' or logp' not finite) */
+    int64_t* bad_flag;        /* pinned host word that takes the count in front of the completion word (pmc_step_t.h_clean) */
+    const double* fill_x;     /* the walkers' current x (device [n][D]): what those rows carry in x_colmajor (fill_rejected) */
+} pmc_handover_t;
+/* the mode that goes with a hand-over (pmc_step_handover) */
+#define PMC_HANDOVER_COPIES 0
+#define PMC_HANDOVER_DIRECT 1
+#define PMC_HANDOVER_DEVLIK 2
+
 /* Cache warmer for the likelihood's input (host side only; csrc/host_prefetch.hip).  n_threads helper threads, pinned to
  * cpus[i] (or unpinned when cpus == NULL) -- cores that share the L3 with the thread that calls the likelihood.  A job:
  * wait until the completion word *flag (i64, pinned host memory, written by the kernels as for pmc_wait_flag) reaches
@@ -670,6 +689,16 @@ int pmc_step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double si
  * needs its pmc_step_fill_next before the same range's pmc_step_post. */
 int pmc_step_pre_deferred(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream);
 int pmc_step_fill_next(const pmc_step_t* s, const pmc_rng_t* rng, double nu, void* stream);
+/* What pmc_step_pre of step number `step` decides about the hand-over of x', the finite mask, logp', the row count and the
+ * completion word (epilogue: 1 when the fused sweep's epilogue runs the scaler, 0 for the scaler launch of its own):
+ *   *out            what the scaler is given;
+ *   *mode           PMC_HANDOVER_COPIES: device arrays only, then D2H copies on the stream -- logp' (with a device prior), x'
+ *                   (p_xT, or p_x without one) and the finite mask;  _DIRECT: the kernels write pinned host memory, no copy;
+ *                   _DEVLIK: x' into lik_x, nothing to the host;
+ *   *clean_unknown  1: pmc_step_pre sets *h_clean = -1, the launch sequence does not count.
+ * Host logic only: reads the fields of *s, follows none of its pointers. */
+int pmc_step_handover(const pmc_step_t* s, int64_t step, int32_t epilogue, pmc_handover_t* out, int32_t* mode,
+                      int32_t* clean_unknown);
 /* mcmc.py:124-156 in one call: H2D logl', logp' -> accept + reductions -> [D2H sums, accept mask]. */
 int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask,
                   int copy_sums, void* stream);

@@ -65,6 +65,11 @@ class pmc_done_t(C.Structure):
     _fields_ = [("flag", c_p), ("value", C.c_int64), ("ticket", c_p)]
 
 
+class pmc_handover_t(C.Structure):
+    _fields_ = [("x_colmajor", c_p), ("finite_copy", c_p), ("logp_copy", c_p), ("done_ticket", c_p), ("done_flag", c_p),
+                ("done_value", C.c_int64), ("bad_count", c_p), ("bad_flag", c_p), ("fill_x", c_p)]
+
+
 class pmc_prior_t(C.Structure):
     _fields_ = [("family", c_p), ("loc", c_p), ("scale", c_p), ("D", C.c_int32), ("reserved", C.c_int32),
                 ("par", c_p), ("n_extended", C.c_int32), ("reserved2", C.c_int32)]
@@ -163,6 +168,7 @@ SIGNATURES = {
     "pmc_step_pre": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, f64, c_p]),
     "pmc_step_pre_deferred": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, f64, c_p]),
     "pmc_step_fill_next": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, c_p]),
+    "pmc_step_handover": (C.c_int, [P(pmc_step_t), i64, i32, P(pmc_handover_t), P(i32), P(i32)]),
     "pmc_step_post": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, C.c_int, C.c_int, c_p]),
     "pmc_step_lik_rows": (C.c_int, [P(pmc_step_t), c_p]),
     "pmc_step_prior_rows": (C.c_int, [P(pmc_step_t), c_p, C.c_int, c_p]),

@@ -123,13 +123,11 @@ __global__ __launch_bounds__(PROP_ROWS) void propose_kernel(
 #define SCL_THREADS 512
 __global__ __launch_bounds__(SCL_THREADS) void scaler_inverse_kernel(
     pmc_scaler_t s, const float* __restrict__ u_in, const double* __restrict__ u_in64,
-    double* __restrict__ u_out, double* __restrict__ x_out, double* __restrict__ x_colmajor,
-    double* __restrict__ ldj_out, int32_t* __restrict__ finite_out, int64_t n, pmc_prior_t pr,
-    double* __restrict__ logp_out, int32_t* __restrict__ finite_copy, double* __restrict__ logp_copy,
-    unsigned* __restrict__ done_ticket, long long* __restrict__ done_flag, long long done_value, pmc_scaler_extra ex) {
+    double* __restrict__ u_out, double* __restrict__ x_out, double* __restrict__ ldj_out,
+    int32_t* __restrict__ finite_out, int64_t n, pmc_prior_t pr, double* __restrict__ logp_out, pmc_handover_t h) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int D = s.D;
-    const bool keep_x = x_colmajor || logp_out;   // x' stays in LDS for the column-major copy / the fused prior
+    const bool keep_x = h.x_colmajor || logp_out; // x' stays in LDS for the column-major copy / the fused prior
     double* Jt = sm;                              // [SCL_ROWS][D]
     double* Xt = sm + (size_t)SCL_ROWS * D;       // [D][SCL_ROWS+1]  (only when keep_x)
     int* rowfin = reinterpret_cast<int*>(sm + (size_t)SCL_ROWS * D + (keep_x ? (size_t)D * (SCL_ROWS + 1) : 0));
@@ -142,16 +140,8 @@ __global__ __launch_bounds__(SCL_THREADS) void scaler_inverse_kernel(
         const int r = e / D, j = e - r * D;
         const int64_t g = (row0 + r) * D + j;
         double u = u_in ? (double)u_in[g] : u_in64[g];
-        double t, x, J;
-        t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
-        bound_inverse(s, j, t, x, J);
-        if (s.bc) {
-            // mcmc.py:94-97: wrap x, re-derive u from it, invert again
-            x = apply_bc(s, j, x);
-            u = bound_forward(s, j, x);
-            t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
-            bound_inverse(s, j, t, x, J);
-        }
+        double x, J;
+        scaler_element(s, j, u, x, J);
         u_out[g] = u;
         x_out[g] = x;
         if (keep_x) Xt[j * (SCL_ROWS + 1) + r] = x;
@@ -165,7 +155,7 @@ __global__ __launch_bounds__(SCL_THREADS) void scaler_inverse_kernel(
         ldj_out[row0 + tid] = l;
         const int fin = (rowfin[tid] && isfinite(l)) ? 1 : 0;
         finite_out[row0 + tid] = fin;
-        if (finite_copy) finite_copy[row0 + tid] = fin;
+        if (h.finite_copy) h.finite_copy[row0 + tid] = fin;
         if (logp_out) {
             // Prior.logpdf of the finite rows (mcmc.py:105-107), dimension after dimension like prior_logpdf_kernel
             double lp = -INFINITY;
@@ -174,42 +164,24 @@ __global__ __launch_bounds__(SCL_THREADS) void scaler_inverse_kernel(
                 for (int j = 0; j < D; ++j) lp += prior_term_any(pr, j, Xt[j * (SCL_ROWS + 1) + tid]);
             }
             logp_out[row0 + tid] = lp;
-            if (logp_copy) logp_copy[row0 + tid] = lp;
+            if (h.logp_copy) h.logp_copy[row0 + tid] = lp;
             if (!isfinite(lp)) rowfin[tid] = 0;
         }
         // rowfin: from here on "the row reaches the likelihood" (mcmc.py:100-109's two masks)
         if (!fin) rowfin[tid] = 0;
-        if (ex.bad_count && !rowfin[tid]) atomicAdd(ex.bad_count, 1u);
+        if (h.bad_count && !rowfin[tid]) atomicAdd(h.bad_count, 1u);
     }
-    if (x_colmajor) {
-        if (ex.fill_x) __syncthreads();
+    if (h.x_colmajor) {
+        if (h.fill_x) __syncthreads();
         // host copy of x' in column-major order ((n, D) Fortran array on the host): coalesced along rows.  A row that does
         // not reach the likelihood carries the walker's CURRENT x there when asked (pmc_step_t.fill_rejected): the host can
         // hand the whole block to the likelihood and drop those rows' values instead of gathering the others
         for (int e = tid; e < rows * D; e += SCL_THREADS) {
             const int j = e / rows, r = e - j * rows;
-            x_colmajor[(size_t)j * n + row0 + r] = (ex.fill_x && !rowfin[r]) ? ex.fill_x[(row0 + r) * D + j] : Xt[j * (SCL_ROWS + 1) + r];
+            h.x_colmajor[(size_t)j * n + row0 + r] = (h.fill_x && !rowfin[r]) ? h.fill_x[(row0 + r) * D + j] : Xt[j * (SCL_ROWS + 1) + r];
         }
     }
-    if (done_flag) {
-        // completion word in pinned host memory: every thread waits for the acknowledgement of its stores (agent-scope
-        // release; see scaler_body.h), the block draws a ticket, the last one publishes done_value with a system-scope
-        // release (the host spins on it instead of going through the runtime)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned t = __hip_atomic_fetch_add(done_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (t == gridDim.x - 1) {
-                *done_ticket = 0u;
-                if (ex.bad_count && ex.bad_flag) {        // (every block's count is in: its ticket came behind its atomicAdd)
-                    const unsigned bad = __hip_atomic_exchange(ex.bad_count, 0u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-                    *ex.bad_flag = (long long)bad;
-                }
-                __threadfence_system();
-                __hip_atomic_store(done_flag, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
+    handover_complete(h, nullptr, tid);
 }
 
 __global__ __launch_bounds__(256) void scaler_forward_kernel(pmc_scaler_t s, const double* __restrict__ x,
@@ -770,32 +742,29 @@ extern "C" int pmc_scaler_inverse_prior(const pmc_scaler_t* s, const pmc_prior_t
                                         const double* u_in64, double* u_out, double* x, double* x_colmajor,
                                         double* logdetj, int32_t* finite, double* logp, int32_t* finite_copy,
                                         double* logp_copy, const pmc_done_t* done, int64_t n, void* stream) {
-    return pmc_scaler_inverse_prior_ex(s, prior, u_in, u_in64, u_out, x, x_colmajor, logdetj, finite, logp, finite_copy, logp_copy,
-                                       done, n, stream, nullptr);
+    // (no count, no fill: those are the step's)
+    const pmc_handover_t h{x_colmajor, finite_copy, logp_copy, done ? done->ticket : nullptr, done ? done->flag : nullptr,
+                           done ? done->value : 0, nullptr, nullptr, nullptr};
+    return pmc_scaler_inverse_prior_ex(s, prior, u_in, u_in64, u_out, x, logdetj, finite, logp, &h, n, stream);
 }
 
-int pmc_scaler_inverse_prior_ex(const pmc_scaler_t* s, const pmc_prior_t* prior, const float* u_in,
-                                const double* u_in64, double* u_out, double* x, double* x_colmajor,
-                                double* logdetj, int32_t* finite, double* logp, int32_t* finite_copy,
-                                double* logp_copy, const pmc_done_t* done, int64_t n, void* stream, const pmc_scaler_extra* extra) {
+int pmc_scaler_inverse_prior_ex(const pmc_scaler_t* s, const pmc_prior_t* prior, const float* u_in, const double* u_in64,
+                                double* u_out, double* x, double* logdetj, int32_t* finite, double* logp,
+                                const pmc_handover_t* h, int64_t n, void* stream) {
     if (int e = check_scaler(s)) return e;
     if (n == 0) return 0;
     if ((!u_in) == (!u_in64)) return pmc_fail("pmc_scaler_inverse: exactly one of u_in / u_in64 must be given");
-    if (!u_out || !x || !logdetj || !finite || n < 0) return pmc_fail("pmc_scaler_inverse: bad argument");
+    if (!u_out || !x || !logdetj || !finite || !h || n < 0) return pmc_fail("pmc_scaler_inverse: bad argument");
     if ((prior != nullptr) != (logp != nullptr)) return pmc_fail("pmc_scaler_inverse_prior: prior and logp go together");
-    if (logp_copy && !logp) return pmc_fail("pmc_scaler_inverse_prior: logp_copy without logp");
+    if (h->logp_copy && !logp) return pmc_fail("pmc_scaler_inverse_prior: logp_copy without logp");
     if (prior && (!prior->family || !prior->loc || !prior->scale || prior->D != s->D))
         return pmc_fail("pmc_scaler_inverse_prior: bad prior descriptor");
     if (prior && (prior->n_extended < 0 || (prior->n_extended > 0 && !prior->par)))
         return pmc_fail("pmc_scaler_inverse_prior: factors other than uniform / normal need the parameter table (par)");
     pmc_prior_t pr_val = {};
     if (prior) pr_val = *prior;
-    pmc_scaler_extra ex{};
-    // (the count travels with the completion word, the fill with the host copy -- or, for a device likelihood, both stay
-    //  on the device: no flag, no completion word)
-    if (extra && x_colmajor && (done || !extra->bad_flag)) ex = *extra;
     const size_t lds = (size_t)SCL_ROWS * s->D * sizeof(double) + SCL_ROWS * sizeof(int) +
-                       ((x_colmajor || logp) ? (size_t)s->D * (SCL_ROWS + 1) * sizeof(double) : 0);
+                       ((h->x_colmajor || logp) ? (size_t)s->D * (SCL_ROWS + 1) * sizeof(double) : 0);
     if (lds > 160 * 1024 || s->D > 1024) return pmc_fail("pmc_scaler_inverse: n_dim too large");
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scaler_inverse_kernel),
@@ -803,9 +772,7 @@ int pmc_scaler_inverse_prior_ex(const pmc_scaler_t* s, const pmc_prior_t* prior,
         if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(scaler_inverse_kernel)");
     }
     hipLaunchKernelGGL(scaler_inverse_kernel, dim3((unsigned)((n + SCL_ROWS - 1) / SCL_ROWS)), dim3(SCL_THREADS), lds,
-                       (hipStream_t)stream, *s, u_in, u_in64, u_out, x, x_colmajor, logdetj, finite, n, pr_val, logp, finite_copy,
-                       logp_copy, done ? done->ticket : nullptr, done ? (long long*)done->flag : nullptr,
-                       done ? (long long)done->value : 0LL, ex);
+                       (hipStream_t)stream, *s, u_in, u_in64, u_out, x, logdetj, finite, n, pr_val, logp, *h);
     return pmc_check_launch("scaler_inverse_kernel");
 }
 

@@ -140,6 +140,48 @@ __device__ __forceinline__ double prior_term(const P& pr, int j, double xv) {
 }
 
 
+// one element of the scaler inverse: u in; u (re-derived from x when boundary conditions apply), x and the Jacobian term J
+// out.  Shared by scaler_inverse_kernel and the epilogue of the fused sweeps.
+__device__ __forceinline__ void scaler_element(const pmc_scaler_t& s, int j, double& u, double& x, double& J) {
+    double t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
+    bound_inverse(s, j, t, x, J);
+    if (s.bc) {
+        // mcmc.py:94-97: wrap x, re-derive u from it, invert again
+        x = apply_bc(s, j, x);
+        u = bound_forward(s, j, x);
+        t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
+        bound_inverse(s, j, t, x, J);
+    }
+}
+
+// The completion word of a hand-over (pmc_handover_t.done_flag, pinned host memory: the host spins on it instead of going
+// through the runtime), behind a workgroup's last store; every thread of the workgroup calls it (it synchronises).
+// Every thread waits for the acknowledgement of its own stores (agent-scope release: pinned host memory is not cached on
+// the device, so there is nothing to write back), the workgroup draws a ticket (agent-scope acq_rel), the last one moves
+// the row count and publishes the word with a system-scope release.  A __threadfence_system() in the fence's place made
+// every one of the ~400 workgroups write back and invalidate the whole L2: 12 us of the launch (timing-only builds of this
+// file), 6 us in scripts/micro/pcie_store.hip, which also checks that the host never sees the word before the data (0 stale
+// words in 8000 launches x 208 k words with either fence).
+// stamps: measurement only (ScalerEpi::stamps), slot 5 between the barrier and the ticket; NULL elsewhere.
+__device__ __forceinline__ void handover_complete(const pmc_handover_t& h, long long* stamps, int tid) {
+    if (!h.done_flag) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (stamps && tid == 0) stamps[blockIdx.x * 8 + 5] = wall_clock64();
+    if (tid == 0) {
+        const unsigned t = __hip_atomic_fetch_add(h.done_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == gridDim.x - 1) {
+            *h.done_ticket = 0u;
+            if (h.bad_count && h.bad_flag) {              // (every block's count is in: its ticket came behind its atomicAdd)
+                const unsigned bad = __hip_atomic_exchange(h.bad_count, 0u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+                *h.bad_flag = (long long)bad;
+            }
+            __threadfence_system();
+            __hip_atomic_store(h.done_flag, (int64_t)h.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The scaler (+ prior) as the epilogue of a sweep: what scaler_inverse_kernel does for 64 rows, for the 16 walkers
 // of one workgroup.  X: the sweep's result in LDS, by rank of the first transform ([rank][16], lidx); rof: rank of
@@ -149,11 +191,8 @@ struct ScalerEpi {
     int on, have_prior;
     pmc_scaler_t s;
     pmc_prior_un_t pr;
-    double* u_out; double* x_out; double* x_colmajor; double* ldj_out; int32_t* finite_out;
-    double* logp_out; int32_t* finite_copy; double* logp_copy;
-    unsigned* done_ticket; long long* done_flag; long long done_value;
-    unsigned* bad_count; long long* bad_flag;       // optional: rows that are not clean (pmc_step_t.h_clean)
-    const double* fill_x;                           // pmc_step_t.fill_rejected: the walkers' current x (device [n][D]) or NULL
+    double* u_out; double* x_out; double* ldj_out; int32_t* finite_out; double* logp_out;
+    pmc_handover_t h;                               // x' (column-major), finite mask, logp', row count and completion word
     long long* stamps;                              // measurement only (pmc_debug_set_epilogue_stamps): [block][8] of the 100 MHz clock
 };
 
@@ -161,40 +200,13 @@ static inline size_t scaler_epilogue_lds_bytes(int D) {
     return (size_t)(2 * 16 * D + D * 17) * sizeof(double) + 16 * sizeof(int);
 }
 
-// one element (walker r of the workgroup's 16, feature j) of the epilogue: the bijector, its Jacobian term, the boundary
-// conditions, the prior factor; u / x to the device arrays, x to the host's column-major array when asked (direct_cm),
-// the row tables Jt / Pt / rowfin (and Xt unless direct_cm) in LDS
-__device__ __forceinline__ void scaler_epilogue_element(const ScalerEpi& e, double* Jt, double* Pt, double* Xt, int* rowfin,
-                                                        float u32, int r, int j, int64_t row0, int64_t n, int D, bool direct_cm) {
-    const pmc_scaler_t& s = e.s;
-    const int64_t g = (row0 + r) * D + j;
-    double u = (double)u32;
-    double t, x, J;
-    t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
-    bound_inverse(s, j, t, x, J);
-    if (s.bc) {
-        // mcmc.py:94-97: wrap x, re-derive u from it, invert again
-        x = apply_bc(s, j, x);
-        u = bound_forward(s, j, x);
-        t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
-        bound_inverse(s, j, t, x, J);
-    }
-    e.u_out[g] = u;
-    e.x_out[g] = x;
-    if (direct_cm) { if (e.x_colmajor) e.x_colmajor[(size_t)j * n + row0 + r] = x; }
-    else Xt[j * 17 + r] = x;
-    Jt[r * D + j] = J;
-    if (e.have_prior) Pt[r * D + j] = prior_term(e.pr, j, x);
-    if (!isfinite(x)) rowfin[r] = 0;
-}
-
 // the rows' part: log-determinant (numpy's pairwise sum of the Jacobian terms), finite mask, Prior.logpdf; then the
-// column-major store of x (unless the elements stored it already: cm_done) and the completion word.  Every thread of
-// the workgroup calls it behind a barrier that follows the last element.
+// column-major store of x and the completion word.  Every thread of the workgroup calls it behind a barrier that follows
+// the last element.
 __device__ __forceinline__ void scaler_epilogue_rows(const ScalerEpi& e, const double* Jt, const double* Pt, const double* Xt,
-                                                     int* rowfin, int64_t row0, int64_t n, int D, int tid, int nthr,
-                                                     bool cm_done) {
+                                                     int* rowfin, int64_t row0, int64_t n, int D, int tid, int nthr) {
     const pmc_scaler_t& s = e.s;
+    const pmc_handover_t& h = e.h;
     const int rows = (int)min((int64_t)16, n - row0);
     // Eight lanes per walker (nthr = 128: all 16 walkers at once; 64: two passes).  Lane i of a walker's group keeps numpy's
     // accumulator r_i of the pairwise sum (np_pairwise_leaf: a[i], a[i+8], ... in index order), the group combines them in
@@ -239,57 +251,35 @@ __device__ __forceinline__ void scaler_epilogue_rows(const ScalerEpi& e, const d
             e.ldj_out[row0 + r] = l;
             const int fin = (rowfin[r] && isfinite(l)) ? 1 : 0;
             e.finite_out[row0 + r] = fin;
-            if (e.finite_copy) e.finite_copy[row0 + r] = fin;
+            if (h.finite_copy) h.finite_copy[row0 + r] = fin;
             bool clean = fin != 0;
             if (e.have_prior) {
                 // Prior.logpdf of the finite rows (mcmc.py:105-107): the terms dimension after dimension
                 const double lp = fin ? lps : -INFINITY;
                 e.logp_out[row0 + r] = lp;
-                if (e.logp_copy) e.logp_copy[row0 + r] = lp;
+                if (h.logp_copy) h.logp_copy[row0 + r] = lp;
                 clean = clean && isfinite(lp);
             }
-            if (e.bad_count && !clean) atomicAdd(e.bad_count, 1u);            // (rows that the host's masks would drop: rare)
-            if (e.fill_x) rowfin[r] = clean ? 1 : 0;                                // (from here on: "the row reaches the likelihood")
+            if (h.bad_count && !clean) atomicAdd(h.bad_count, 1u);            // (rows that the host's masks would drop: rare)
+            if (h.fill_x) rowfin[r] = clean ? 1 : 0;                                // (from here on: "the row reaches the likelihood")
         }
     }
-    if (e.fill_x) __syncthreads();
+    if (h.fill_x) __syncthreads();
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 2] = wall_clock64();
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 3] = wall_clock64();
-    if (e.x_colmajor && !cm_done) {
+    if (h.x_colmajor) {
         // element el = j * rows + r; (j, r) step by nthr = dj * rows + dr without a division per element
         const int dj = nthr / rows, dr = nthr - dj * rows;
         int j = tid / rows, r = tid - j * rows;
         for (int el = tid; el < rows * D; el += nthr) {
             // (a row that does not reach the likelihood: the walker's current x in the host copy, see scaler_inverse_kernel)
-            e.x_colmajor[(size_t)j * n + row0 + r] = (e.fill_x && !rowfin[r]) ? e.fill_x[(row0 + r) * D + j] : Xt[j * 17 + r];
+            h.x_colmajor[(size_t)j * n + row0 + r] = (h.fill_x && !rowfin[r]) ? h.fill_x[(row0 + r) * D + j] : Xt[j * 17 + r];
             j += dj; r += dr;
             if (r >= rows) { r -= rows; ++j; }
         }
     }
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 4] = wall_clock64();
-    if (e.done_flag) {
-        // Every thread waits for the acknowledgement of its own stores (agent-scope release: pinned host memory is not
-        // cached on the device, so there is nothing to write back), the workgroup draws a ticket (agent-scope acq_rel), the
-        // last one publishes the word with a system-scope release.  A __threadfence_system() here made every one of the ~400
-        // workgroups write back and invalidate the whole L2: 12 us of the launch (timing-only builds of this file), 6 us in
-        // scripts/micro/pcie_store.hip, which also checks that the host never sees the word before the data (0 stale words
-        // in 8000 launches x 208 k words with either fence).
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 5] = wall_clock64();
-        if (tid == 0) {
-            const unsigned t = __hip_atomic_fetch_add(e.done_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (t == gridDim.x - 1) {
-                *e.done_ticket = 0u;
-                if (e.bad_count && e.bad_flag) {          // (every block's count is in: its ticket came behind its atomicAdd)
-                    const unsigned bad = __hip_atomic_exchange(e.bad_count, 0u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-                    *e.bad_flag = (long long)bad;
-                }
-                __threadfence_system();
-                __hip_atomic_store(e.done_flag, e.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
+    handover_complete(h, e.stamps, tid);
 }
 
 template <class LIDX>
@@ -308,17 +298,24 @@ __device__ __forceinline__ void scaler_epilogue(const ScalerEpi& e, const float*
         const int dr = nthr / D, dj = nthr - dr * D;
         int r = tid / D, j = tid - r * D;
         for (int el = tid; el < rows * D; el += nthr) {
-            scaler_epilogue_element(e, Jt, Pt, Xt, rowfin, X[lidx_of(rof[j], r)], r, j, row0, n, D, false);
+            // the bijector, its Jacobian term, the boundary conditions, the prior factor: u / x to the device arrays, the
+            // row tables Jt / Pt / Xt / rowfin in LDS
+            double u = (double)X[lidx_of(rof[j], r)], x, J;
+            scaler_element(e.s, j, u, x, J);
+            const int64_t g = (row0 + r) * D + j;
+            e.u_out[g] = u;
+            e.x_out[g] = x;
+            Xt[j * 17 + r] = x;
+            Jt[r * D + j] = J;
+            if (e.have_prior) Pt[r * D + j] = prior_term(e.pr, j, x);
+            if (!isfinite(x)) rowfin[r] = 0;
             r += dr; j += dj;
             if (j >= D) { j -= D; ++r; }
         }
     }
     __syncthreads();
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 1] = wall_clock64();
-    scaler_epilogue_rows(e, Jt, Pt, Xt, rowfin, row0, n, D, tid, nthr, false);
+    scaler_epilogue_rows(e, Jt, Pt, Xt, rowfin, row0, n, D, tid, nthr);
 }
-
-// the progressive form's tables only (no Xt): [16][D] Jacobian terms, [16][D] prior terms, 16 row flags
-static inline size_t scaler_progressive_lds_bytes(int D) { return (size_t)(2 * 16 * D) * sizeof(double) + 16 * sizeof(int); }
 
 #endif

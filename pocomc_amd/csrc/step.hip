@@ -41,6 +41,59 @@ extern "C" int pmc_step_fill_next(const pmc_step_t* s, const pmc_rng_t* rng, dou
     return 0;
 }
 
+// host_direct: the kernels read mu from / write x', finite, logp' to pinned host memory themselves
+static bool step_direct(const pmc_step_t* s) { return s->host_direct && !s->p_xT; }
+
+// the pre-step's device likelihood: x' stays on the device only behind a prior that is evaluated there too
+static bool step_devlik(const pmc_step_t* s) { return s->lik_x && (s->prior || s->prior_rows); }
+
+// where x' goes and where logl' / logp' come from (PMC_HANDOVER_*); devlik: the caller's, see pmc_step_post
+static int step_mode(const pmc_step_t* s, bool devlik) {
+    return devlik ? PMC_HANDOVER_DEVLIK : step_direct(s) ? PMC_HANDOVER_DIRECT : PMC_HANDOVER_COPIES;
+}
+
+// THE decision of the pre-step of step number `step` about x', the finite mask, logp', the row count and the completion
+// word (pmc_step_handover has the outputs); epilogue: the plan's fused sweep runs the scaler, else a launch of its own.
+//   device likelihood with a device prior: x' (rejected rows filled) into lik_x, the count into clean_count; nothing goes
+//   to the host and no completion word follows (the likelihood is the next operation on the stream).  A prior that is the
+//   caller's GPU callable (prior_rows): the same hand-over with the finite mask as the only gate -- pmc_step_prior_rows
+//   closes the prior's behind the callable.
+//   host_direct: everything into pinned host memory, the completion word behind it where the caller gave one; the rows
+//   that do not reach the likelihood are counted into *h_clean in front of the word (and their host rows filled when asked).
+// One asymmetry, kept as it is: the fused epilogue counts whenever it has the word, h_clean and clean_count -- without a
+// device prior too (the rows whose x' is not finite), and without a host x' -- while the launch of its own counts only
+// when it hands x' over and evaluates the prior.  (The epilogues evaluate uniform / normal factors only: a prior with a
+// factor of another family keeps the launch of its own, which counts, fills and hands over x' the same way.)
+static void step_handover(const pmc_step_t* s, int64_t step, bool epilogue, pmc_handover_t* h, int32_t* mode,
+                          int32_t* clean_unknown) {
+    const bool devlik = step_devlik(s);
+    *mode = step_mode(s, devlik);
+    const bool host = *mode == PMC_HANDOVER_DIRECT;
+    *h = pmc_handover_t{};
+    h->x_colmajor = devlik ? s->lik_x : step_direct(s) ? s->h_x : s->p_xT;
+    if (host) {
+        h->finite_copy = s->h_fin;
+        if (s->prior) h->logp_copy = s->h_logp_out;
+    }
+    const bool done = host && s->h_done && s->done_ticket;
+    if (done) { h->done_ticket = s->done_ticket; h->done_flag = s->h_done; h->done_value = step + 1; }
+    const bool word = done && s->h_clean && s->clean_count;             // the count has somewhere to go
+    if (word && (epilogue || (h->x_colmajor && s->prior))) {
+        h->bad_count = s->clean_count;
+        h->bad_flag = s->h_clean;
+        if (s->fill_rejected && h->x_colmajor) h->fill_x = s->cur.x;
+    }
+    if (devlik) { h->bad_count = s->clean_count; h->bad_flag = nullptr; h->fill_x = s->cur.x; }
+    *clean_unknown = s->h_clean && !(word && h->x_colmajor && (epilogue || s->prior));
+}
+
+extern "C" int pmc_step_handover(const pmc_step_t* s, int64_t step, int32_t epilogue, pmc_handover_t* out, int32_t* mode,
+                                 int32_t* clean_unknown) {
+    if (!s || !out || !mode || !clean_unknown) return pmc_fail("pmc_step_handover: null argument");
+    step_handover(s, step, epilogue != 0, out, mode, clean_unknown);
+    return 0;
+}
+
 // fill_next = false: the caller enqueues pmc_step_fill_next itself, behind whatever the host waits for first (the pipeline:
 // behind the last lane's pre-step)
 static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream,
@@ -71,45 +124,35 @@ static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double
         if (prefill && fill_next) return pmc_step_fill_next(s, rng_in, nu, stream);
         return 0;
     };
-    // host_direct: the kernels read mu from / write x', finite, logp' to pinned host memory themselves
-    const bool direct = s->host_direct && !s->p_xT;
     const double* mu = s->mu;
     // adaptation on the device: sigma, cn_a and mu come from adapt_state (pmc_step_post keeps it up to date)
     const double* adapt = (s->adapt_state && s->adapt_mode) ? s->adapt_state : nullptr;
     if (!adapt && tpcn && s->h_mu) {
-        if (direct) mu = s->h_mu;
+        if (step_direct(s)) mu = s->h_mu;
         else if (hipMemcpyAsync((void*)s->mu, s->h_mu, (size_t)D * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_pre: H2D mu");
     }
     int rc;
-    bool fused = false;
-    int scaled = 0;                                  // the sweep's epilogue applied the scaler (+ prior) as well
     // scaler inverse and (when it runs on the device) Prior.logpdf: one launch, or the epilogue of the fused sweep
     const pmc_prior_t* pr = s->prior;
     double* lp = pr ? s->p_logp : nullptr;
-    // device likelihood with a device prior: x' (rejected rows filled) into lik_x, the count into clean_count; nothing goes
-    // to the host and no completion word follows (the likelihood is the next operation on the stream)
-    // (a prior that is the caller's GPU callable, pmc_step_t.prior_rows: the same hand-over with the finite mask as the only
-    //  gate -- pmc_step_prior_rows closes the prior's behind the callable)
-    const bool devlik = s->lik_x && (pr || s->prior_rows);
-    if (devlik && !s->clean_count) return pmc_fail("pmc_step_pre: a device likelihood needs clean_count");
-    double* xT = devlik ? s->lik_x : direct ? s->h_x : s->p_xT;
-    int32_t* fin2 = (direct && !devlik) ? s->h_fin : nullptr;
-    double* lp2 = (direct && pr && !devlik) ? s->h_logp_out : nullptr;
-    pmc_done_t dn{s->h_done, (int64_t)rng->step + 1, s->done_ticket};
-    const pmc_done_t* done = (direct && !devlik && s->h_done && s->done_ticket) ? &dn : nullptr;
+    if (step_devlik(s) && !s->clean_count) return pmc_fail("pmc_step_pre: a device likelihood needs clean_count");
     // proposal + flow inverse (+ scaler) in one launch where the plan has such an instance (inverse_plan.hip: affine flows of
     // D <= 64 and < 16 hidden tiles, spline flows of D <= 64); no_fuse & 1 keeps the stages apart, no_fuse & 2 the scaler
     const bool want_epi = s->preconditioned && !(s->no_fuse & 3) && s->scaler && s->scaler->low && s->scaler->high &&
                           s->scaler->kind && s->scaler->log_width && (!s->scaler->scale || (s->scaler->mu && s->scaler->sigma)) &&
                           (!pr || (pr->family && pr->loc && pr->scale && pr->D == D && pr->n_extended == 0));
-    // (the epilogues evaluate uniform / normal factors only: a prior with a factor of another family keeps the scaler
-    //  launch of its own, which counts, fills and hands over x' the same way)
     pmc_inverse_plan_t plan{};
     if (s->preconditioned && !(s->no_fuse & 1)) {
         rc = pmc_plan_inverse(s->maf, n, s->inverse_algo, PMC_FUSED_STEP, want_epi, want_epi ? s->scaler->D : 0, &plan);
         if (rc) return rc;
     }
+    pmc_handover_t hand;
+    int32_t mode, clean_unknown;
+    step_handover(s, (int64_t)rng->step, plan.epilogue != 0, &hand, &mode, &clean_unknown);
+    // (this launch sequence does not count.  No kernel writes the word then, so the store may stand in front of the launches:
+    //  a pre-step that fails in one of them leaves "not known" behind, not the count of an earlier step)
+    if (clean_unknown) *s->h_clean = -1;
     if (plan.sweep != PMC_SWEEP_NONE) {
         ProposeArgs pa{s->kind, s->cur.theta32, mu, s->inv_cov, s->chol, nu, sigma, cn_a, *rng, s->p_theta64,
                        tpcn ? s->quad : nullptr, tpcn ? s->p_quad : nullptr, adapt};
@@ -119,57 +162,36 @@ static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double
             epi.s = *s->scaler;
             epi.have_prior = pr ? 1 : 0;
             if (pr) epi.pr = pmc_prior_un_t{pr->family, pr->loc, pr->scale, pr->D, pr->reserved};
-            epi.u_out = s->p_u; epi.x_out = s->p_x; epi.x_colmajor = xT; epi.ldj_out = s->p_logdetj;
-            epi.finite_out = s->p_fin; epi.logp_out = lp; epi.finite_copy = fin2; epi.logp_copy = lp2;
-            epi.done_ticket = done ? done->ticket : nullptr;
-            epi.done_flag = done ? (long long*)done->flag : nullptr;
-            epi.done_value = done ? (long long)done->value : 0LL;
-            epi.bad_count = (done && s->h_clean) ? s->clean_count : nullptr;
-            epi.bad_flag = (done && s->h_clean && s->clean_count) ? (long long*)s->h_clean : nullptr;
+            epi.u_out = s->p_u; epi.x_out = s->p_x; epi.ldj_out = s->p_logdetj; epi.finite_out = s->p_fin; epi.logp_out = lp;
+            epi.h = hand;
 #ifdef PMC_DEBUG_HOOKS
             epi.stamps = (n == g_epilogue_stamps_n) ? g_epilogue_stamps : nullptr;
 #endif
-            epi.fill_x = (s->fill_rejected && epi.bad_flag && xT) ? s->cur.x : nullptr;
-            if (devlik) { epi.bad_count = s->clean_count; epi.bad_flag = nullptr; epi.fill_x = s->cur.x; }
         }
         if (s->ev_inv0) (void)hipEventRecord((hipEvent_t)s->ev_inv0, st);
         rc = pmc_launch_inverse(&plan, &pa, s->maf, nullptr, s->p_u32, s->p_ldjf, n, st);
         if (rc) return rc;
-        fused = true;
-        scaled = plan.epilogue;
         if (s->ev_inv1) (void)hipEventRecord((hipEvent_t)s->ev_inv1, st);
-    }
-    if (!fused) {
+    } else {
         rc = pmc_propose_adapt(s->kind, s->preconditioned ? s->cur.theta32 : nullptr,
                                s->preconditioned ? nullptr : s->cur.u, mu, s->inv_cov, s->chol, nu, sigma, cn_a, rng,
                                s->p_theta64, s->preconditioned ? s->p_theta32 : nullptr, tpcn ? s->quad : nullptr,
                                tpcn ? s->p_quad : nullptr, n, D, stream, adapt);
         if (rc) return rc;
-    }
-    // the scaler launch of its own counts the rows that do not reach the likelihood like the fused epilogue does (and fills
-    // their host rows when asked) whenever it hands x' to the host itself and evaluates the prior
-    pmc_scaler_extra sx{};
-    const bool counted = done && s->h_clean && s->clean_count && xT && (scaled || pr);
-    if (!scaled && counted) { sx.bad_count = s->clean_count; sx.bad_flag = (long long*)s->h_clean; sx.fill_x = s->fill_rejected ? s->cur.x : nullptr; }
-    if (!scaled && devlik) { sx.bad_count = s->clean_count; sx.bad_flag = nullptr; sx.fill_x = s->cur.x; }
-    if (s->h_clean && !counted) *s->h_clean = -1;     // (this launch sequence does not count)
-    if (scaled) {
-        rc = 0;
-    } else if (s->preconditioned) {
-        if (!fused) {
+        if (s->preconditioned) {
             if (s->ev_inv0) (void)hipEventRecord((hipEvent_t)s->ev_inv0, st);
             rc = pmc_maf_inverse(s->maf, s->p_theta32, s->p_u32, s->p_ldjf, n, s->inverse_algo, stream);
             if (s->ev_inv1) (void)hipEventRecord((hipEvent_t)s->ev_inv1, st);
             if (rc) return rc;
         }
-        rc = pmc_scaler_inverse_prior_ex(s->scaler, pr, s->p_u32, nullptr, s->p_u, s->p_x, xT, s->p_logdetj, s->p_fin, lp,
-                                         fin2, lp2, done, n, stream, &sx);
-    } else {
-        rc = pmc_scaler_inverse_prior_ex(s->scaler, pr, nullptr, s->p_theta64, s->p_u, s->p_x, xT, s->p_logdetj, s->p_fin,
-                                         lp, fin2, lp2, done, n, stream, &sx);
     }
-    if (rc) return rc;
-    if (direct || devlik) return finish();
+    if (!plan.epilogue) {                             // the scaler launch of its own
+        rc = pmc_scaler_inverse_prior_ex(s->scaler, pr, s->preconditioned ? s->p_u32 : nullptr,
+                                         s->preconditioned ? nullptr : s->p_theta64, s->p_u, s->p_x, s->p_logdetj, s->p_fin,
+                                         lp, &hand, n, stream);
+        if (rc) return rc;
+    }
+    if (mode != PMC_HANDOVER_COPIES) return finish();
     if (pr) {
         if (hipMemcpyAsync(s->h_logp_out, s->p_logp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
             return pmc_fail("pmc_step_pre: D2H logp");
@@ -276,9 +298,11 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
         rr.uniform = s->rng_uniform[rng->step & 1];                      // drawn ahead of time by pmc_step_pre
         rng = &rr;
     }
-    const bool direct = s->host_direct && !s->p_xT;
-    // device likelihood: logl' is in p_logl and logp' in p_logp already (the device prior, or pmc_step_lik_rows)
+    // device likelihood: logl' is in p_logl and logp' in p_logp already (the device prior, or pmc_step_lik_rows).  Unlike the
+    // pre-step's, this devlik does not ask for a prior on the device: behind a host prior x' went to the host first
+    // (pmc_step_lik_rows filled lik_x), but logl' is on the device all the same.
     const bool devlik = s->lik_x != nullptr;
+    const int mode = step_mode(s, devlik);
     if (devlik && (!s->clean_count || !s->h_calls)) return pmc_fail("pmc_step_post: a device likelihood needs clean_count and h_calls");
     // blobs of a device likelihood (blob_cur / blob_prop): the accept launch moves the accepted rows'
     const bool blobs = s->blob_row_bytes != 0 && s->blob_cur && s->blob_prop;
@@ -289,7 +313,7 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
         if (((uintptr_t)s->blob_cur | (uintptr_t)s->blob_prop) & 3) return pmc_fail("pmc_step_post: blob buffers must be 4-byte aligned");
         if (s->blob_cur == s->blob_prop) return pmc_fail("pmc_step_post: blob_cur and blob_prop must be different buffers");
     }
-    if (!direct && !devlik) {
+    if (mode == PMC_HANDOVER_COPIES) {
         if (hipMemcpyAsync(s->p_logl, s->h_logl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_post: H2D");
         if (!s->prior &&     // with a device prior logp' never left the device
@@ -301,12 +325,12 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
     prop.theta64 = s->preconditioned ? s->p_theta64 : nullptr;
     prop.u = s->p_u; prop.x = s->p_x; prop.logdetj = s->p_logdetj;
     // host_direct: the accept kernel reads logl' (and a host-evaluated logp') from the pinned host buffers
-    prop.logl = (direct && !devlik) ? s->h_logl : s->p_logl;
-    prop.logp = (direct && !devlik && !s->prior) ? s->h_logp : s->p_logp;
+    prop.logl = mode == PMC_HANDOVER_DIRECT ? s->h_logl : s->p_logl;
+    prop.logp = (mode == PMC_HANDOVER_DIRECT && !s->prior) ? s->h_logp : s->p_logp;
     prop.logdetj_flow = s->preconditioned ? s->p_ldjf : nullptr;
     prop.quad = s->quad; prop.quad_prop = s->p_quad;
     int rc;
-    if (direct || devlik) {
+    if (mode != PMC_HANDOVER_COPIES) {
         pmc_done_t dn{s->h_done ? s->h_done + 1 : nullptr, (int64_t)rng->step + 1, nullptr};
         pmc_adapt_args ad{s->adapt_state, s->adapt_state ? s->adapt_mode : 0, s->adapt_c_sigma, s->adapt_c_mu,
                           s->adapt_cap, s->adapt_n_total, {}, 0};
@@ -330,7 +354,7 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
         rc = pmc_accept(s->kind, s->preconditioned, &cur, &prop, beta, nu, rng, s->alpha, s->accept, s->sums, s->ws, n,
                         s->D, stream);
     if (rc) return rc;
-    if (copy_sums && !direct && !devlik &&
+    if (copy_sums && mode == PMC_HANDOVER_COPIES &&
         hipMemcpyAsync(s->h_sums, s->sums, (size_t)(s->D + 4) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
         return pmc_fail("pmc_step_post: D2H sums");
     if (want_mask && s->h_accept &&

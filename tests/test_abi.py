@@ -62,6 +62,7 @@ def test_struct_sizes():
     assert ctypes.sizeof(_lib.pmc_rng_t) == 48
     assert ctypes.sizeof(_lib.pmc_state_t) == 56
     assert ctypes.sizeof(_lib.pmc_proposal_t) == 72
+    assert ctypes.sizeof(_lib.pmc_handover_t) == 72
 
 
 def test_no_gpu_fails_loudly():
