@@ -135,18 +135,28 @@ __global__ __launch_bounds__(SCL_THREADS) void scaler_inverse_kernel(
     const int64_t row0 = (int64_t)blockIdx.x * SCL_ROWS;
     const int rows = (int)min((int64_t)SCL_ROWS, n - row0);
     if (tid < SCL_ROWS) rowfin[tid] = 1;
+    // A thread keeps ONE feature, as in the epilogue of the fused sweeps (scaler_body.h): feature tid % D of the rows
+    // tid / D, + rpp, + 2 rpp, ...  (D <= 319 < SCL_THREADS: what the block's LDS admits), its constants requested in one
+    // batch ahead of the barrier
+    const int rpp = SCL_THREADS / D;
+    const int r0 = tid / D, j = tid - r0 * D;
+    const bool act = r0 < rpp;
+    ScalerFeat f;
+    if (act) scaler_feat_request(f, s, (const pmc_prior_t*)nullptr, j);
     __syncthreads();
-    for (int e = tid; e < rows * D; e += SCL_THREADS) {
-        const int r = e / D, j = e - r * D;
-        const int64_t g = (row0 + r) * D + j;
-        double u = u_in ? (double)u_in[g] : u_in64[g];
-        double x, J;
-        scaler_element(s, j, u, x, J);
-        u_out[g] = u;
-        x_out[g] = x;
-        if (keep_x) Xt[j * (SCL_ROWS + 1) + r] = x;
-        Jt[r * D + j] = J;
-        if (!isfinite(x)) rowfin[r] = 0;
+    if (act) {
+        scaler_feat_finish(f, s, false);
+        for (int r = r0; r < rows; r += rpp) {
+            const int64_t g = (row0 + r) * D + j;
+            double u = u_in ? (double)u_in[g] : u_in64[g];
+            double x, J;
+            scaler_element(s, f, u, x, J);
+            u_out[g] = u;
+            x_out[g] = x;
+            if (keep_x) Xt[j * (SCL_ROWS + 1) + r] = x;
+            Jt[r * D + j] = J;
+            if (!isfinite(x)) rowfin[r] = 0;
+        }
     }
     __syncthreads();
     if (tid < rows) {

@@ -110,6 +110,8 @@ __device__ __forceinline__ void propose_body(
         if (tpcn) matfrag16<M, false>(inv_cov, D, fS, q, p);
         matfrag16<M, true>(chol, D, fL, q, p);
     }
+    // (the walker's gamma variate: requested with its other operands, used behind the first quadratic form)
+    const double g_pre = (rng.gamma && live && tpcn) ? rng.gamma[k_w] : 1.0;
     double dif[M], zz[M], muv[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {
@@ -159,7 +161,7 @@ __device__ __forceinline__ void propose_body(
         for (int m = 0; m < M; ++m) part += dif[m] * tmp[m];
         q_cur = quad_sum_d(part);
         double g;
-        if (rng.gamma) g = live ? rng.gamma[k_w] : 1.0;
+        if (rng.gamma) g = g_pre;
         else { Philox ph(rng.seed, rng.step, gidx, 0); g = ph.std_gamma(0.5 * ((double)D + nu)); }
         const double s = 1.0 / ((2.0 / (nu + q_cur)) * g);       // 1/np.random.gamma(shape, scale), mcmc.py:80
         scale_z = sigma * sqrt(s);

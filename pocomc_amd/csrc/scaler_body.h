@@ -50,58 +50,104 @@ __device__ __forceinline__ double np_pairwise_sum_l(const double* a, int n) {
 
 __device__ __forceinline__ double np_pairwise_sum(const double* a, int n) { return np_pairwise_sum_l<2>(a, n); }
 
+// The two families the epilogues of the fused sweeps evaluate: pmc_prior_t up to `reserved` (a prior with a factor of
+// another family takes the scaler launch of its own, prior_body.h)
+struct pmc_prior_un_t {
+    const int32_t* family;
+    const double* loc;
+    const double* scale;
+    int32_t D;
+    int32_t reserved;
+};
+
+// What an element needs of its feature j: the scaler's per-feature constants and the feature's factor of the prior.  The
+// users fetch it once per feature -- every field requested before the first is waited for -- and keep it in registers
+// over the feature's elements: loaded where they are used, under the branches on the kind and the family, the fields
+// came as four to five L2 round trips in a row for every element.
+struct ScalerFeat {
+    double mu, sigma;                              // affine part (s.scale)
+    double low, high, log_width;
+    double loc, pscale, log_pscale;                // the prior's factor: loc, scale and log(scale) (uniform: the value inside
+                                                   // the support is its negative; normal: the term subtracted)
+    int kind, bc, family;
+};
+
+// The loads alone.  A field the descriptors do not have (mu / sigma without the affine part, bc == NULL, no prior) is read
+// from an array they do have and never used: a request under a branch would be waited for where the branch joins.
+// pr: pmc_prior_t / pmc_prior_un_t, or NULL
+template <class P>
+__device__ __forceinline__ void scaler_feat_request(ScalerFeat& f, const pmc_scaler_t& s, const P* pr, int j) {
+    const double* mu = s.scale ? s.mu : s.low;
+    const double* sigma = s.scale ? s.sigma : s.low;
+    const int32_t* bc = s.bc ? s.bc : s.kind;
+    const double* loc = pr ? pr->loc : s.low;
+    const double* pscale = pr ? pr->scale : s.low;
+    const int32_t* family = pr ? pr->family : s.kind;
+    f.mu = mu[j]; f.sigma = sigma[j];
+    f.low = s.low[j]; f.high = s.high[j]; f.log_width = s.log_width[j];
+    f.loc = loc[j]; f.pscale = pscale[j];
+    f.kind = s.kind[j]; f.bc = bc[j]; f.family = family[j];
+    f.log_pscale = 0.0;
+}
+// what is computed from the fields (waits for them): log(scale) of the prior's factor, once per feature instead of once
+// per element -- the same device log of the same value
+__device__ __forceinline__ void scaler_feat_finish(ScalerFeat& f, const pmc_scaler_t& s, bool have_prior) {
+    if (!s.bc) f.bc = 0;
+    if (have_prior) f.log_pscale = log(f.pscale);
+}
+
 // bounded <- unbounded for one element; t is the (affine-transformed) input.  scaler.py:329-425
-__device__ __forceinline__ void bound_inverse(const pmc_scaler_t& s, int j, double t, double& x, double& J) {
-    {
-        const int kind = s.kind[j];
-        if (kind == 0) { x = t; J = 0.0; }
-        else if (kind == 1) { x = exp(t) + s.low[j]; J = t; }
-        else if (kind == 2) { x = s.high[j] - exp(t); J = t; }
-        else {
-            const double w = s.high[j] - s.low[j];
-            if (s.logit) {
-                // p = exp(-logaddexp(0, -t))
-                const double mt = -t;
-                double lae;
-                if (mt == 0.0) lae = 0.6931471805599453;
-                else if (0.0 - mt > 0.0) lae = 0.0 + log1p(exp(-(0.0 - mt)));
-                else lae = mt + log1p(exp(0.0 - mt));
-                const double p = exp(-lae);
-                x = p * w + s.low[j];
-                J = (s.log_width[j] + log(p)) + log(1.0 - p);
-            } else {
-                const double p = (erf(t / SQRT2) + 1.0) / 2.0;
-                x = p * w + s.low[j];
-                J = (s.log_width[j] + (-(t * t) / 2.0)) - LOG_SQRT_2PI;
-            }
+__device__ __forceinline__ void bound_inverse(const ScalerFeat& f, int logit, double t, double& x, double& J) {
+    if (f.kind == 0) { x = t; J = 0.0; }
+    else if (f.kind == 1) { x = exp(t) + f.low; J = t; }
+    else if (f.kind == 2) { x = f.high - exp(t); J = t; }
+    else {
+        const double w = f.high - f.low;
+        if (logit) {
+            // p = exp(-logaddexp(0, -t))
+            const double mt = -t;
+            double lae;
+            if (mt == 0.0) lae = 0.6931471805599453;
+            else if (0.0 - mt > 0.0) lae = 0.0 + log1p(exp(-(0.0 - mt)));
+            else lae = mt + log1p(exp(0.0 - mt));
+            const double p = exp(-lae);
+            x = p * w + f.low;
+            J = (f.log_width + log(p)) + log(1.0 - p);
+        } else {
+            const double p = (erf(t / SQRT2) + 1.0) / 2.0;
+            x = p * w + f.low;
+            J = (f.log_width + (-(t * t) / 2.0)) - LOG_SQRT_2PI;
         }
     }
 }
 
 // unbounded <- bounded (scaler.py:228-247, :315-400), then the affine part (:273-289)
-__device__ __forceinline__ double bound_forward(const pmc_scaler_t& s, int j, double x) {
+__device__ __forceinline__ double bound_forward(const ScalerFeat& f, int logit, int scale, double x) {
     double u;
-    {
-        const int kind = s.kind[j];
-        if (kind == 0) u = x;
-        else if (kind == 1) u = log(x - s.low[j]);
-        else if (kind == 2) u = log(s.high[j] - x);
-        else {
-            const double p = (x - s.low[j]) / (s.high[j] - s.low[j]);
-            if (s.logit) u = log(p / (1.0 - p));
-            else u = SQRT2 * erfinv(2.0 * p - 1.0);
-        }
-        if (s.scale) u = (u - s.mu[j]) / s.sigma[j];
+    if (f.kind == 0) u = x;
+    else if (f.kind == 1) u = log(x - f.low);
+    else if (f.kind == 2) u = log(f.high - x);
+    else {
+        const double p = (x - f.low) / (f.high - f.low);
+        if (logit) u = log(p / (1.0 - p));
+        else u = SQRT2 * erfinv(2.0 * p - 1.0);
     }
+    if (scale) u = (u - f.mu) / f.sigma;
     return u;
+}
+// (one element, the feature's constants from the descriptor: scaler_forward_kernel)
+__device__ __forceinline__ double bound_forward(const pmc_scaler_t& s, int j, double x) {
+    ScalerFeat f;
+    scaler_feat_request(f, s, (const pmc_prior_un_t*)nullptr, j);
+    return bound_forward(f, s.logit, s.scale, x);
 }
 
 // periodic wrap / reflective fold (scaler.py:109-157).  The reference loops "while
 // outside"; a non-finite x would never leave that loop, the device bounds it.
-__device__ __forceinline__ double apply_bc(const pmc_scaler_t& s, int j, double x) {
-    const int bc = s.bc[j];
+__device__ __forceinline__ double apply_bc(const ScalerFeat& f, double x) {
+    const int bc = f.bc;
     if (bc == 0) return x;
-    const double lo = s.low[j], hi = s.high[j];
+    const double lo = f.low, hi = f.high;
     {
         if (bc & 1) {
             for (int it = 0; it < 4096 && x > hi; ++it) x = lo + x - hi;
@@ -115,42 +161,38 @@ __device__ __forceinline__ double apply_bc(const pmc_scaler_t& s, int j, double 
     return x;
 }
 
-// The two families the epilogues of the fused sweeps evaluate: pmc_prior_t up to `reserved` (a prior with a factor of
-// another family takes the scaler launch of its own, prior_body.h)
-struct pmc_prior_un_t {
-    const int32_t* family;
-    const double* loc;
-    const double* scale;
-    int32_t D;
-    int32_t reserved;
-};
-
 // one uniform / normal factor of Prior.logpdf (pocomc/prior.py:70-100), shared by prior_logpdf_kernel, the scaler kernel
-// and the epilogues of the fused sweeps (P: pmc_prior_t or pmc_prior_un_t)
-template <class P>
-__device__ __forceinline__ double prior_term(const P& pr, int j, double xv) {
-    const double loc = pr.loc[j], sc = pr.scale[j];
-    if (pr.family[j] == PMC_PRIOR_UNIFORM) {
+// and the epilogues of the fused sweeps
+__device__ __forceinline__ double prior_term(const ScalerFeat& f, double xv) {
+    if (f.family == PMC_PRIOR_UNIFORM) {
         // scipy uniform(loc, scale).logpdf: -log(scale) on [loc, loc+scale], -inf outside
-        return (xv >= loc && xv <= loc + sc) ? -log(sc) : -INFINITY;
+        return (xv >= f.loc && xv <= f.loc + f.pscale) ? -f.log_pscale : -INFINITY;
     }
     // scipy norm(loc, scale).logpdf: _norm_logpdf((x-loc)/scale) - log(scale)
-    const double z = (xv - loc) / sc;
-    return (-(z * z) / 2.0 - LOG_SQRT_2PI) - log(sc);
+    const double z = (xv - f.loc) / f.pscale;
+    return (-(z * z) / 2.0 - LOG_SQRT_2PI) - f.log_pscale;
+}
+// (the factor's constants from the descriptor; P: pmc_prior_t or pmc_prior_un_t)
+template <class P>
+__device__ __forceinline__ double prior_term(const P& pr, int j, double xv) {
+    ScalerFeat f;
+    f.loc = pr.loc[j]; f.pscale = pr.scale[j]; f.family = pr.family[j];
+    f.log_pscale = log(f.pscale);
+    return prior_term(f, xv);
 }
 
 
 // one element of the scaler inverse: u in; u (re-derived from x when boundary conditions apply), x and the Jacobian term J
 // out.  Shared by scaler_inverse_kernel and the epilogue of the fused sweeps.
-__device__ __forceinline__ void scaler_element(const pmc_scaler_t& s, int j, double& u, double& x, double& J) {
-    double t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
-    bound_inverse(s, j, t, x, J);
+__device__ __forceinline__ void scaler_element(const pmc_scaler_t& s, const ScalerFeat& f, double& u, double& x, double& J) {
+    double t = s.scale ? f.mu + f.sigma * u : u;
+    bound_inverse(f, s.logit, t, x, J);
     if (s.bc) {
         // mcmc.py:94-97: wrap x, re-derive u from it, invert again
-        x = apply_bc(s, j, x);
-        u = bound_forward(s, j, x);
-        t = s.scale ? s.mu[j] + s.sigma[j] * u : u;
-        bound_inverse(s, j, t, x, J);
+        x = apply_bc(f, x);
+        u = bound_forward(f, s.logit, s.scale, x);
+        t = s.scale ? f.mu + f.sigma * u : u;
+        bound_inverse(f, s.logit, t, x, J);
     }
 }
 
@@ -293,24 +335,33 @@ __device__ __forceinline__ void scaler_epilogue(const ScalerEpi& e, const float*
     const int rows = (int)min((int64_t)16, n - row0);
     if (tid < 16) rowfin[tid] = 1;
     if (e.stamps && tid == 0) e.stamps[blockIdx.x * 8 + 0] = wall_clock64();
+    // A thread keeps ONE feature: thread tid takes feature tid % D of the rows tid / D, + rpp, + 2 rpp, ... (D <= nthr: the
+    // fused instances end at D = 64; the nthr % D threads left over rest).  Its feature's constants and rank are
+    // requested here, in one batch ahead of the barrier, and stay in registers over its rows.
+    const int rpp = nthr / D;
+    const int r0 = tid / D, j = tid - r0 * D;
+    const bool act = r0 < rpp;
+    ScalerFeat f;
+    int rk = 0;
+    if (act) {
+        scaler_feat_request(f, e.s, e.have_prior ? &e.pr : nullptr, j);
+        rk = rof[j];
+    }
     __syncthreads();
-    {   // element el = r * D + j; (r, j) step by nthr = dr * D + dj without a division per element
-        const int dr = nthr / D, dj = nthr - dr * D;
-        int r = tid / D, j = tid - r * D;
-        for (int el = tid; el < rows * D; el += nthr) {
+    if (act) {
+        scaler_feat_finish(f, e.s, e.have_prior != 0);
+        for (int r = r0; r < rows; r += rpp) {
             // the bijector, its Jacobian term, the boundary conditions, the prior factor: u / x to the device arrays, the
             // row tables Jt / Pt / Xt / rowfin in LDS
-            double u = (double)X[lidx_of(rof[j], r)], x, J;
-            scaler_element(e.s, j, u, x, J);
+            double u = (double)X[lidx_of(rk, r)], x, J;
+            scaler_element(e.s, f, u, x, J);
             const int64_t g = (row0 + r) * D + j;
             e.u_out[g] = u;
             e.x_out[g] = x;
             Xt[j * 17 + r] = x;
             Jt[r * D + j] = J;
-            if (e.have_prior) Pt[r * D + j] = prior_term(e.pr, j, x);
+            if (e.have_prior) Pt[r * D + j] = prior_term(f, x);
             if (!isfinite(x)) rowfin[r] = 0;
-            r += dr; j += dj;
-            if (j >= D) { j -= D; ++r; }
         }
     }
     __syncthreads();
