@@ -595,7 +595,23 @@ typedef struct pmc_step {
     const double* adapt_other[7];  /* device [D+4] sums of the other row ranges of the walker set (their accepts precede this
                                * one on the stream): added to this step's sums before the update and before the host copy */
     int32_t adapt_n_other;
-    int32_t adapt_pad2;
+    /* Blobs of a likelihood on the HOST (a vectorised host likelihood that returns (logl, blobs); the word was reserved
+     * padding, zero in every caller so far: no offset and no size changes).  1: blob_cur (below) is the walkers' device
+     * buffer as for a device likelihood, but blob_prop is a PINNED HOST buffer [n][blob_row_bytes] into which the host writes
+     * the blobs of x' next to logl' into h_logl (rows that do not reach the likelihood may hold anything: their logl' is
+     * -inf, alpha = 0).  No lik_x is needed or allowed.  pmc_step_post (and with it pmc_pipeline_next) enqueues, BEHIND the
+     * accept launch on the same stream, one more launch (pmc_blob_rows_move) that reads the accept's int32 mask and copies
+     * the accepted walkers' rows from blob_prop to blob_cur.  The accept launch is the one without blobs, and the move takes
+     * no part in the completion words: the closing accept's word reaches the host before the move's loads cross PCIe (in a
+     * sharded pipeline the move follows the exchange launch, which stores that word).
+     * Ordering of the pinned buffer (one stream per lane): the host rewrites a lane's blob_prop for step k+1 only after it
+     * has seen that lane's pre-step k+1 completion word (h_done[0], or ev_pre_done); that pre-step was enqueued behind the
+     * lane's step-k pmc_step_post, hence behind its move launch, which has therefore read the buffer by then.  In the
+     * pipeline the last lane's move launch is followed by the pre-steps of step k+1: they touch proposal buffers only --
+     * neither blob_cur nor blob_prop -- so no wait is needed there either.  The walkers' blob_cur is complete once the stream
+     * has been synchronised (pmc_stream_synchronize), not at the completion word h_done[1].
+     * The buffers are checked as the device blobs' are (blob_row_bytes, alignment, distinct). */
+    int32_t blob_host;
     /* "every row is clean": with h_clean non-NULL pmc_step_pre leaves there, before the completion word h_done[0], the
      * number of rows whose x' is not finite or whose device-evaluated logp' is not finite (mcmc.py:100-109's two masks) --
      * 0 lets the host skip both mask scans and hand the whole block to the likelihood.  -1: the launch sequence that ran
@@ -654,11 +670,17 @@ typedef struct pmc_step {
      * 4-byte aligned and distinct.  Zero / NULL: no blobs, and the accept launch is the one without them.  pmc_accept and
      * pmc_accept_armed take no blobs. */
     void* blob_cur;           /* device [n][blob_row_bytes] or NULL */
-    const void* blob_prop;    /* device [n][blob_row_bytes] or NULL */
+    const void* blob_prop;    /* device [n][blob_row_bytes] or NULL (blob_host: pinned host memory, see there) */
     int64_t blob_row_bytes;
 } pmc_step_t;
 
 #define PMC_BLOB_ROW_BYTES_MAX (1 << 20)
+
+/* dst[r] <- src[r] (rows of row_bytes bytes) for every r < n with accept[r] != 0; the other rows are neither read nor
+ * written.  accept: device int32 [n] (pmc_step_t.accept); src: device-accessible memory, typically pinned host memory
+ * (the loads cross PCIe: the kernel keeps several in flight per thread); dst: device.  row_bytes a multiple of 4 between 4
+ * and PMC_BLOB_ROW_BYTES_MAX, src and dst 4-byte aligned and distinct.  One launch on `stream`, no wait, no completion word. */
+int pmc_blob_rows_move(const int32_t* accept, const void* src, void* dst, int64_t n, int64_t row_bytes, void* stream);
 
 #define PMC_ADAPT_TPCN 1      /* sigma <- |min(sigma + c (mean alpha - 0.234), cap)|      (mcmc.py:152, :476) */
 #define PMC_ADAPT_PRWM 2      /* sigma <- sigma + c (mean alpha - 0.234)                   (mcmc.py:314) */

@@ -107,7 +107,7 @@ class pmc_step_t(C.Structure):
                 ("adapt_state", C.c_void_p), ("adapt_mode", C.c_int32), ("adapt_pad", C.c_int32),
                 ("adapt_c_sigma", C.c_double), ("adapt_c_mu", C.c_double), ("adapt_cap", C.c_double),
                 ("adapt_n_total", C.c_double), ("adapt_other", C.c_void_p * 7), ("adapt_n_other", C.c_int32),
-                ("adapt_pad2", C.c_int32), ("h_clean", c_p), ("clean_count", c_p),
+                ("blob_host", C.c_int32), ("h_clean", c_p), ("clean_count", c_p),
                 ("fill_rejected", C.c_int32), ("prior_rows", C.c_int32), ("lik_x", c_p), ("h_calls", c_p),
                 ("blob_cur", c_p), ("blob_prop", c_p), ("blob_row_bytes", C.c_int64)]
 
@@ -172,6 +172,7 @@ SIGNATURES = {
     "pmc_step_post": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, C.c_int, C.c_int, c_p]),
     "pmc_step_lik_rows": (C.c_int, [P(pmc_step_t), c_p]),
     "pmc_step_prior_rows": (C.c_int, [P(pmc_step_t), c_p, C.c_int, c_p]),
+    "pmc_blob_rows_move": (C.c_int, [c_p, c_p, c_p, i64, i64, c_p]),
     "pmc_stream_synchronize": (C.c_int, [c_p]),
     "pmc_pipeline_create": (C.c_void_p, [C.POINTER(C.c_void_p), i32, C.c_uint64, C.POINTER(C.c_uint64), c_p, f64, c_p]),
     "pmc_pipeline_set_comm": (C.c_int, [c_p, c_p]),

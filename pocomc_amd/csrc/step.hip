@@ -13,9 +13,11 @@
 // buffers must be pinned for the copies to be asynchronous.
 
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include <time.h>
 #include "pmc_internal.h"
 #include "propose_body.h"
+#include "blob_move.h"
 
 #ifdef PMC_DEBUG_HOOKS                               // measurement builds only (make DEBUG_HOOKS=1): not in the product library
 static long long* g_epilogue_stamps = nullptr;       // pmc_debug_set_epilogue_stamps
@@ -287,8 +289,37 @@ extern "C" int pmc_propose_inverse(int kind, const float* cur32, const double* m
     return pmc_launch_inverse(&plan, &pa, maf, nullptr, u_out, ladj, n, (hipStream_t)stream);
 }
 
-extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask,
-                             int copy_sums, void* stream) {
+// what pmc_step_post asks of its device blobs, asked of any pair of blob buffers
+static int blob_buffers_check(const char* who, const void* a, const void* b, int64_t row_bytes) {
+    char msg[160];
+    if (row_bytes < 4 || row_bytes % 4 || row_bytes > PMC_BLOB_ROW_BYTES_MAX) {
+        snprintf(msg, sizeof msg, "%s: blob_row_bytes must be a multiple of 4 between 4 and PMC_BLOB_ROW_BYTES_MAX", who);
+        return pmc_fail(msg);
+    }
+    if (((uintptr_t)a | (uintptr_t)b) & 3) { snprintf(msg, sizeof msg, "%s: blob buffers must be 4-byte aligned", who); return pmc_fail(msg); }
+    if (a == b) { snprintf(msg, sizeof msg, "%s: the two blob buffers must be different buffers", who); return pmc_fail(msg); }
+    return 0;
+}
+
+extern "C" int pmc_blob_rows_move(const int32_t* accept, const void* src, void* dst, int64_t n, int64_t row_bytes,
+                                  void* stream) {
+    if (!accept || !src || !dst || n < 0) return pmc_fail("pmc_blob_rows_move: needs accept, src, dst and n >= 0");
+    if (int e = blob_buffers_check("pmc_blob_rows_move", src, dst, row_bytes)) return e;
+    if (n == 0) return 0;
+    blob_rows_move_launch<BLOB_MOVE_INFLIGHT>(accept, src, dst, n, (int)(row_bytes / 4), (hipStream_t)stream);
+    return pmc_check_launch("blob_rows_move_kernel");
+}
+
+// blobs of a host likelihood (pmc_step_t.blob_host: blob_prop is the host's pinned buffer): the move launch behind the accept
+static bool step_host_blobs(const pmc_step_t* s) { return s->blob_host != 0; }
+
+static int step_move_host_blobs(const pmc_step_t* s, void* stream) {
+    return pmc_blob_rows_move(s->accept, s->blob_prop, s->blob_cur, s->n, s->blob_row_bytes, stream);
+}
+
+// move_blobs = false: the caller enqueues the host blobs' move launch itself (the sharded pipeline: behind the exchange)
+static int step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask, int copy_sums,
+                     void* stream, bool move_blobs) {
     if (!s || !rng) return pmc_fail("pmc_step_post: null argument");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = s->n;
@@ -305,13 +336,19 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
     const int mode = step_mode(s, devlik);
     if (devlik && (!s->clean_count || !s->h_calls)) return pmc_fail("pmc_step_post: a device likelihood needs clean_count and h_calls");
     // blobs of a device likelihood (blob_cur / blob_prop): the accept launch moves the accepted rows'
-    const bool blobs = s->blob_row_bytes != 0 && s->blob_cur && s->blob_prop;
+    const bool blobs = !step_host_blobs(s) && s->blob_row_bytes != 0 && s->blob_cur && s->blob_prop;
     if (blobs) {
         if (!devlik) return pmc_fail("pmc_step_post: blobs on the device need a device likelihood (lik_x)");
         if (s->blob_row_bytes < 0 || s->blob_row_bytes % 4 || s->blob_row_bytes > PMC_BLOB_ROW_BYTES_MAX)
             return pmc_fail("pmc_step_post: blob_row_bytes must be a multiple of 4 between 4 and PMC_BLOB_ROW_BYTES_MAX");
         if (((uintptr_t)s->blob_cur | (uintptr_t)s->blob_prop) & 3) return pmc_fail("pmc_step_post: blob buffers must be 4-byte aligned");
         if (s->blob_cur == s->blob_prop) return pmc_fail("pmc_step_post: blob_cur and blob_prop must be different buffers");
+    }
+    // blobs of a host likelihood (blob_host): a launch of its own behind the accept, which is the one without blobs
+    if (step_host_blobs(s)) {
+        if (devlik) return pmc_fail("pmc_step_post: blob_host is for a host likelihood (lik_x is set)");
+        if (!s->blob_cur || !s->blob_prop || !s->accept) return pmc_fail("pmc_step_post: blob_host needs blob_cur, blob_prop and the accept mask");
+        if (int e = blob_buffers_check("pmc_step_post", s->blob_prop, s->blob_cur, s->blob_row_bytes)) return e;
     }
     if (mode == PMC_HANDOVER_COPIES) {
         if (hipMemcpyAsync(s->p_logl, s->h_logl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
@@ -357,10 +394,19 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
     if (copy_sums && mode == PMC_HANDOVER_COPIES &&
         hipMemcpyAsync(s->h_sums, s->sums, (size_t)(s->D + 4) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
         return pmc_fail("pmc_step_post: D2H sums");
+    if (move_blobs && step_host_blobs(s)) {
+        rc = step_move_host_blobs(s, stream);
+        if (rc) return rc;
+    }
     if (want_mask && s->h_accept &&
         hipMemcpyAsync(s->h_accept, s->accept, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess)
         return pmc_fail("pmc_step_post: D2H accept");
     return 0;
+}
+
+extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, double nu, int want_mask,
+                             int copy_sums, void* stream) {
+    return step_post(s, rng, beta, nu, want_mask, copy_sums, stream, true);
 }
 
 #ifdef PMC_DEBUG_HOOKS
@@ -529,9 +575,12 @@ extern "C" int pmc_pipeline_next(void* pp, int32_t lane_done, double beta, doubl
             for (int k = 0; k < last; ++k) s.adapt_other[k] = p->lanes[k]->sums;
             s.adapt_n_other = last;
         }
-        const int rc = pmc_step_post(&s, &p->rng[lane_done], beta, nu, 0, (lane_done == last && !p->comm) ? 1 : 0, p->stream);
+        // (blobs of a host likelihood: the lane's move launch follows its accept -- behind the exchange, where the exchange
+        //  stores the completion word the host waits for)
+        const bool exchange = lane_done == last && p->comm;
+        const int rc = step_post(&s, &p->rng[lane_done], beta, nu, 0, (lane_done == last && !p->comm) ? 1 : 0, p->stream, !exchange);
         if (rc) return rc;
-        if (lane_done == last && p->comm) {
+        if (exchange) {
             // sharded: this rank's lanes + the other ranks' totals (rank order), the adaptation, sums + completion word
             const double* parts[8];
             for (int k = 0; k <= last; ++k) parts[k] = p->lanes[k]->sums;
@@ -540,6 +589,10 @@ extern "C" int pmc_pipeline_next(void* pp, int32_t lane_done, double beta, doubl
             const int rc2 = pmc_comm_adapt_update(p->comm, parts, last + 1, sl->D, nullptr, sl->h_sums, sl->adapt_state, adapt_mode,
                                                   c_sigma, c_mu, cap, n_total, &dn, p->timeout, p->stream);
             if (rc2) return rc2;
+            if (step_host_blobs(&s)) {
+                const int rc3 = step_move_host_blobs(&s, p->stream);
+                if (rc3) return rc3;
+            }
         }
         const double t1 = now_s();
         p->t_enq_accept += t1 - t0;

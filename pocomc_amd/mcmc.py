@@ -9,7 +9,10 @@ user's prior / likelihood black boxes on the compacted finite rows
 (``mcmc.py:100-121``) and the scalar adaptation / stopping logic
 (``mcmc.py:152-180``).  With ``option_dict["device_likelihood"]`` the likelihood is a
 GPU callable too: x' stays on the device, and the host reads the sums of each step only; blobs such a likelihood returns
-stay in HBM as well and move with the accepted walkers in the accept launch.  ``option_dict["device_logprior"]`` makes the
+stay in HBM as well and move with the accepted walkers in the accept launch.  A vectorised HOST likelihood that returns
+``(logl, blobs)`` keeps the walkers' blobs in HBM too (``state_dict["blobs"]`` a device tensor): the proposals' blobs go into a
+pinned host buffer and a launch behind each accept moves the accepted rows, in whichever mode the call takes without blobs.
+``option_dict["device_logprior"]`` makes the
 prior a GPU callable of the same kind, for priors that are no product of the scipy factors the device has a table for.
 
 
@@ -213,6 +216,55 @@ def device_blobs(out, n, device, like=None):
     if like is not None and b.dtype != like.dtype:
         raise ValueError(f"device blobs: expected dtype {like.dtype} as in the first call, got {b.dtype}")
     return b.contiguous()
+
+
+PMC_BLOB_ROW_BYTES_MAX = 1 << 20                                                  # include/pocomc_amd.h
+HOST_BLOB_DTYPES = tuple(np.dtype(t) for t in (np.float64, np.float32, np.int64, np.int32))
+
+
+def host_blobs_dtype(dtype):
+    """``blobs_dtype`` of a vectorised host likelihood as a numpy dtype: float64 (``float``), float32, int64 or int32, the
+    types the device moves.  Anything else -- bool, 2-byte types, structured and object dtypes -- raises ValueError."""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError as e:
+        raise ValueError(f"blobs_dtype: {dtype!r} is no numpy dtype") from e
+    if dt not in HOST_BLOB_DTYPES:
+        raise ValueError(f"blobs_dtype: a vectorised likelihood's blobs are float64, float32, int64 or int32, got {dt}; "
+                         "use vectorize=False for blobs of any other type")
+    return dt
+
+
+def host_blobs(out, n, dtype, blob_shape=None):
+    """What a vectorised host likelihood that returns blobs gave for ``n`` rows: ``(logl, blobs)``, ``logl`` of shape
+    ``(n,)``, ``blobs`` an array-like of shape ``(n, *blob_shape)`` with at least one element and at most
+    ``PMC_BLOB_ROW_BYTES_MAX`` bytes per row.  Returns ``(logl, blobs)`` as numpy arrays, the blobs cast to ``dtype`` (one of
+    :data:`HOST_BLOB_DTYPES`) and C-contiguous.  ``blob_shape``: the trailing shape the blobs must have (fixed by the first
+    call).  Anything else raises ValueError naming what was received.  Pure numpy: no device is touched."""
+    if not isinstance(out, tuple) or len(out) != 2:
+        got = f"a tuple of {len(out)}" if isinstance(out, tuple) else type(out).__name__
+        raise ValueError(f"host blobs: expected the likelihood to return a tuple (logl, blobs), got {got}")
+    logl = np.asarray(out[0], dtype=np.float64)
+    if logl.shape != (n,):
+        raise ValueError(f"host blobs: expected logl of shape ({n},), got {logl.shape}")
+    dt = host_blobs_dtype(dtype)
+    if out[1] is None:
+        raise ValueError(f"host blobs: expected blobs of shape ({n}, ...), got None")
+    try:
+        b = np.asarray(out[1], dtype=dt)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"host blobs: the blobs do not form a ({n}, ...) array of {dt}: {e}") from e
+    if b.ndim < 1 or b.shape[0] != n:
+        raise ValueError(f"host blobs: expected blobs of shape ({n}, ...), got {b.shape}")
+    b = np.ascontiguousarray(b)
+    row_bytes = int(np.prod(b.shape[1:], dtype=np.int64)) * b.itemsize
+    if row_bytes == 0:
+        raise ValueError(f"host blobs: expected at least one element per row, got shape {b.shape}")
+    if row_bytes > PMC_BLOB_ROW_BYTES_MAX:
+        raise ValueError(f"host blobs: a row of {row_bytes} bytes is more than PMC_BLOB_ROW_BYTES_MAX = {PMC_BLOB_ROW_BYTES_MAX}")
+    if blob_shape is not None and tuple(b.shape[1:]) != tuple(blob_shape):
+        raise ValueError(f"host blobs: expected blob_shape {tuple(blob_shape)} as in the first call, got {tuple(b.shape[1:])}")
+    return logl, b
 
 
 def _timed(fn, timers, key):
@@ -532,6 +584,10 @@ class StepEngine:
         # blobs of the device likelihood (set_device_blobs): the walkers' and the proposals', (n, *blob_shape) each
         self.blobs = None
         self.p_blobs = None
+        # blobs of a vectorised HOST likelihood (set_host_blobs): the walkers' in ``blobs`` all the same, the proposals' in a
+        # pinned host buffer that evaluate() fills and the move launch behind the accept reads (pmc_step_t.blob_host)
+        self.h_blobs = None
+        self._np_blobs = None
         # prior on the device as the caller's GPU callable (set_device_logprior): its values go through pmc_step_prior_rows
         self.device_logprior = False
         self._sums_part = None   # (exchange_enqueue: this rank's sums as the exchange's single part)
@@ -641,6 +697,34 @@ class StepEngine:
         self._step.blob_cur = self.blobs.data_ptr()
         self._step.blob_prop = self.p_blobs.data_ptr()
         self._step.blob_row_bytes = _blob_row_bytes(b)
+
+    def set_host_blobs(self, blobs):
+        """The walkers carry blobs of a vectorised host likelihood that returns ``(logl, blobs)`` numpy: ``blobs`` (a device
+        tensor ``(n, *blob_shape)``, checked by :func:`device_blobs`) is copied into the engine's own buffer;
+        :meth:`evaluate` writes the proposals' blobs into a pinned host buffer of the same shape, and a launch behind the
+        accept moves the accepted walkers' rows from there (``pmc_step_t.blob_host``, ``pmc_blob_rows_move``).  The engine
+        keeps the mode it has without blobs."""
+        assert not self.device_likelihood
+        b = device_blobs((None, blobs), self.n, self.device)
+        row_bytes = _blob_row_bytes(b)
+        if row_bytes > PMC_BLOB_ROW_BYTES_MAX:
+            raise ValueError(f"host blobs: a row of {row_bytes} bytes is more than PMC_BLOB_ROW_BYTES_MAX = {PMC_BLOB_ROW_BYTES_MAX}")
+        self.blobs = torch.empty_like(b)
+        self.blobs.copy_(b)
+        self.h_blobs = _pinned_take(tuple(int(v) for v in b.shape), b.dtype)
+        self._pins.append(self.h_blobs)
+        self._np_blobs = self.h_blobs.numpy()
+        self._step.blob_cur = self.blobs.data_ptr()
+        self._step.blob_prop = self.h_blobs.data_ptr()
+        self._step.blob_host = 1
+        self._step.blob_row_bytes = row_bytes
+
+    def _keep_blobs(self, out, rows, n_rows):
+        """The blobs in ``out``, what the likelihood returned for ``n_rows`` rows, into the rows ``rows`` (a slice or a mask)
+        of the pinned buffer; returns logl'."""
+        logl, b = host_blobs(out, n_rows, self._np_blobs.dtype, self._np_blobs.shape[1:])
+        self._np_blobs[rows] = b
+        return logl
 
     def set_mu(self, mu):
         # pinned staging + async copy; the previous upload was consumed by a kernel that has
@@ -801,9 +885,14 @@ class StepEngine:
         if ((waited or not self._instrumented()) and self._direct_now and self.prior_desc is not None
                 and self.host_threads <= 1 and not have_blobs):
             bad = int(self._np_clean[0])
+        # blobs of a vectorised host likelihood (set_host_blobs): every path below leaves blobs' of the rows it hands to the
+        # likelihood in the pinned buffer; the rows it leaves out, or whose value it drops, keep whatever the buffer held --
+        # their logl' is -inf, alpha = 0, they never move
+        keep = self._np_blobs is not None
         if bad == 0:
             # both masks of mcmc.py:100-109 are all-true, x'[mask] is x' itself
-            logl_prime[:] = log_like(x_prime)[0]
+            out = log_like(x_prime)
+            logl_prime[:] = self._keep_blobs(out, slice(None), n) if keep else out[0]
             return n, None
         all_fin = fin_i.all()
         if all_fin and self.host_threads > 1 and not have_blobs:
@@ -828,6 +917,8 @@ class StepEngine:
         if have_blobs:
             blobs_prime = np.empty(n, dtype=np.dtype((blobs[0].dtype, blobs[0].shape)))
             logl_prime[rows], blobs_prime[rows] = log_like(xs)
+        elif keep:
+            logl_prime[rows] = self._keep_blobs(log_like(xs), rows, len(xs))
         else:
             logl_prime[rows], _ = log_like(xs)
         if not whole:
@@ -852,11 +943,14 @@ class StepEngine:
                 logp_prime[lo:hi] = log_prior(xs)
             lp = logp_prime[lo:hi]
             ok = np.isfinite(lp)
+            keep = self._np_blobs is not None           # (host blobs: the chunks' rows of the pinned buffer are disjoint)
             if ok.all():
-                logl_prime[lo:hi] = log_like(xs)[0]
+                out = log_like(xs)
+                logl_prime[lo:hi] = self._keep_blobs(out, slice(lo, hi), hi - lo) if keep else out[0]
                 return hi - lo
             ll = np.full(hi - lo, -np.inf)
-            ll[ok] = log_like(xs[ok])[0]
+            out = log_like(xs[ok])
+            ll[ok] = self._keep_blobs(out, np.flatnonzero(ok) + lo, int(ok.sum())) if keep else out[0]
             logl_prime[lo:hi] = ll
             return int(ok.sum())
         # the calling thread takes the last chunk itself, the pool's threads the others
@@ -1098,6 +1192,15 @@ class LanedEngine:
             with torch.cuda.stream(self_stream):
                 e.load_state(u[lo:hi], x[lo:hi], logdetj[lo:hi], logl[lo:hi], logp[lo:hi])
         torch.cuda.synchronize(self.device)
+
+    def set_host_blobs(self, blobs):
+        """Blobs of a vectorised host likelihood (``StepEngine.set_host_blobs``): every lane owns its rows' device buffer
+        and its own pinned buffer for the proposals' blobs."""
+        if blobs.shape[0] != self.n:
+            raise ValueError(f"device blobs: expected shape ({self.n}, ...), got {tuple(blobs.shape)}")
+        for e, (lo, hi) in zip(self.lanes, self.bounds):
+            e.set_host_blobs(blobs[lo:hi])
+        torch.cuda.synchronize(self.device)           # (copied on the current stream; the lanes may step on their own)
 
     def can_pipeline(self):
         return all(e.stream is None and e.can_pipeline() for e in self.lanes)
@@ -1514,14 +1617,23 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     if device_logprior and not device_like:
         raise ValueError("device_logprior: a prior on the device needs device_likelihood=True (with a host likelihood x' "
                          "goes to the host anyway)")
+    # blobs as a device tensor with a HOST likelihood: the likelihood returns (logl, blobs) numpy on whole blocks, the walkers'
+    # blobs stay in HBM and the call keeps the mode it takes without blobs.  Blobs as a numpy array: the whole-set mode
+    # (arbitrary dtypes, replay, trace), as ever
+    tensor_blobs = have_blobs and not device_like and isinstance(blobs, torch.Tensor)
+    if tensor_blobs and (replay is not None or trace is not None):
+        raise ValueError("blobs as a device tensor do not combine with replayed variates or traces: pass them as a numpy array")
     eng, pipelined = _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior,
-                                  whole_set=have_blobs or trace is not None or replay is not None, device_like=device_like,
-                                  device_logprior=device_logprior)
+                                  whole_set=(have_blobs and not tensor_blobs) or trace is not None or replay is not None,
+                                  device_like=device_like, device_logprior=device_logprior)
     laned = isinstance(eng, LanedEngine)
     lanes = eng.lanes if laned else [eng]
     eng.load_state(u, x, logdetj, logl, logp)
     if device_like and have_blobs:
         eng.set_device_blobs(blobs)                # (the engine's own copy: the accept launches move its rows)
+    if tensor_blobs:
+        eng.set_host_blobs(blobs)                  # (the engine's own copy: a launch behind each accept moves its rows)
+        blobs, have_blobs = None, False            # (none of the whole-set bookkeeping below)
     nu = 0.0
     if tpcn:
         nu = float(geometry.t_nu)
@@ -1588,6 +1700,10 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
         eng.finish_pipeline()
     elif device_like:
         _lib.check(eng.lib.pmc_stream_synchronize(eng._stream), "pmc_stream_synchronize")
+    elif tensor_blobs:
+        # the move launch of the last step follows the accept whose completion word ended the loop, on each lane's stream
+        for e in lanes:
+            _lib.check(eng.lib.pmc_stream_synchronize(e._stream), "pmc_stream_synchronize")
 
     keep = bool(option_dict.get("device_state", False))
     if keep:

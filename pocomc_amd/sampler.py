@@ -168,6 +168,13 @@ class Sampler:
                           that disagrees raises.  The blobs stay in HBM through the run (an accepted walker's row moves in
                           the accept launch, the pool keeps every iteration's block on the device); they come out as numpy
                           arrays like everything else: ``posterior(return_blobs=True)``, ``results["blobs"]``, checkpoints.
+        ``vectorize=True`` with ``blobs_dtype``  (a host likelihood) the likelihood is called on ``(n, D)`` float64 numpy
+                          blocks and returns ``(logl, blobs)``: ``logl`` of shape ``(n,)``, ``blobs`` an array-like
+                          ``(n, *blob_shape)`` with at least one element per row, cast to ``blobs_dtype`` -- float64
+                          (``float``), float32, int64 or int32; any other dtype raises (use ``vectorize=False`` for those).
+                          ``blob_shape`` is fixed by the first call.  The MCMC steps keep the mode they have without blobs
+                          (pipelined, laned, ``host_threads``, sharded); the blobs live in HBM and come out as a device
+                          likelihood's do;
         ``device_prior``  (needs ``device_likelihood=True``) the prior is evaluated on the GPU by a function of the user's:
                           ``prior.logpdf_device`` (``prior.DevicePrior``, or any prior object with that method) under the
                           device likelihood's contract -- an ``(n, D)`` float64 tensor in, an ``(n,)`` float64 or float32
@@ -237,9 +244,14 @@ class Sampler:
         if self.device_prior and not callable(getattr(prior, "logpdf_device", None)):
             raise ValueError(f"device_prior=True needs a prior with a logpdf_device method (pocomc_amd.DevicePrior), "
                              f"got {type(prior).__name__}")
-        self._blob_spec = None         # (blob_shape, dtype name) of the device blobs, fixed by the first call
-        if vectorize and self.have_blobs and not self.device_blobs:
-            raise ValueError("Cannot vectorize likelihood with blobs.")
+        # (blob_shape, dtype name) of the device blobs, or blob_shape of a vectorised host likelihood's: fixed by the first call
+        self._blob_spec = None
+        # blobs of a vectorised HOST likelihood: it returns (logl, blobs) numpy on whole blocks; the walkers' and the pool's
+        # blobs live in HBM like a device likelihood's, and the MCMC steps keep their pipelined / laned mode
+        self.host_blobs = bool(vectorize and self.have_blobs and not self.device_likelihood)
+        if self.host_blobs:
+            self.blobs_dtype = _mcmc.host_blobs_dtype(blobs_dtype)
+        self.blobs_on_device = self.device_blobs or self.host_blobs
         self.pool, self.distribute = pool, map
         if isinstance(pool, int) and pool > 1:
             from multiprocess import Pool
@@ -364,6 +376,8 @@ class Sampler:
             if self.device_blobs:
                 to = lambda i: torch.from_numpy(i).to(blobs.device)
                 blobs = blobs.index_copy(0, to(rows[bad]), blobs[to(src)])      # (a new tensor: the likelihood's own stays)
+        if self.host_blobs:
+            blobs = torch.from_numpy(blobs).to(self.flow.device)      # (replaced on the host above; resident from here on)
         self.walkers = dict(u=u, x=x, logl=logl, logp=logp, logdetj=logdetj, blobs=blobs, iter=self.t, calls=self.calls,
                             steps=1, efficiency=1.0, ess=self.n_effective, accept=1.0, beta=0.0, logz=0.0)
         self.particles.update(self.walkers)
@@ -469,7 +483,7 @@ class Sampler:
             pick = systematic_resample(self.n_active, weights=w, device_indices=True)
         rows = idx[pick]
         self.walkers.update(self.particles.take(rows))
-        if self.device_blobs:
+        if self.blobs_on_device:
             self.walkers["blobs"] = self.particles.blob_rows()[rows]        # (row gather on the device)
         elif self.have_blobs:
             self.walkers["blobs"] = self.particles.get("blobs", flat=True)[rows.cpu().numpy()]
@@ -481,7 +495,7 @@ class Sampler:
         w, n = self.walkers, self.n_active
         sl = self.ranks.share(n)
         state = {k: w[k][sl] for k in ROW_KEYS}
-        if self.device_blobs:
+        if self.blobs_on_device:
             blobs = torch.as_tensor(w["blobs"], device=self.flow.device)[sl]     # (numpy right after load_state)
         else:
             blobs = w["blobs"][sl].copy() if self.have_blobs else None
@@ -502,7 +516,7 @@ class Sampler:
         res = _KERNELS[(bool(self.preconditioned), self.sample)](state, funcs, opts)
         for k in ROW_KEYS:
             w[k] = self.ranks.gather_rows(res[k], n)
-        if self.device_blobs:
+        if self.blobs_on_device:
             w["blobs"] = self.ranks.gather_rows(res["blobs"], n)
         elif self.have_blobs:
             w["blobs"] = self._gather_blobs(res["blobs"], n)
@@ -521,10 +535,22 @@ class Sampler:
         return np.concatenate(parts, axis=0)
 
     # --------------------------------------------------------------------------------------------- likelihood
-    def _log_like(self, x):
-        """``sampler.py:807-861``.  Vectorised likelihood: one call on the whole block, no blobs.  Otherwise the
-        likelihood is mapped over the rows (``distribute``: ``map`` or a pool's); a row's return value is either the
-        log-likelihood alone or a sequence ``(logl, blob, blob, ...)`` whose tail is kept as that walker's blob."""
+    def _log_like(self, x, want_blobs=True):
+        """``sampler.py:807-861``.  Vectorised likelihood: one call on the whole block; with ``blobs_dtype`` it returns
+        ``(logl, blobs)``, checked and cast by ``mcmc.host_blobs`` (``blob_shape`` is fixed by the first call;
+        ``want_blobs=False``: dropped unseen).  Otherwise the likelihood is mapped over the rows (``distribute``: ``map`` or a
+        pool's); a row's return value is either the log-likelihood alone or a sequence ``(logl, blob, blob, ...)`` whose tail
+        is kept as that walker's blob."""
+        if self.vectorize and self.host_blobs:
+            out = self.log_likelihood(x)
+            if not want_blobs:
+                if not isinstance(out, tuple) or len(out) != 2:
+                    _mcmc.host_blobs(out, len(x), self.blobs_dtype)      # (raises, naming what came back)
+                return np.asarray(out[0], dtype=np.float64), None
+            logl, blobs = _mcmc.host_blobs(out, len(x), self.blobs_dtype, self._blob_spec)
+            if self._blob_spec is None:
+                self._blob_spec = tuple(blobs.shape[1:])
+            return logl, blobs
         if self.vectorize:
             return self.log_likelihood(x), None
         per_row = list(self.distribute(self.log_likelihood, x))
@@ -578,6 +604,13 @@ class Sampler:
             if self.device_blobs and want_blobs:
                 blobs = self.ranks.gather_rows(self._device_blobs(out, len(xt)), len(x))
             return self.ranks.gather_rows(logl.to(torch.float64).cpu().numpy(), len(x)), blobs
+        if self.host_blobs:
+            # (a vectorised host likelihood's blobs: numpy here -- the warm-up replaces rows on the host before it uploads the
+            #  block; the ranks' shares meet through gather_rows, as tensors)
+            sl = self.ranks.share(len(x))
+            logl, blobs = self._log_like(x[sl], want_blobs=want_blobs)
+            logl = self.ranks.gather_rows(np.asarray(logl, dtype=np.float64), len(x))
+            return logl, (None if blobs is None else self.ranks.gather_rows(blobs, len(x)))
         if self.world == 1:
             return self._log_like(x)
         sl = self.ranks.share(len(x))
