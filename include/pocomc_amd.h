@@ -96,13 +96,18 @@ int pmc_maf_pack(const float* flat, const int32_t* pack_idx, float* packed, int6
 int pmc_maf_forward(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob,
                     int64_t n, void* stream);
 
-/* bf16 matrix-core variant of pmc_maf_forward for the affine flows (BASELINE config 5: "8-layer MAF bf16"):
- * v_mfma_f32_16x16x32_bf16 with fp32 accumulation, the univariate map and the log-determinant in fp32.  The weight
+/* bf16 matrix-core variant of pmc_maf_forward (BASELINE config 5: "8-layer MAF bf16"), for the affine flows (n_out = 2)
+ * and the spline flows of 4, 8 and 16 bins (n_out = 11, 23, 47); any other n_out is refused.
+ * v_mfma_f32_16x16x32_bf16 with fp32 accumulation, the univariate map and the log-determinant in fp32 -- the spline is
+ * evaluated on the unrounded fp32 x from an fp32 panel of its 3 K - 1 parameters.  The weight
  * fragments are a bf16 image of the fp32 master parameters: image u16 [T * image_per_transform], built by
  * pmc_maf_pack_bf16 through MAFSpec.pack_index_bf16 (image[i] = bf16(flat[idx[i]]) or 0; round to nearest even);
- * biases are read from the fp32 image of `m`.  idx i64 [n] or NULL: row gather like pmc_maf_loss_grad.
+ * image_per_transform must be MAFSpec.bf16_layout's; biases are read from the fp32 image of `m`.  idx i64 [n] or NULL:
+ * row gather like pmc_maf_loss_grad.  Fails with a message when one 16-row set of the flow (activations, and for a spline
+ * flow n_out KB of panel) exceeds 160 KB of LDS.  There is no width rule here: Flow(precision="bf16") has one.
  * Precision: activations and weights carry 8 mantissa bits -- the parity tests state the tolerance against the fp32
- * oracle. */
+ * oracle, tests/test_gpu_bf16_model.py and tests/test_gpu_bf16_spline.py hold the kernel to a model that rounds where it
+ * does. */
 int pmc_maf_pack_bf16(const float* flat, const int32_t* pack_idx, uint16_t* image, int64_t n, void* stream);
 int pmc_maf_forward_bf16(const pmc_maf_t* m, const uint16_t* image, int64_t image_per_transform, const float* x,
                          float* z, float* ladj, float* log_prob, int64_t n, const int64_t* idx, void* stream);

@@ -19,6 +19,9 @@ int pmc_check_launch(const char* what);
 
 int pmc_launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob, int64_t n,
                           hipStream_t stream, const int64_t* idx = nullptr);
+// the spline instances of the bf16 forward kernel (maf_forward_bf16_nsf.hip), behind pmc_maf_forward_bf16's checks
+int pmc_launch_forward_bf16_nsf(const pmc_maf_t* m, const uint16_t* image, int64_t per_t, const float* x, float* z, float* ladj,
+                                float* log_prob, int64_t n, const int64_t* idx, hipStream_t stream);
 // The flow inverse (inverse_plan.hip): ONE function decides which kernel instance a call launches; the launchers below
 // launch what its plan names (pa: the fused proposal's arguments, propose_body.h; NULL for the plain inverse of z).
 // fused: PMC_FUSED_NO -- the plan of pmc_maf_inverse(algo), or non-zero with that call's error message; PMC_FUSED_STEP --

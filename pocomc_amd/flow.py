@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maf_spec import MAFSpec, SPEC_BY_NAME, NSF_BY_NAME, spec_by_name
+from .maf_spec import MAFSpec, SPEC_BY_NAME, NSF_BY_NAME, spec_by_name, bf16_forward_refusal
 
 PMC_MAF_TABLES = 4             # pmc_maf_t.reserved: the metadata carries the two-wave affine sweep's table image
 
@@ -52,10 +52,13 @@ class Flow:
 
     def __init__(self, n_dim, flow="nsf3", device=None, seed=None, precision="f32", train_engine=None,
                  inverse_precision=None, inverse_guard=True):                                                                 # default flow as pocomc/flow.py:46
-        """``precision="bf16"`` (affine flows): ``forward`` / ``log_prob`` run on the bf16 matrix cores with fp32
-        accumulation (``csrc/maf_forward_bf16.hip``; BASELINE config 5 names this precision), and ``fit`` takes the bf16
+        """``precision="bf16"`` (affine flows; spline flows of hidden width >= ``train.WIDE_MIN_HIDDEN``, the rule of
+        ``maf_spec.bf16_forward_refusal``): ``forward`` / ``log_prob`` run on the bf16 matrix cores with fp32
+        accumulation (``csrc/maf_forward_bf16.h``; BASELINE config 5 names this precision; the spline itself is evaluated in
+        float32 on the unrounded x), and ``fit`` of an AFFINE flow takes the bf16
         gradient engine (``csrc/maf_train_bf16.hip``: bf16 weights / activations, fp32 master parameters, accumulation and
-        optimizer) when the hidden layers are wide (>= ``train.WIDE_MIN_HIDDEN`` units: the config-5 flow);
+        optimizer) when the hidden layers are wide (>= ``train.WIDE_MIN_HIDDEN`` units: the config-5 flow) -- a spline
+        flow trains and validates with the float32 kernels;
         ``train_engine="f32" | "bf16"`` fixes the engine instead of the width rule (kept by ``save_state``).  The
         parameters, the chain of the inverse and the univariate maps stay float32.  ``inverse_precision`` ("f32" | "bf16" |
         "f16"; default "f32" whatever ``precision`` says -- an explicit opt-in): operand type of the LEFT-LOOKING products of the
@@ -104,8 +107,8 @@ class Flow:
         self.inverse_algo = 0          # PMC_INVERSE_AUTO
         if precision not in ("f32", "bf16"):
             raise ValueError("precision must be 'f32' or 'bf16'")
-        if precision == "bf16" and spec.univariate != "affine":
-            raise NotImplementedError("the bf16 kernels are built for the affine flows")
+        if precision == "bf16" and bf16_forward_refusal(spec):
+            raise NotImplementedError(bf16_forward_refusal(spec))
         self.precision = precision
         if train_engine not in (None, "f32", "bf16"):
             raise ValueError("train_engine must be None, 'f32' or 'bf16'")

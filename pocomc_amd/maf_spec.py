@@ -846,6 +846,20 @@ class MAFSpec:
         return n
 
 
+WIDE_MIN_HIDDEN = 256       # hidden width from which the bf16 matrix cores pay: the bf16 trainer (train.py) and the spline flows' bf16 forward
+
+
+def bf16_forward_refusal(spec: "MAFSpec"):
+    """Why ``Flow(..., precision="bf16")`` refuses ``spec``, or None where it accepts it -- the one rule of that switch.
+    Affine flows: every width (``csrc/maf_forward_bf16.hip``).  Spline flows: ``hidden >= WIDE_MIN_HIDDEN`` only -- a
+    narrower hyper-network has one to four 32-wide k tiles per layer, its call is a chain of barrier-separated layers
+    that the matrix cores do not shorten, so such a flow would pay bf16's rounding for nothing."""
+    if spec.univariate == "affine" or spec.hidden >= WIDE_MIN_HIDDEN:
+        return None
+    return (f"precision='bf16' takes spline flows of hidden width >= {WIDE_MIN_HIDDEN} (this one: {spec.hidden}): "
+            f"narrower flows gain nothing on the bf16 matrix cores and keep the float32 kernels")
+
+
 SPEC_BY_NAME = {"maf3": 3, "maf6": 6, "maf12": 12}
 NSF_BY_NAME = {"nsf3": 3, "nsf6": 6, "nsf12": 12}          # pocomc/flow.py:69-86
 

@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .maf_spec import WIDE_MIN_HIDDEN       # precision="bf16" affine flows at least this wide train on the bf16 matrix cores
 from .mcmc import _pinned_give, _pinned_take
 
 
@@ -127,9 +128,6 @@ def _train_state(flow):
     if ts is None or (ts.light and not want_light):
         flow._train = TrainState(flow, light=want_light)
     return flow._train
-
-
-WIDE_MIN_HIDDEN = 256       # precision="bf16" flows at least this wide train on the bf16 matrix cores
 
 
 class WideState:
