@@ -1,5 +1,6 @@
 // Flow.fit's loss + parameter gradient (pocomc/flow.py:297-323) for the WIDE affine flows on the bf16 matrix cores
-// (BASELINE config 5: D = 128, 8 transforms, H = 512 -- "MFMA-bound flow training").
+// (BASELINE config 5: D = 128, 8 transforms, H = 512 -- "MFMA-bound flow training"), and for the spline flows (the
+// phase kernel's UNI instances and maf_wide_spline_kernel: the same products with OK = (3 bins - 1) DK output rows).
 //
 // Why not the structure of maf_train.hip (a workgroup per 16 rows for the whole chain): a batch is <= 512 rows
 // (sampler.py:289), i.e. 32 workgroups on 256 CUs, each of which streams the whole 23 MB of fp32 weights through one
@@ -16,15 +17,17 @@
 // through LDS and each finish one 16 x 16 quarter with the layer's epilogue (bias, residual, relu / relu gate, the
 // univariate map, the scatter into the canonical gradient).  Dependent layers are separate launches on one stream;
 // weight-gradient products ride along in the launch of the next data-gradient product.  Per batch of <= 512 rows:
-// 4 T + 2 forward and 4 T + 2 backward launches.
+// 4 T + 2 forward and 4 T + 2 backward launches (a spline flow: 5 T + 2 and 5 T + 2, the element kernel of every transform).
 //
 // fp32: master parameters (the bf16 image is re-derived after every optimizer step), x_t, log-scales, the loss and
-// dL/dx_t; bf16: weights, hidden activations and their gradients.  Sums run in a fixed order: a fit is reproducible.
+// dL/dx_t (a spline flow: also its parameters phi, the spline and its own dL/dx); bf16: weights, hidden activations and
+// their gradients (dphi included).  Sums run in a fixed order: a fit is reproducible.
 #include <stdlib.h>
 #include <string>
 #include "bf16.h"
 #include "maf_wg.h"
 #include "pmc_internal.h"
+#include "rqs.h"
 
 #define WIDE_NB 512                 // rows per chunk (larger batches are looped over inside the launch)
 #define WIDE_THREADS 256
@@ -37,8 +40,10 @@ struct WideDims { int D, DK, HK, OK, T, tri; };      // tri: hidden units' degre
 struct WideBufs {
     float *X, *LS, *DD, *G, *C, *RL, *WS;
     u16 *XB, *XBT, *H, *HT, *DA, *DAT, *DO, *DOT;
+    float *PHI, *GX;                // spline flows only: the raw spline parameters [T][NB][OK], the spline's own dL/dx [NB][DK]
 };
 
+template <bool SPLINE>               // (a compile-time switch: the affine kernels' address arithmetic stays what it was)
 __host__ __device__ inline size_t wide_carve(const WideDims& d, char* base, WideBufs* b) {
     size_t o = 0;
     const size_t NB = WIDE_NB;
@@ -59,8 +64,17 @@ __host__ __device__ inline size_t wide_carve(const WideDims& d, char* base, Wide
     u16* DAT = (u16*)take((size_t)d.T * 3 * d.HK * NB * 2);
     u16* DO = (u16*)take((size_t)d.T * NB * d.OK * 2);
     u16* DOT = (u16*)take((size_t)d.T * d.OK * NB * 2);
-    if (b) *b = WideBufs{X, LS, DD, G, C, RL, WS, XB, XBT, H, HT, DA, DAT, DO, DOT};
+    float *PHI = nullptr, *GX = nullptr;
+    if constexpr (SPLINE) {          // (OK = (3 bins - 1) DK: 36 MB at D = 128, T = 6, 8 bins)
+        PHI = (float*)take((size_t)d.T * NB * d.OK * 4);
+        GX = (float*)take(NB * d.DK * 4);
+    }
+    if (b) *b = WideBufs{X, LS, DD, G, C, RL, WS, XB, XBT, H, HT, DA, DAT, DO, DOT, PHI, GX};
     return o;
+}
+
+static size_t wide_scratch(const WideDims& d) {
+    return d.OK != 2 * d.DK ? wide_carve<true>(d, nullptr, nullptr) : wide_carve<false>(d, nullptr, nullptr);
 }
 
 static WideDims wide_dims(const pmc_maf_t& m) {
@@ -68,7 +82,7 @@ static WideDims wide_dims(const pmc_maf_t& m) {
     d.D = m.D; d.T = m.T;
     d.DK = (m.D + 31) / 32 * 32;
     d.HK = (m.Hp + 31) / 32 * 32;
-    d.OK = 2 * d.DK;
+    d.OK = m.n_out * d.DK;
     d.tri = m.tri_ok;
     return d;
 }
@@ -244,7 +258,9 @@ struct WideArgs {
     float* grad; float* loss;
 };
 
-template <int PH>
+// UNI: the univariate map, as in maf_forward_bf16.h -- 0 the affine map, 4 / 8 / 16 a spline of that many bins.  Only the
+// phases that touch the map differ (PH_F3, PH_Z, PH_B4); a spline flow's map itself is maf_wide_spline_kernel below.
+template <int PH, int UNI = 0>
 __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a) {
     using namespace fbf;
     __shared__ __attribute__((aligned(16))) float4 red[4 * 256];
@@ -264,7 +280,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a
     const int64_t* __restrict__ idx = a.idx;
     float* __restrict__ grad = a.grad;
     WideBufs b;
-    wide_carve(d, (char*)a.wd.scratch, &b);
+    wide_carve<UNI != 0>(d, (char*)a.wd.scratch, &b);
     const int it = blockIdx.x;
 
     if constexpr (PH == PH_WSUM) {                                 // sum of the call's weights (flow.py:311), fixed order
@@ -319,7 +335,13 @@ __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a
             c[2] = fmaxf((c[2] + bb.z) + h[2], 0.f); c[3] = fmaxf((c[3] + bb.w) + h[3], 0.f);
             put4(Hout, HK, HoutT, NB, nc, mr, c);
         }
-        if constexpr (PH == PH_F3) {                               // output layer + univariate affine map (fp32)
+        if constexpr (PH == PH_F3 && UNI != 0) {                   // output layer of a spline flow: phi = W3 h2 + b3, unrounded
+            const float4 bb = *reinterpret_cast<const float4*>(v.b3 + mr);
+            const f32x4 c = tile_product(v.W3f, HK, H2, HK, m0, n0, HK, red, wv, lane);
+            *reinterpret_cast<float4*>(b.PHI + ((size_t)t * NB + nc) * OK + mr) =
+                make_float4(c[0] + bb.x, c[1] + bb.y, c[2] + bb.z, c[3] + bb.w);
+        }
+        if constexpr (PH == PH_F3 && UNI == 0) {                   // output layer + univariate affine map (fp32)
             const float4 bb = *reinterpret_cast<const float4*>(v.b3 + mr);
             const int f0 = mr >> 1;
             const float2 xin = *reinterpret_cast<const float2*>(b.X + ((size_t)t * NB + nc) * DK + f0);
@@ -370,7 +392,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a
             for (int f = lane; f < DK; f += 64) {
                 const float gz = (f < D) ? c * Z[f] : 0.0f;
                 b.G[(size_t)n * DK + f] = gz;
-                emit_do(b, d, T - 1, n, f, gz, c);
+                if constexpr (UNI == 0) emit_do(b, d, T - 1, n, f, gz, c);
             }
         }
     }
@@ -454,22 +476,31 @@ __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a
             if (it < nA) {
                 const int m0 = (it / nNT) << 5, n0 = (it % nNT) << 5;
                 const int mr = m0 + 16 * mi + 4 * g, nc = n0 + 16 * ni + p;
-                const float cn = b.C[nc];
-                const float4 gold = *reinterpret_cast<const float4*>(b.G + (size_t)nc * DK + mr);
-                const float4 lsv = *reinterpret_cast<const float4*>(b.LS + ((size_t)t * NB + nc) * DK + mr);
-                const size_t ep = ((size_t)(t > 0 ? t - 1 : 0) * NB + nc) * DK + mr;      // the previous transform's x, ls, 1 / den^2
-                const float4 px = *reinterpret_cast<const float4*>(b.X + ep), pl = *reinterpret_cast<const float4*>(b.LS + ep),
-                             pd = *reinterpret_cast<const float4*>(b.DD + ep);
-                const f32x4 c = tile_product(v.W0b, HK, DA0, HK, m0, n0, HK, red, wv, lane);
-                const float go[4] = {gold.x, gold.y, gold.z, gold.w}, lv[4] = {lsv.x, lsv.y, lsv.z, lsv.w};
-                const float pxv[4] = {px.x, px.y, px.z, px.w}, plv[4] = {pl.x, pl.y, pl.z, pl.w}, pdv[4] = {pd.x, pd.y, pd.z, pd.w};
+                if constexpr (UNI != 0) {       // a spline flow: dL/dx_t = the spline's own dL/dx (maf_wide_spline_kernel) + W0^T da0
+                    const float4 gd = *reinterpret_cast<const float4*>(b.GX + (size_t)nc * DK + mr);
+                    const f32x4 c = tile_product(v.W0b, HK, DA0, HK, m0, n0, HK, red, wv, lane);
+                    float4 o;
+                    o.x = mr < D ? c[0] + gd.x : 0.0f; o.y = mr + 1 < D ? c[1] + gd.y : 0.0f;
+                    o.z = mr + 2 < D ? c[2] + gd.z : 0.0f; o.w = mr + 3 < D ? c[3] + gd.w : 0.0f;
+                    *reinterpret_cast<float4*>(b.G + (size_t)nc * DK + mr) = o;
+                } else {
+                    const float cn = b.C[nc];
+                    const float4 gold = *reinterpret_cast<const float4*>(b.G + (size_t)nc * DK + mr);
+                    const float4 lsv = *reinterpret_cast<const float4*>(b.LS + ((size_t)t * NB + nc) * DK + mr);
+                    const size_t ep = ((size_t)(t > 0 ? t - 1 : 0) * NB + nc) * DK + mr;      // the previous transform's x, ls, 1 / den^2
+                    const float4 px = *reinterpret_cast<const float4*>(b.X + ep), pl = *reinterpret_cast<const float4*>(b.LS + ep),
+                                 pd = *reinterpret_cast<const float4*>(b.DD + ep);
+                    const f32x4 c = tile_product(v.W0b, HK, DA0, HK, m0, n0, HK, red, wv, lane);
+                    const float go[4] = {gold.x, gold.y, gold.z, gold.w}, lv[4] = {lsv.x, lsv.y, lsv.z, lsv.w};
+                    const float pxv[4] = {px.x, px.y, px.z, px.w}, plv[4] = {pl.x, pl.y, pl.z, pl.w}, pdv[4] = {pd.x, pd.y, pd.z, pd.w};
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int f = mr + r;
-                    float gx = 0.0f;
-                    if (f < D) gx = c[r] + go[r] * expf(lv[r]);
-                    b.G[(size_t)nc * DK + f] = gx;
-                    if (t > 0) (void)emit_do_vals(b, d, t - 1, nc, f, gx, cn, pxv[r], plv[r], pdv[r]);
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = mr + r;
+                        float gx = 0.0f;
+                        if (f < D) gx = c[r] + go[r] * expf(lv[r]);
+                        b.G[(size_t)nc * DK + f] = gx;
+                        if (t > 0) (void)emit_do_vals(b, d, t - 1, nc, f, gx, cn, pxv[r], plv[r], pdv[r]);
+                    }
                 }
             } else {
                 const int j = it - nA, nKT = HK >> 5;
@@ -491,6 +522,61 @@ __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a
 }
 
 
+// The spline flows' univariate map, one thread per (row, feature) of a chunk, features fastest (a row's OK parameters and
+// its DO row are contiguous: a wavefront reads and writes one stretch of memory).  The parameters phi (PH_F3, float32,
+// unrounded) and the unrounded x_t go through rqs.h's element code, the float32 trainer's.
+//   BWD = 0, behind PH_F3 of transform t:  y -> X[t + 1] (float32) and XB / XBT of transform t + 1 (bf16, layer 0's
+//            operand), the element's log-derivative -> LS (PH_Z sums it).
+//   BWD = 1, in front of PH_B1 of transform t:  rqs_backward_t(phi, x_t, gy = G, gl = -c_n) -> dphi rounded to bf16 into
+//            DO / DOT (what emit_do_vals writes for the affine map), the spline's own dL/dx -> GX (PH_B4 adds W0^T da0).
+// Padded rows and features write zeros: the products that read DO / DOT sum over them.
+template <int K, int BWD>
+__global__ __launch_bounds__(WIDE_THREADS) void maf_wide_spline_kernel(WideArgs a) {
+    using namespace fbf;
+    constexpr int NO = RQS_NOUT_OF(K);
+    const WideDims& d = a.d;
+    const int D = d.D, DK = d.DK, OK = d.OK, T = d.T, NB = WIDE_NB, t = a.t;
+    const int NBc = (a.nb + 31) & ~31;
+    WideBufs b;
+    wide_carve<true>(d, (char*)a.wd.scratch, &b);
+    const int e = blockIdx.x * WIDE_THREADS + threadIdx.x;
+    if (e >= NBc * DK) return;
+    const int n = e / DK, f = e - n * DK;
+    const bool live = n < a.nb && f < D;
+    const size_t ex = ((size_t)t * NB + n) * DK + f;
+    float phi[NO];
+    if (live) {
+        const float* __restrict__ pp = b.PHI + ((size_t)t * NB + n) * OK + NO * f;
+#pragma unroll
+        for (int j = 0; j < NO; ++j) phi[j] = pp[j];
+    }
+    if constexpr (BWD == 0) {
+        float y = 0.0f, l = 0.0f;
+        if (live) rqs_forward_t<K>(phi, b.X[ex], y, l);
+        b.LS[ex] = l;
+        b.X[ex + (size_t)NB * DK] = y;
+        if (t + 1 < T) {
+            const u16 h = to_bf16(y);
+            b.XB[((size_t)(t + 1) * NB + n) * DK + f] = h;
+            b.XBT[((size_t)(t + 1) * DK + f) * NB + n] = h;
+        }
+    } else {
+        float dphi[NO], gx = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NO; ++j) dphi[j] = 0.0f;
+        if (live) rqs_backward_t<K>(phi, b.X[ex], b.G[(size_t)n * DK + f], -b.C[n], dphi, gx);
+        b.GX[(size_t)n * DK + f] = gx;
+        u16* DOr = b.DO + ((size_t)t * NB + n) * OK + NO * f;
+        u16* DOc = b.DOT + ((size_t)t * OK + NO * f) * NB + n;
+#pragma unroll
+        for (int j = 0; j < NO; ++j) {
+            const u16 h = to_bf16(dphi[j]);
+            DOr[j] = h;
+            DOc[(size_t)j * NB] = h;
+        }
+    }
+}
+
 // (Round 4 built "fat phases" here -- a workgroup of sixteen wavefronts per 16 rows sweeping ALL layers of ALL transforms
 // with the activations in LDS, three launches instead of 68 -- and measured them SLOWER: 686 / 662 us per optimizer step of
 // 512 / 64 rows against 559 / 421 for the per-layer launches.  A workgroup that sweeps all layers streams the flow's whole
@@ -501,18 +587,19 @@ __global__ __launch_bounds__(WIDE_THREADS) void maf_wide_phase_kernel(WideArgs a
 extern "C" int64_t pmc_maf_wide_scratch_bytes(const pmc_maf_t* m) {
     if (!m) return 0;
     const WideDims d = wide_dims(*m);
-    return (int64_t)wide_carve(d, nullptr, nullptr);
+    return (int64_t)wide_scratch(d);
 }
 
 static int wide_check(const pmc_maf_t* m, const pmc_maf_wide_t* wd, const char* who) {
     if (!m || !wd || !wd->image || !wd->image_idx || !wd->bias || !wd->bias_idx || !wd->scratch)
         return pmc_fail((std::string(who) + ": incomplete descriptor").c_str());
-    if (m->n_out != 2) return pmc_fail((std::string(who) + ": affine flows only").c_str());
+    if (m->n_out != 2 && m->n_out != RQS_NOUT_OF(4) && m->n_out != RQS_NOUT_OF(8) && m->n_out != RQS_NOUT_OF(16))
+        return pmc_fail((std::string(who) + ": affine flows and spline flows of 4, 8 or 16 bins only").c_str());
     const WideDims d = wide_dims(*m);
     const int64_t per = 2LL * ((int64_t)d.HK * d.DK + 2LL * d.HK * d.HK + (int64_t)d.OK * d.HK);
     if (wd->image_per_transform != per || wd->bias_per_transform != 3LL * d.HK + d.OK)
         return pmc_fail((std::string(who) + ": image sizes do not match the flow").c_str());
-    if (wd->scratch_bytes < (int64_t)wide_carve(d, nullptr, nullptr))
+    if (wd->scratch_bytes < (int64_t)wide_scratch(d))
         return pmc_fail((std::string(who) + ": scratch too small").c_str());
     return 0;
 }
@@ -524,6 +611,8 @@ extern "C" int pmc_maf_wide_refresh(const pmc_maf_t* m, const pmc_maf_wide_t* wd
     return pmc_maf_pack(params, wd->bias_idx, wd->bias, (int64_t)m->T * wd->bias_per_transform, stream);
 }
 
+// UNI: 0 the affine map, else the spline's bins (the phase kernel's parameter)
+template <int UNI>
 static int launch_wide_part(const pmc_maf_t* m, const pmc_maf_wide_t* wd, const float* x, const float* w, const int64_t* idx,
                             float wmul, float* grad, float* loss, int64_t n, hipStream_t st, bool do_wsum) {
     WideArgs a;
@@ -533,33 +622,41 @@ static int launch_wide_part(const pmc_maf_t* m, const pmc_maf_wide_t* wd, const 
     const WideDims& d = a.d;
     const int T = d.T, mH = d.HK >> 5, mD = d.DK >> 5, mO = d.OK >> 5;
 #define PHASE(PH, GRID) hipLaunchKernelGGL((maf_wide_phase_kernel<PH>), dim3((unsigned)(GRID)), dim3(WIDE_THREADS), 0, st, a)
+#define PHASE_U(PH, GRID) hipLaunchKernelGGL((maf_wide_phase_kernel<PH, UNI>), dim3((unsigned)(GRID)), dim3(WIDE_THREADS), 0, st, a)
+#define SPLINE(BWD, GRID) \
+    if constexpr (UNI != 0) hipLaunchKernelGGL((maf_wide_spline_kernel<UNI, BWD>), dim3((unsigned)(GRID)), dim3(WIDE_THREADS), 0, st, a)
     if (do_wsum && w && !wd->wsum) PHASE(PH_WSUM, 1);
     for (int64_t c0 = 0; c0 < n; c0 += WIDE_NB) {
         a.c0 = c0;
         a.nb = (int)((n - c0 < WIDE_NB) ? n - c0 : WIDE_NB);
         a.first = (c0 == 0);
         const int NBc = (a.nb + 31) & ~31, nNT = NBc >> 5;
-        PHASE(PH_GATHER, ((int64_t)NBc * d.DK + WIDE_THREADS - 1) / WIDE_THREADS);
+        const int64_t nEl = ((int64_t)NBc * d.DK + WIDE_THREADS - 1) / WIDE_THREADS;      // a thread per (row, feature)
+        PHASE(PH_GATHER, nEl);
         for (int t = 0; t < T; ++t) {
             a.t = t;
             PHASE(PH_F0, mH * nNT);
             a.layer = 1; PHASE(PH_F12, mH * nNT);
             a.layer = 2; PHASE(PH_F12, mH * nNT);
-            PHASE(PH_F3, mO * nNT);
+            PHASE_U(PH_F3, mO * nNT);
+            SPLINE(0, nEl);
         }
-        PHASE(PH_Z, (NBc + 3) / 4);
+        PHASE_U(PH_Z, (NBc + 3) / 4);
         for (int t = T - 1; t >= 0; --t) {
             a.t = t;
+            SPLINE(1, nEl);
             PHASE(PH_B1, mH * nNT + (t + 1 < T ? mH * mD + (d.HK >> 4) : 0));
             PHASE(PH_B2, mH * nNT + mO * mH + (d.OK >> 4) + (d.HK >> 4));
             PHASE(PH_B3, mH * nNT + mH * mH + (d.HK >> 4));
-            PHASE(PH_B4, mD * nNT + mH * mH);
+            PHASE_U(PH_B4, mD * nNT + mH * mH);
         }
         a.t = -1;
         PHASE(PH_B1, mH * mD + (d.HK >> 4));                       // dW0, db0 of the first transform
         PHASE(PH_LOSS, 1);
     }
 #undef PHASE
+#undef PHASE_U
+#undef SPLINE
     return pmc_check_launch("maf_wide_phase_kernel");
 }
 
@@ -570,7 +667,12 @@ static int launch_wide_part(const pmc_maf_t* m, const pmc_maf_wide_t* wd, const 
 // stream), not by idle CUs that a second chain could fill: more launches, more time.  Removed again.)
 static int launch_wide(const pmc_maf_t* m, const pmc_maf_wide_t* wd, const float* x, const float* w, const int64_t* idx,
                        float wmul, float* grad, float* loss, int64_t n, hipStream_t st) {
-    return launch_wide_part(m, wd, x, w, idx, wmul, grad, loss, n, st, true);
+    switch (m->n_out) {              // (wide_check has admitted these four)
+    case RQS_NOUT_OF(4): return launch_wide_part<4>(m, wd, x, w, idx, wmul, grad, loss, n, st, true);
+    case RQS_NOUT_OF(8): return launch_wide_part<8>(m, wd, x, w, idx, wmul, grad, loss, n, st, true);
+    case RQS_NOUT_OF(16): return launch_wide_part<16>(m, wd, x, w, idx, wmul, grad, loss, n, st, true);
+    default: return launch_wide_part<0>(m, wd, x, w, idx, wmul, grad, loss, n, st, true);
+    }
 }
 
 extern "C" int pmc_maf_loss_grad_bf16(const pmc_maf_t* m, const pmc_maf_wide_t* wd, const float* x, const float* w,

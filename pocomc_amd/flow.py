@@ -58,8 +58,9 @@ class Flow:
         float32 on the unrounded x), and ``fit`` of an AFFINE flow takes the bf16
         gradient engine (``csrc/maf_train_bf16.hip``: bf16 weights / activations, fp32 master parameters, accumulation and
         optimizer) when the hidden layers are wide (>= ``train.WIDE_MIN_HIDDEN`` units: the config-5 flow) -- a spline
-        flow trains and validates with the float32 kernels;
-        ``train_engine="f32" | "bf16"`` fixes the engine instead of the width rule (kept by ``save_state``).  The
+        flow trains and validates with the float32 kernels unless ``train_engine="bf16_spline"`` asks for the same
+        engine's spline instances (an explicit opt-in: no width rule; validation stays float32);
+        ``train_engine="f32" | "bf16"`` fixes the affine flows' engine instead of the width rule (all kept by ``save_state``).  The
         parameters, the chain of the inverse and the univariate maps stay float32.  ``inverse_precision`` ("f32" | "bf16" |
         "f16"; default "f32" whatever ``precision`` says -- an explicit opt-in): operand type of the LEFT-LOOKING products of the
         inverse sweep of the wide flows (``csrc/maf_inverse_tri6.hip``: everything left of the diagonal tile, multiplied by
@@ -110,8 +111,11 @@ class Flow:
         if precision == "bf16" and bf16_forward_refusal(spec):
             raise NotImplementedError(bf16_forward_refusal(spec))
         self.precision = precision
-        if train_engine not in (None, "f32", "bf16"):
-            raise ValueError("train_engine must be None, 'f32' or 'bf16'")
+        if train_engine not in (None, "f32", "bf16", "bf16_spline"):
+            raise ValueError("train_engine must be None, 'f32', 'bf16' or 'bf16_spline'")
+        if train_engine == "bf16_spline" and (spec.univariate != "rqs" or precision != "bf16"):
+            raise ValueError("train_engine='bf16_spline' needs a spline flow with precision='bf16' "
+                             "(affine flows: train_engine='bf16')")
         self.train_engine = train_engine
         if inverse_precision is None:
             inverse_precision = "f32"          # (also what a checkpoint without the key reloads as)

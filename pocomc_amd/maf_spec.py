@@ -561,18 +561,17 @@ class MAFSpec:
     def wide_layout(self):
         """Sizes of the row-major bf16 weight image of ``csrc/maf_train_bf16.hip`` (elements per transform):
         ``W0f [HK][DK]  W0b = W0f^T  W1f [HK][HK]  W1b  W2f  W2b  W3f [OK][HK]  W3b`` and of its float32 bias image
-        ``b0 b1 b2 [HK]  b3 [OK]``; hidden units in slot order, features in canonical order, W3 rows ``2 feature + s``."""
+        ``b0 b1 b2 [HK]  b3 [OK]``; hidden units in slot order, features in canonical order, ``OK = n_out DK`` and W3 rows
+        ``n_out feature + s`` (the canonical order: shift, raw for the affine map; widths, heights, derivatives for a spline)."""
         DK, HK = _ceil_to(self.n_dim, 32), _ceil_to(self.Hp, 32)
-        OK = 2 * DK
+        OK = self.n_out * DK
         return dict(DK=DK, HK=HK, OK=OK, per_transform=2 * (HK * DK + 2 * HK * HK + OK * HK),
                     bias_per_transform=3 * HK + OK)
 
     def wide_index(self):
         """``(image_idx, bias_idx)`` int32: canonical index of every element of the two images, -1 where masked or
         padded.  ``image[i] = bf16(flat[idx[i]])``; the ``W?f`` parts double as the scatter map of the weight gradients."""
-        if self.univariate != "affine":
-            raise NotImplementedError("the bf16 training image is built for the affine flows")
-        D, H = self.n_dim, self.hidden
+        D, H, NO = self.n_dim, self.hidden, self.n_out
         L = self.wide_layout()
         DK, HK, OK = L["DK"], L["HK"], L["OK"]
         su = np.full(HK, -1, dtype=np.int64)
@@ -582,8 +581,8 @@ class MAFSpec:
         feat = np.arange(DK)
         fv = feat < D
         fc = np.where(fv, feat, 0)
-        orow = np.arange(OK)                                  # 2 feature + s
-        ov = (orow // 2) < D
+        orow = np.arange(OK)                                  # n_out feature + s
+        ov = (orow // NO) < D
         oc = np.where(ov, orow, 0)
         img = np.full(self.n_transforms * L["per_transform"], -1, dtype=np.int64)
         bias = np.full(self.n_transforms * L["bias_per_transform"], -1, dtype=np.int64)

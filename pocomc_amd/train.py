@@ -132,7 +132,8 @@ def _train_state(flow):
 
 class WideState:
     """Device side of ``csrc/maf_train_bf16.hip`` (``pmc_maf_wide_t``): the row-major bf16 weight image with its index
-    map, the float32 bias image and the activation scratch."""
+    map, the float32 bias image and the activation scratch -- for an affine flow or a spline flow (``OK = n_out DK``
+    output rows; the scratch of a spline flow also holds its raw spline parameters in float32)."""
 
     def __init__(self, flow):
         spec, dev, lib = flow.spec, flow.device, flow.lib
@@ -158,13 +159,20 @@ class WideState:
 
 def _wide_state(flow):
     """The bf16 training engine of this flow, or None (float32 kernels): ``precision="bf16"`` affine flows of hidden
-    width >= WIDE_MIN_HIDDEN; ``flow.train_engine = "f32" | "bf16"`` overrides the width rule."""
+    width >= WIDE_MIN_HIDDEN; ``flow.train_engine = "f32" | "bf16"`` overrides the width rule.  A spline flow takes the
+    engine only when asked: ``flow.train_engine = "bf16_spline"`` with ``precision="bf16"``, at any width."""
     engine = getattr(flow, "train_engine", None)
-    if engine == "f32" or getattr(flow, "precision", "f32") != "bf16" or flow.spec.univariate != "affine":
+    bf16 = getattr(flow, "precision", "f32") == "bf16"
+    if engine == "bf16_spline":
+        if not bf16 or flow.spec.univariate != "rqs":
+            raise ValueError("train_engine='bf16_spline' needs a spline flow with precision='bf16' "
+                             "(affine flows: train_engine='bf16')")
+    elif engine == "f32" or not bf16 or flow.spec.univariate != "affine":
         if engine == "bf16":
-            raise ValueError("train_engine='bf16' needs an affine flow with precision='bf16'")
+            raise ValueError("train_engine='bf16' needs an affine flow with precision='bf16' "
+                             "(spline flows: train_engine='bf16_spline')")
         return None
-    if engine != "bf16" and flow.spec.hidden < WIDE_MIN_HIDDEN:
+    elif engine != "bf16" and flow.spec.hidden < WIDE_MIN_HIDDEN:
         return None
     if getattr(flow, "_wide", None) is None:
         flow._wide = WideState(flow)
