@@ -62,6 +62,8 @@ typedef struct pmc_maf {
 
 #define PMC_MAF_VARIANT_LEFT_LOOKING 1  /* two-wave spline sweep: the burst wave forms no output partials ahead of time */
 #define PMC_MAF_VARIANT_LANE_FOUR 2     /* lane-per-walker sweep of a flow of >= 16 hidden tiles: no fifth wavefront */
+#define PMC_MAF_VARIANT_LEAN_LDS 8      /* forward / D-pass workgroup kernel and float32 trainer: the instances with two hidden-width
+                                         * LDS arrays (pmc_maf_lds_plan) also where the full ones fit -- a test switch, not an option */
 /* meta carries the constant tables of the two-wave affine sweep (D <= 64) in the layout of the kernel's LDS, so that a
  * workgroup copies them instead of deriving them from the quad meta words and the rank maps on every launch:
  *   DGT [nT+2][16]  per hidden tile (two rows of "no groups" behind the last): words 0..3 the ranks its four degree groups
@@ -145,10 +147,29 @@ int pmc_maf_inverse_auto_is_nsf2(const pmc_maf_t* m);
 #define PMC_SWEEP_LANE 5
 #define PMC_SWEEP_NSF_SOLO 6
 #define PMC_SWEEP_NSF_DUO 7
+#define PMC_SWEEP_DPASS_LEAN 8     /* the D-pass algorithm through the lean instance of the forward workgroup kernel (affine and
+                                    * spline flows): AUTO / NAIVE where no sweep and no other D-pass kernel fits the LDS */
 typedef struct pmc_inverse_plan {
     int32_t sweep, fused, epilogue, maxo, fm, subsets, waves, helper_fmt, lds_bytes;
 } pmc_inverse_plan_t;
 int pmc_maf_inverse_plan(const pmc_maf_t* m, int64_t n, int algo, int fused, pmc_inverse_plan_t* plan);
+
+/* Which instance of the float32 flow kernels a flow takes, by the LDS of one workgroup (160 KiB): the forward workgroup
+ * kernel (pmc_maf_forward, log_prob, pmc_maf_valid_epoch), the same kernel's D-pass inverse, and the trainer's chain kernel
+ * (pmc_maf_loss_grad, pmc_maf_train_epoch).  The FULL instances keep three (trainer: four) hidden-width activation arrays
+ * of 16 rows in LDS, the LEAN ones two: the forward kernel's third array aliases the first, the trainer reads the
+ * activations its backward sweep gates with from the global scratch.  A flow takes the full instance wherever that fits
+ * and the lean one otherwise (or with PMC_MAF_VARIANT_LEAN_LDS).  Per call: *_lean 0 / 1 and *_lds_bytes of the instance
+ * taken, -1 and the full instance's bytes where neither fits (the call then fails); *_full_bytes is the full instance's
+ * size whatever is taken.  forward: for the eight-wavefront launch (calls of <= 16384 rows; the four-wavefront one is 128
+ * bytes smaller).  Like pmc_maf_inverse_plan a pure host function of the layout fields.  Returns non-zero (pmc_last_error:
+ * the message of the first call that would fail, in the order forward, D-pass, training) where an instance is missing. */
+typedef struct pmc_flow_lds_plan {
+    int32_t forward_lean, forward_lds_bytes, forward_full_bytes;
+    int32_t dpass_lean, dpass_lds_bytes, dpass_full_bytes;
+    int32_t train_lean, train_lds_bytes, train_full_bytes;
+} pmc_flow_lds_plan_t;
+int pmc_maf_lds_plan(const pmc_maf_t* m, pmc_flow_lds_plan_t* plan);
 
 /* 16-bit helper image of the lane-per-walker inverse sweep (Flow.inverse of the wide flows, flow.py:116-132, in the opt-in
  * precision of BASELINE config 5): image u16 [pmc_maf_lane16_elems(m)], derived on the device from m->packed (call again

@@ -30,6 +30,10 @@ class pmc_inverse_plan_t(C.Structure):
                                          "lds_bytes")]
 
 
+class pmc_flow_lds_plan_t(C.Structure):
+    _fields_ = [(f"{call}_{k}", C.c_int32) for call in ("forward", "dpass", "train") for k in ("lean", "lds_bytes", "full_bytes")]
+
+
 class pmc_maf_train_t(C.Structure):
     _fields_ = [("packedT", c_p), ("gmap", c_p), ("pkT_per_transform", C.c_int64),
                 ("gmap_per_transform", C.c_int64),
@@ -123,6 +127,7 @@ SIGNATURES = {
     "pmc_maf_inverse_auto_is_lane": (C.c_int, [C.POINTER(pmc_maf_t)]),
     "pmc_maf_inverse_auto_is_nsf2": (C.c_int, [C.POINTER(pmc_maf_t)]),
     "pmc_maf_inverse_plan": (C.c_int, [C.POINTER(pmc_maf_t), C.c_int64, C.c_int, C.c_int, C.POINTER(pmc_inverse_plan_t)]),
+    "pmc_maf_lds_plan": (C.c_int, [C.POINTER(pmc_maf_t), C.POINTER(pmc_flow_lds_plan_t)]),
     "pmc_maf_train_waves": (C.c_int, [C.POINTER(pmc_maf_t)]),
     "pmc_abi_version": (C.c_int, []),
     "pmc_build_id": (C.c_char_p, []),

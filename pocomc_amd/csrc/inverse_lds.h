@@ -60,9 +60,19 @@ static inline size_t pmc_lds_nsf_solo(const pmc_maf_t* m) { return (size_t)(2 * 
 static inline size_t pmc_lds_dense(const pmc_maf_t* m, int n_rank_arrays) { return (size_t)(n_rank_arrays * m->Dp * 16 + 3 * m->Hp * 16) * sizeof(float); }
 
 // ---- workgroup kernel of the forward pass and of the spline flows' D-pass inverse (maf_forward_wg.hip): nw wavefronts, the
-// univariate map's panel, the inverse's iterate
-static inline size_t pmc_lds_wg(const pmc_maf_t* m, int nw, int panel_tiles, int inverse) {
-    return (size_t)(2 * m->Dp * 16 + 3 * m->Hp * 16 + 16 * nw + panel_tiles * 256 + (inverse ? m->Dp * 16 : 0)) * sizeof(float);
+// univariate map's panel, the inverse's iterate.  lean: the instance whose third activation array aliases the first
+static inline size_t pmc_lds_wg(const pmc_maf_t* m, int nw, int panel_tiles, int inverse, int lean = 0) {
+    return (size_t)(2 * m->Dp * 16 + (lean ? 2 : 3) * m->Hp * 16 + 16 * nw + panel_tiles * 256 + (inverse ? m->Dp * 16 : 0)) * sizeof(float);
+}
+static inline int pmc_wg_panel_tiles(const pmc_maf_t* m) { return m->n_out == 2 ? 0 : m->n_out; }
+// Which instance of the workgroup kernel a call takes: the full one wherever it fits (what every flow that ran before the
+// lean instances existed keeps launching), the lean one where only that fits or PMC_MAF_VARIANT_LEAN_LDS asks for it.
+// Returns the launch's LDS bytes and sets *lean, or 0: neither fits
+static inline size_t pmc_wg_instance(const pmc_maf_t* m, int nw, int inverse, int* lean) {
+    const size_t full = pmc_lds_wg(m, nw, pmc_wg_panel_tiles(m), inverse, 0), small = pmc_lds_wg(m, nw, pmc_wg_panel_tiles(m), inverse, 1);
+    *lean = (m->reserved & PMC_MAF_VARIANT_LEAN_LDS) || full > PMC_LDS_CAP;
+    const size_t lds = *lean ? small : full;
+    return lds <= PMC_LDS_CAP ? lds : 0;
 }
 
 // A launch with dynamic LDS: hipFuncSetAttribute first when it is more than 48 KiB (every such launch: nothing is remembered)

@@ -1,7 +1,7 @@
 // Which flow-inverse kernel runs: the one place that decides it (host code only, no kernel).
 //
 // Seven kernels invert a flow (pocomc/mcmc.py:88, every preconditioned step): the two D-pass kernels of the reference's
-// algorithm, the register-chain sweeps of the affine flows with one (SOLO) or two (DUO) wavefronts per 16 walkers, the
+// algorithm (the workgroup one in a full and a lean instance), the register-chain sweeps of the affine flows with one (SOLO) or two (DUO) wavefronts per 16 walkers, the
 // lane-per-walker sweep (LANE), the spline sweeps with one (NSF_SOLO) or two (NSF_DUO) wavefronts.  pmc_plan_inverse maps
 // (flow, rows, algo) to the instance pmc_maf_inverse / pmc_step_pre launch -- or, asked for the fused launch, to the
 // proposal + inverse (+ scaler epilogue) instance of the step, if there is one.  What a sweep covers is a predicate below;
@@ -101,10 +101,25 @@ static void set_lane(pmc_inverse_plan_t* p, const pmc_maf_t* m, int64_t n, bool 
     p->fm = fused ? fused_fm(m) : 0;
     set_plain(p, PMC_SWEEP_LANE, pmc_lds_lane(m, p->subsets, hb));
 }
+// The lean D-pass workgroup kernel as the last resort covers the default-width flows: MAFSpec(D) has at most 51 hidden
+// tiles for D <= 157, the widest MCMC step (H = 512 padded to whole quads per degree: Hp = 816 at D = 102 - 104).  Layouts
+// beyond that are hand-made ones, and they keep the refusals they always had (tests/test_inverse_plan_cpu.py pins 64 and
+// 65 tiles at D = 66 to the D-pass kernel's error): D + 1 full passes of a wider flow are not a plan to fall into silently.
+#define PMC_LEAN_DPASS_MAX_TILES 51
+static bool lean_forced(const pmc_maf_t* m) { return (m->reserved & PMC_MAF_VARIANT_LEAN_LDS) != 0; }
+static bool set_dpass_lean(pmc_inverse_plan_t* p, const pmc_maf_t* m) {
+    const size_t lds = pmc_lds_wg(m, 8, pmc_wg_panel_tiles(m), 1, 1);
+    if (lds > PMC_LDS_CAP || (!lean_forced(m) && m->nT > PMC_LEAN_DPASS_MAX_TILES)) return false;
+    set_plain(p, PMC_SWEEP_DPASS_LEAN, lds);
+    return true;
+}
 static const char* set_dpass(pmc_inverse_plan_t* p, const pmc_maf_t* m) {
     const bool affine = m->n_out == 2;
     const size_t lds = affine ? pmc_lds_dense(m, 3) : pmc_lds_wg(m, 8, m->n_out, 1);
-    if (lds > PMC_LDS_CAP) return affine ? "MAF too wide for one wave's LDS budget (160 KiB)" : "pmc_maf_forward: flow too wide for 160 KB of LDS";
+    if (lean_forced(m) || lds > PMC_LDS_CAP) {
+        if (set_dpass_lean(p, m)) return nullptr;
+        return affine ? "MAF too wide for one wave's LDS budget (160 KiB)" : "pmc_maf_forward: flow too wide for 160 KB of LDS";
+    }
     set_plain(p, affine ? PMC_SWEEP_DPASS_AFFINE : PMC_SWEEP_DPASS_SPLINE, lds);
     return nullptr;
 }
@@ -134,7 +149,8 @@ static void plan_fused(const pmc_maf_t* m, int64_t n, int algo, bool any, bool w
 static const char* plan_spline(const pmc_maf_t* m, int algo, pmc_inverse_plan_t* p) {
     // triangular sweep, or the D-pass algorithm of the reference (zuko) as cross-check and for layouts whose degree groups
     // exceed a tile (the sweeps are built for the reference's 8 bins; other bin counts take zuko's own D-pass algorithm)
-    if (algo == PMC_INVERSE_AUTO) algo = (m->tri_ok && m->n_out == 23) ? PMC_INVERSE_TRIANGULAR : PMC_INVERSE_NAIVE;
+    const bool any = algo == PMC_INVERSE_AUTO;
+    if (any) algo = (m->tri_ok && m->n_out == 23) ? PMC_INVERSE_TRIANGULAR : PMC_INVERSE_NAIVE;
     if (algo == PMC_INVERSE_NAIVE) return set_dpass(p, m);
     if (algo != PMC_INVERSE_TRIANGULAR && algo != PMC_INVERSE_TRIANGULAR_SOLO && algo != PMC_INVERSE_TRIANGULAR_DUO)
         return "pmc_maf_inverse: spline flows know PMC_INVERSE_TRIANGULAR (_SOLO, _DUO) and PMC_INVERSE_NAIVE";
@@ -143,7 +159,11 @@ static const char* plan_spline(const pmc_maf_t* m, int algo, pmc_inverse_plan_t*
     // two wavefronts per 16 rows (D <= 64), else / on request the lone-wave sweep
     if (algo != PMC_INVERSE_TRIANGULAR_SOLO && nsf_duo_covers(m)) { set_plain(p, PMC_SWEEP_NSF_DUO, pmc_lds_nsf_duo(m)); return nullptr; }
     if (algo == PMC_INVERSE_TRIANGULAR_DUO) return "pmc_maf_inverse: the two-wave spline sweep needs D <= 64 and its tiles in 160 KiB of LDS";
-    if (pmc_lds_nsf_solo(m) > PMC_LDS_CAP) return "pmc_maf_inverse: flow too wide for one wave's LDS budget (160 KiB)";
+    if (pmc_lds_nsf_solo(m) > PMC_LDS_CAP) {
+        // (AUTO: the lean D-pass kernel covers what is left -- the full one is larger than the lone-wave sweep)
+        if (any && set_dpass_lean(p, m)) return nullptr;
+        return "pmc_maf_inverse: flow too wide for one wave's LDS budget (160 KiB)";
+    }
     set_plain(p, PMC_SWEEP_NSF_SOLO, pmc_lds_nsf_solo(m));
     return nullptr;
 }
@@ -211,3 +231,27 @@ static int auto_sweep(const pmc_maf_t* m, int64_t n) {
 extern "C" int pmc_maf_inverse_auto_is_duo(const pmc_maf_t* m, int64_t n) { return auto_sweep(m, n) == PMC_SWEEP_DUO; }
 extern "C" int pmc_maf_inverse_auto_is_lane(const pmc_maf_t* m) { return auto_sweep(m, 1) == PMC_SWEEP_LANE; }
 extern "C" int pmc_maf_inverse_auto_is_nsf2(const pmc_maf_t* m) { return auto_sweep(m, 1) == PMC_SWEEP_NSF_DUO; }
+
+// ---- which instance of the float32 flow kernels a flow takes (include/pocomc_amd.h: pmc_flow_lds_plan_t)
+extern "C" int pmc_maf_lds_plan(const pmc_maf_t* m, pmc_flow_lds_plan_t* plan) {
+    if (!m || !plan) return pmc_fail("pmc_maf_lds_plan: bad argument");
+    const char* err = nullptr;
+    int lean;
+    size_t lds = pmc_wg_instance(m, 8, 0, &lean);
+    plan->forward_full_bytes = (int32_t)pmc_lds_wg(m, 8, pmc_wg_panel_tiles(m), 0, 0);
+    plan->forward_lean = lds ? lean : -1;
+    plan->forward_lds_bytes = (int32_t)(lds ? lds : (size_t)plan->forward_full_bytes);
+    if (!lds) err = "pmc_maf_forward: flow too wide for 160 KB of LDS";
+    lds = pmc_wg_instance(m, 8, 1, &lean);
+    plan->dpass_full_bytes = (int32_t)pmc_lds_wg(m, 8, pmc_wg_panel_tiles(m), 1, 0);
+    plan->dpass_lean = lds ? lean : -1;
+    plan->dpass_lds_bytes = (int32_t)(lds ? lds : (size_t)plan->dpass_full_bytes);
+    if (!lds && !err) err = "pmc_maf_forward: flow too wide for 160 KB of LDS";
+    size_t full;
+    lds = pmc_train_instance(m, &lean, nullptr, &full);
+    plan->train_full_bytes = (int32_t)full;
+    plan->train_lean = lds ? lean : -1;
+    plan->train_lds_bytes = (int32_t)(lds ? lds : full);
+    if (!lds && !err) err = "pmc_maf_loss_grad: flow too wide for the 160 KB LDS of one workgroup";
+    return err ? pmc_fail(err) : 0;
+}

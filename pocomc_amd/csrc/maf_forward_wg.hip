@@ -33,7 +33,9 @@ __device__ __forceinline__ void rqs_panel(const pmc_maf_t& m, const MafView& w, 
 }
 
 // MODE 0: forward (x -> z, ladj of the forward map).  MODE 1: D-pass inverse (z -> x, ladj of the inverse map).
-template <int NW, int UNI, int MODE>
+// LEAN: two hidden-width arrays instead of three -- h2 is written over h0, which is dead once h1 is complete (the hidden
+// layers are separated by barriers, and layer 2 reads h1 only).  The same arithmetic in the same order: the same bits.
+template <int NW, int UNI, int MODE, bool LEAN>
 __global__ __launch_bounds__(64 * NW) void maf_forward_wg_kernel(pmc_maf_t m, const float* __restrict__ in,
                                                                  float* __restrict__ out,
                                                                  float* __restrict__ ladj_out,
@@ -52,8 +54,8 @@ __global__ __launch_bounds__(64 * NW) void maf_forward_wg_kernel(pmc_maf_t m, co
     float* Xn = Xc + Dp * 16;
     float* A = Xn + Dp * 16;
     float* B = A + Hp * 16;
-    float* C = B + Hp * 16;
-    float* RED = C + Hp * 16;                 // [16 * NW]
+    float* C = LEAN ? A : B + Hp * 16;
+    float* RED = (LEAN ? B : C) + Hp * 16;    // [16 * NW]
     float* P = RED + 16 * NW;                 // spline: [NOUT * 256]
     float* Y = P + (UNI ? NOUT * 256 : 0);    // MODE 1: the transform's input, by rank
     const int* feat_of_rank = m.meta + 8;
@@ -164,21 +166,30 @@ __global__ __launch_bounds__(64 * NW) void maf_forward_wg_kernel(pmc_maf_t m, co
     }
 }
 
-template <int NW, int UNI, int MODE>
-static int launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob, int64_t n,
-                             hipStream_t st, const int64_t* idx = nullptr) {
-    const size_t lds = pmc_lds_wg(m, NW, UNI ? PANEL_TILES(UNI) : 0, MODE);
-    if (lds > 160 * 1024) return pmc_fail("pmc_maf_forward: flow too wide for 160 KB of LDS");
+template <int NW, int UNI, int MODE, bool LEAN>
+static int launch_forward_wg_instance(const pmc_maf_t* m, size_t lds, const float* x, float* z, float* ladj, float* log_prob,
+                                      int64_t n, hipStream_t st, const int64_t* idx) {
     static size_t lds_set = 0;
     if (lds > 48 * 1024 && lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_forward_wg_kernel<NW, UNI, MODE>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_forward_wg_kernel<NW, UNI, MODE, LEAN>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_forward_wg_kernel)");
         lds_set = lds;
     }
-    hipLaunchKernelGGL((maf_forward_wg_kernel<NW, UNI, MODE>), dim3((unsigned)((n + 15) / 16)), dim3(64 * NW), lds, st,
+    hipLaunchKernelGGL((maf_forward_wg_kernel<NW, UNI, MODE, LEAN>), dim3((unsigned)((n + 15) / 16)), dim3(64 * NW), lds, st,
                        *m, x, z, ladj, log_prob, n, idx);
     return pmc_check_launch("maf_forward_wg_kernel");
+}
+
+// the full instance wherever it fits, the lean one otherwise (pmc_wg_instance, inverse_lds.h)
+template <int NW, int UNI, int MODE>
+static int launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob, int64_t n,
+                             hipStream_t st, const int64_t* idx = nullptr) {
+    int lean;
+    const size_t lds = pmc_wg_instance(m, NW, MODE, &lean);
+    if (!lds) return pmc_fail("pmc_maf_forward: flow too wide for 160 KB of LDS");
+    return lean ? launch_forward_wg_instance<NW, UNI, MODE, true>(m, lds, x, z, ladj, log_prob, n, st, idx)
+                : launch_forward_wg_instance<NW, UNI, MODE, false>(m, lds, x, z, ladj, log_prob, n, st, idx);
 }
 
 int pmc_launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* ladj, float* log_prob, int64_t n,
@@ -196,14 +207,20 @@ int pmc_launch_forward_wg(const pmc_maf_t* m, const float* x, float* z, float* l
                 : launch_forward_wg<4, 0, 0>(m, x, z, ladj, log_prob, n, st, idx);
 }
 
-// D-pass inverse through the same workgroup kernel (the only inverse of the spline flows until the
-// triangular sweep learns the spline; a cross-check for the affine flows)
+// D-pass inverse through the same workgroup kernel, the instance the plan names: PMC_SWEEP_DPASS_SPLINE the full one (the
+// spline flows' D-pass algorithm), PMC_SWEEP_DPASS_LEAN the lean one (affine and spline flows)
 int pmc_launch_inverse_dpass_wg(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
                                 float* x, float* ladj, int64_t n, hipStream_t st) {
-    if (plan->sweep != PMC_SWEEP_DPASS_SPLINE || pa || (size_t)plan->lds_bytes != pmc_lds_wg(m, 8, m->n_out == 2 ? 0 : m->n_out, 1))
+    const bool lean = plan->sweep == PMC_SWEEP_DPASS_LEAN;
+    const size_t lds = pmc_lds_wg(m, 8, pmc_wg_panel_tiles(m), 1, lean);
+    if ((!lean && plan->sweep != PMC_SWEEP_DPASS_SPLINE) || pa || lds > PMC_LDS_CAP || (size_t)plan->lds_bytes != lds)
         return pmc_fail("pmc_launch_inverse_dpass_wg: not this sweep's plan");
-    if (m->n_out == RQS_NOUT_OF(8)) return launch_forward_wg<8, 8, 1>(m, z, x, ladj, nullptr, n, st);
-    if (m->n_out == RQS_NOUT_OF(4)) return launch_forward_wg<8, 4, 1>(m, z, x, ladj, nullptr, n, st);
-    if (m->n_out == RQS_NOUT_OF(16)) return launch_forward_wg<8, 16, 1>(m, z, x, ladj, nullptr, n, st);
-    return launch_forward_wg<8, 0, 1>(m, z, x, ladj, nullptr, n, st);
+#define DPASS(K)                                                                                         \
+    return lean ? launch_forward_wg_instance<8, K, 1, true>(m, lds, z, x, ladj, nullptr, n, st, nullptr)  \
+                : launch_forward_wg_instance<8, K, 1, false>(m, lds, z, x, ladj, nullptr, n, st, nullptr);
+    if (m->n_out == RQS_NOUT_OF(8)) { DPASS(8) }
+    if (m->n_out == RQS_NOUT_OF(4)) { DPASS(4) }
+    if (m->n_out == RQS_NOUT_OF(16)) { DPASS(16) }
+    DPASS(0)
+#undef DPASS
 }

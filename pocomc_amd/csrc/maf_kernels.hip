@@ -204,7 +204,8 @@ int pmc_launch_inverse(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, co
         case PMC_SWEEP_LANE: return pmc_launch_tri6(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_NSF_DUO: return pmc_launch_nsf2(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_NSF_SOLO: return pmc_launch_inverse_tri_nsf(plan, pa, m, z, x, ladj, n, stream);
-        case PMC_SWEEP_DPASS_SPLINE: return pmc_launch_inverse_dpass_wg(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_DPASS_SPLINE:
+        case PMC_SWEEP_DPASS_LEAN: return pmc_launch_inverse_dpass_wg(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_DPASS_AFFINE: if (pa) break;
             if (int e = pmc_launch_lds(maf_dense_kernel<1>, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", dim3((unsigned)((n + 15) / 16)),
                                        dim3(64), (size_t)plan->lds_bytes, stream, *m, z, x, ladj, (float*)nullptr, n)) return e;

@@ -32,6 +32,12 @@
 //     E: x_t -> da2 -> da0      A: h0      B: h1      C: h2 -> da1
 //     P: (shift, raw) -> their gradients -> dx      G: dL/dy -> direct dL/dx term -> dL/dy of t-1
 // which keeps the 8-transform, H=512, D=128 flow (BASELINE config 5) inside 160 KB.
+//
+// LEAN instances (two hidden-width buffers; the flows whose four do not fit: pmc_train_instance): LDS holds only what an
+// MFMA reads as its B operand.  The forward half alternates  x -> U (h0) -> V (h1) -> U (h2)  and stores every activation
+// tile to the scratch as it is produced; the backward sweep keeps  da2 -> U,  da1 -> V,  da0 -> U  and takes the relu'
+// masks' operands (h2, h1, h0: element-wise, one tile per wave at a time) from the scratch, which is L2 resident.  x has a
+// buffer of its own (X: the spline instances' XB).  Every sum runs in the order of the full instances: the same bits.
 
 #include <string>
 #include "maf_common.h"
@@ -73,10 +79,12 @@ __device__ __forceinline__ TrainView train_view(const pmc_maf_t& m, const pmc_ma
 // hidden layers of one transform for the workgroup's 16 rows: X -> H0, H1, H2.  Like hidden_pass_wg (maf_wg.h), with the
 // tiles of the two triangular layers dealt by the host-built ownership table: tile cost ranks per wave, balanced over the
 // four SIMDs the waves share (the f32 matrix pipe of a SIMD is what bounds a layer).
-template <int NW, int PF, bool PROF>
+// LEAN: H2 is H0's buffer (h0 is dead once h1 is complete), and every tile also goes to G, the transform's block of the
+// activation scratch ([3][Hp * 16], the LDS layout), as it is produced.
+template <int NW, int PF, bool PROF, bool LEAN>
 __device__ __forceinline__ void hidden_pass_train(const pmc_maf_t& m, const MafView& w, const float* X, float* H0,
                                                   float* H1, float* H2, int wv, int lane, const int* own,
-                                                  long long* pacc, long long& tk) {
+                                                  long long* pacc, long long& tk, float* G) {
     const int q = lane >> 4, p = lane & 15;
     const int nT = m.nT, nXT = m.nXT;
     for (int T = wv; T < nT; T += NW) {
@@ -85,6 +93,7 @@ __device__ __forceinline__ void hidden_pass_train(const pmc_maf_t& m, const MafV
 #pragma unroll
         for (int r = 0; r < 4; ++r) a[r] = fmaxf(a[r], 0.0f);
         store_rows(H0, T, q, p, a);
+        if constexpr (LEAN) store_rows(G, T, q, p, a);
     }
     LAPT(15)
     lds_barrier();
@@ -104,6 +113,7 @@ __device__ __forceinline__ void hidden_pass_train(const pmc_maf_t& m, const MafV
 #pragma unroll
             for (int r2 = 0; r2 < 4; ++r2) a[r2] = fmaxf(a[r2] + h[r2], 0.0f);
             store_rows(Hout, T, q, p, a);
+            if constexpr (LEAN) store_rows(G + (size_t)layer * m.Hp * 16, T, q, p, a);
         }
         LAPT(13)
         lds_barrier();
@@ -136,7 +146,7 @@ __device__ __forceinline__ void rqs_panel_train(const pmc_maf_t& m, const MafVie
 
 // UNI 0: affine univariate (MAF), 2 outputs per feature.  UNI = K > 0: K-bin spline (NSF; K = 4, 8, 16), 3 K - 1 outputs.
 // One workgroup per row set of 16 (rows 16 (set0 + blockIdx.x) ..., scratch block blockIdx.x).
-template <int NW, int PF, bool PROF, int UNI>
+template <int NW, int PF, bool PROF, int UNI, bool LEAN>
 __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf_train_t tr,
                                                                   const float* __restrict__ x,
                                                                   const float* __restrict__ w,
@@ -155,16 +165,18 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
     const int D = m.D, Dp = m.Dp, Hp = m.Hp, T = m.T, nT = m.nT, nXT = m.nXT, nOT = m.nOT;
     const int Psz = UNI ? NOUT * 256 : 2 * Dp * 16;       // spline flows: one 16-rank panel at a time
     const int nOeff = UNI ? (NOUT * D + 15) / 16 : min(nOT, (D + 7) / 8);   // output tiles with real rows
-    float* A = smem;
-    float* B = A + Hp * 16;
-    float* Cb = B + Hp * 16;
-    float* E = Cb + Hp * 16;
-    float* P = E + Hp * 16;                   // [Psz]
+    float* A = smem;                          // LEAN: U -- h0, h2 | da2, da0
+    float* B = A + Hp * 16;                   // LEAN: V -- h1 | da1
+    float* Cb = LEAN ? A : B + Hp * 16;       // forward: h2
+    float* E = LEAN ? A : Cb + Hp * 16;
+    float* DA1 = LEAN ? B : Cb;               // backward: da1
+    float* P = (LEAN ? B : E) + Hp * 16;      // [Psz]
     float* Gb = P + Psz;                      // [Dp*16]
     float* CC = Gb + Dp * 16;                 // [16] per-row loss coefficient
     float* RED = CC + 16;                     // [16 * NW]
-    float* XB = RED + 16 * NW;       // UNI 1: [Dp*16] the transform's input during its backward sweep
-    float* PART = XB + (UNI ? Dp * 16 : 0);   // ksplit: [NW][256] partial tiles of the phases with fewer tiles than waves
+    float* XB = RED + 16 * NW;       // UNI 1, LEAN: [Dp*16] the transform's input (UNI 1: during its backward sweep)
+    float* PART = XB + ((UNI || LEAN) ? Dp * 16 : 0);   // ksplit: [NW][256] partial tiles of the phases with fewer tiles than waves
+    float* XT = LEAN ? XB : E;                // x: the forward sweep's first input; the affine backward sweep's x_t
     const int* feat_of_rank = m.meta + 8;
     // host-built tables (MAFSpec.train_tables): which hidden tiles a wave owns (by cost rank, balanced over the SIMDs),
     // and where a rank of transform t sits in transform t + 1 / t - 1
@@ -205,7 +217,7 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
             }
             CC[tid] = c;
         }
-        float* Xc = E;
+        float* Xc = XT;
         float* Xn = Gb;
         for (int e = tid; e < Dp * 16; e += (64 * NW)) {
             const int r = e >> 4, pp = e & 15;
@@ -225,8 +237,9 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
             const MafView wvw = maf_view(m, t);
             float* xtn = xt + (size_t)(t + 1) * Dp * 16;
             float* part = par + (size_t)t * tr.par_per_transform;
-            hidden_pass_train<NW, PF, PROF>(m, wvw, Xc, A, B, Cb, wv, lane, own, pacc, tk);
-            {                                                // A, B, Cb are contiguous in LDS: one copy
+            hidden_pass_train<NW, PF, PROF, LEAN>(m, wvw, Xc, A, B, Cb, wv, lane, own, pacc, tk,
+                                                  act + (size_t)t * 3 * Hp * 16);
+            if constexpr (!LEAN) {                           // A, B, Cb are contiguous in LDS: one copy
                 float4* dst = reinterpret_cast<float4*>(act + (size_t)t * 3 * Hp * 16);
                 for (int e = tid; e < 3 * Hp * 4; e += (64 * NW)) dst[e] = reinterpret_cast<const float4*>(A)[e];
             }
@@ -337,12 +350,16 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
             float* part = par + (size_t)t * tr.par_per_transform;
             float* dl = dlt + (size_t)t * 3 * Hp * 16;
             const float4* asrc = reinterpret_cast<const float4*>(act + (size_t)t * 3 * Hp * 16);
+            // the relu' masks' operands: h0, h1, h2 in LDS, or (LEAN) where the forward sweep stored them
+            const float* G0 = LEAN ? act + (size_t)t * 3 * Hp * 16 : A;
+            const float* G1 = LEAN ? G0 + Hp * 16 : B;
+            const float* G2 = LEAN ? G0 + 2 * Hp * 16 : Cb;
             if (UNI == 0) {
                 // x_t -> E, (h0, h1, h2) -> A, B, C, (shift, raw) -> P: everything the forward sweep kept
-                for (int e = tid; e < Dp * 4; e += (64 * NW)) reinterpret_cast<float4*>(E)[e] = xsrc[e];
+                for (int e = tid; e < Dp * 4; e += (64 * NW)) reinterpret_cast<float4*>(XT)[e] = xsrc[e];
                 for (int e = tid; e < nOeff * 64; e += (64 * NW))
                     reinterpret_cast<float4*>(P)[e] = reinterpret_cast<const float4*>(part)[e];
-                if (t < T - 1)                               // (the last transform's activations never left LDS)
+                if (!LEAN && t < T - 1)                      // (the last transform's activations never left LDS)
                     for (int e = tid; e < 3 * Hp * 4; e += (64 * NW)) reinterpret_cast<float4*>(A)[e] = asrc[e];
                 PHASE_END(4)
                 // element-wise part: y = x e^{ls} + shift,  L += -c * sum ls   (in place: P -> dP, G -> direct dx)
@@ -350,7 +367,7 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
                     const int r = e >> 4, pp = e & 15;
                     float gs = 0.0f, gr = 0.0f, gx = 0.0f;
                     if (r < D) {
-                        const float xv = E[lidx(r, pp)];
+                        const float xv = XT[lidx(r, pp)];
                         const float raw = P[lidx(2 * r + 1, pp)];
                         const float den = 1.0f + fabsf(raw / PMC_LOG_SLOPE);
                         const float el = expf(raw / den);
@@ -370,7 +387,7 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
                 for (int K = wv; K < nT; K += NW) {
                     f32x4 a = {0.f, 0.f, 0.f, 0.f};
                     a = mac_range<PF>(a, tv.f3T + (size_t)K * nOT * 64, P, 0, nOeff, lane);
-                    a = relu_gate(a, Cb, K, q, p);
+                    a = relu_gate(a, G2, K, q, p);
                     store_rows(E, K, q, p, a);
                     store_rows(dl + 2 * Hp * 16, K, q, p, a);
                 }
@@ -381,7 +398,7 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
                 for (int e = tid; e < Dp * 4; e += (64 * NW)) reinterpret_cast<float4*>(XB)[e] = xsrc[e];
                 for (int e = tid; e < Hp * 4; e += (64 * NW))
                     reinterpret_cast<float4*>(E)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (t < T - 1)
+                if (!LEAN && t < T - 1)
                     for (int e = tid; e < 3 * Hp * 4; e += (64 * NW)) reinterpret_cast<float4*>(A)[e] = asrc[e];
                 lds_barrier();
                 LAPT(4)
@@ -418,7 +435,7 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
                 }
                 // da2 = relu'(h2) . (W3^T dP)
                 for (int K = wv; K < nT; K += NW) {
-                    f32x4 a = relu_gate(rows_of(E, K, q, p), Cb, K, q, p);
+                    f32x4 a = relu_gate(rows_of(E, K, q, p), G2, K, q, p);
                     store_rows(E, K, q, p, a);
                     store_rows(dl + 2 * Hp * 16, K, q, p, a);
                 }
@@ -430,8 +447,8 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
                 if (Ti < 0) break;
                 f32x4 a = rows_of(E, Ti, q, p);
                 a = mac_range<PF>(a, tv.f2T + (size_t)Ti * nT * 64, E, (m.tri_ok ? Ti : 0), nT, lane);
-                a = relu_gate(a, B, Ti, q, p);
-                store_rows(Cb, Ti, q, p, a);
+                a = relu_gate(a, G1, Ti, q, p);
+                store_rows(DA1, Ti, q, p, a);
                 store_rows(dl + Hp * 16, Ti, q, p, a);
             }
             PHASE_END(7)
@@ -439,9 +456,9 @@ __global__ __launch_bounds__(64 * NW) void maf_chain_kernel(pmc_maf_t m, pmc_maf
             for (int it = 0; it < TRAIN_OWN_MAX; ++it) {
                 const int Ti = own[it];
                 if (Ti < 0) break;
-                f32x4 a = rows_of(Cb, Ti, q, p);
-                a = mac_range<PF>(a, tv.f1T + (size_t)Ti * nT * 64, Cb, (m.tri_ok ? Ti : 0), nT, lane);
-                a = relu_gate(a, A, Ti, q, p);
+                f32x4 a = rows_of(DA1, Ti, q, p);
+                a = mac_range<PF>(a, tv.f1T + (size_t)Ti * nT * 64, DA1, (m.tri_ok ? Ti : 0), nT, lane);
+                a = relu_gate(a, G0, Ti, q, p);
                 store_rows(E, Ti, q, p, a);
                 store_rows(dl, Ti, q, p, a);
             }
@@ -686,11 +703,27 @@ __global__ __launch_bounds__(256) void pack2_kernel(const float* __restrict__ fl
 }
 
 // ---------------------------------------------------------------------------
-static size_t train_lds_bytes(const pmc_maf_t& m, bool ksplit) {
+// lean: two hidden-width buffers, and the affine instances get the x buffer the spline ones have
+static size_t train_lds_bytes(const pmc_maf_t& m, bool ksplit, bool lean = false) {
     const size_t part = ksplit ? (size_t)TRAIN_WAVES * 256 : 0;
+    const int nh = lean ? 2 : 4;
     if (m.n_out != 2)
-        return (size_t)(4 * m.Hp * 16 + m.n_out * 256 + 2 * m.Dp * 16 + 16 + 16 * TRAIN_WAVES + part) * sizeof(float);
-    return (size_t)(4 * m.Hp * 16 + 2 * m.Dp * 16 + m.Dp * 16 + 16 + 16 * TRAIN_WAVES + part) * sizeof(float);   // (sized for 16 waves)
+        return (size_t)(nh * m.Hp * 16 + m.n_out * 256 + 2 * m.Dp * 16 + 16 + 16 * TRAIN_WAVES + part) * sizeof(float);
+    return (size_t)(nh * m.Hp * 16 + 2 * m.Dp * 16 + (lean ? 2 : 1) * m.Dp * 16 + 16 + 16 * TRAIN_WAVES + part) * sizeof(float);   // (sized for 16 waves)
+}
+
+// The full buffer plan wherever it fits (what every flow that trained before the lean instances existed keeps launching),
+// the lean one where only that fits or PMC_MAF_VARIANT_LEAN_LDS asks for it.  ksplit is decided by the full plan's size
+// as it always was (it is off above 64 KB).
+size_t pmc_train_instance(const pmc_maf_t* m, int* lean, int* ksplit, size_t* full_bytes) {
+    // partial-tile staging for the phases with fewer tiles than waves, where the workgroup's LDS has room for it
+    const bool ks = train_lds_bytes(*m, true) <= 64 * 1024;
+    const size_t full = train_lds_bytes(*m, ks);
+    *lean = (m->reserved & PMC_MAF_VARIANT_LEAN_LDS) || full > (size_t)160 * 1024;
+    if (ksplit) *ksplit = ks;
+    if (full_bytes) *full_bytes = full;
+    const size_t lds = *lean ? train_lds_bytes(*m, ks, true) : full;
+    return lds <= (size_t)160 * 1024 ? lds : 0;
 }
 
 static int train_check(const pmc_maf_t* m, const pmc_maf_train_t* tr, const char* who) {
@@ -705,28 +738,28 @@ static int train_check(const pmc_maf_t* m, const pmc_maf_train_t* tr, const char
 static int launch_lossgrad(const pmc_maf_t* m, const pmc_maf_train_t* tr, const float* x, const float* w,
                            const int64_t* idx, float wmul, float* grad, float* loss, int64_t n, hipStream_t st,
                            long long* prof = nullptr) {
-    // partial-tile staging for the phases with fewer tiles than waves, where the workgroup's LDS has room for it
-    const bool ksplit = train_lds_bytes(*m, true) <= 64 * 1024;
-    const size_t lds = train_lds_bytes(*m, ksplit);
-    if (lds > 160 * 1024) return pmc_fail("pmc_maf_loss_grad: flow too wide for the 160 KB LDS of one workgroup");
+    int lean, ksplit;
+    const size_t lds = pmc_train_instance(m, &lean, &ksplit, nullptr);
+    if (!lds) return pmc_fail("pmc_maf_loss_grad: flow too wide for the 160 KB LDS of one workgroup");
     const bool narrow = train_waves_of(*m) == TRAIN_WAVES_NARROW;
     const int64_t nsets = (n + 15) / 16;
     // a batch of more row sets than the scratch arrays hold comes in chunks: chain + weight gradients per chunk, the
     // later chunks adding to the gradient in place (the same order of additions whatever the rows are)
     for (int64_t set0 = 0; set0 < nsets; set0 += tr->max_sets) {
         const int n_wg = (int)(nsets - set0 < tr->max_sets ? nsets - set0 : tr->max_sets);
-#define LG(NWV, PFV, PR, UN)                                                                                       \
+#define LGI(NWV, PFV, PR, UN, LN)                                                                                  \
     {                                                                                                              \
         static size_t lds_set = 0;                                                                                 \
         if (lds > 48 * 1024 && lds > lds_set) {                                                                    \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_chain_kernel<NWV, PFV, PR, UN>), \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(maf_chain_kernel<NWV, PFV, PR, UN, LN>), \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
             if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(maf_chain_kernel)");                  \
             lds_set = lds;                                                                                         \
         }                                                                                                          \
-        hipLaunchKernelGGL((maf_chain_kernel<NWV, PFV, PR, UN>), dim3((unsigned)n_wg), dim3(64 * NWV), lds, st, *m, *tr, \
+        hipLaunchKernelGGL((maf_chain_kernel<NWV, PFV, PR, UN, LN>), dim3((unsigned)n_wg), dim3(64 * NWV), lds, st, *m, *tr, \
                            x, w, idx, wmul, n, set0, ksplit ? 1 : 0, prof);                                        \
     }
+#define LG(NWV, PFV, PR, UN) { if (lean) LGI(NWV, PFV, PR, UN, true) else LGI(NWV, PFV, PR, UN, false) }
 #define LGK(PR, K)                                                                                                 \
     if (m->n_out == RQS_NOUT_OF(K)) {                                                                              \
         if (narrow) LG(TRAIN_WAVES_NARROW, TRAIN_PF_NARROW, PR, K) else LG(TRAIN_WAVES, TRAIN_PF, PR, K)           \
@@ -739,6 +772,7 @@ static int launch_lossgrad(const pmc_maf_t* m, const pmc_maf_train_t* tr, const 
         { LGK(false, 8) LGK(false, 4) LGK(false, 16) LG(TRAIN_WAVES, TRAIN_PF, false, 0) }
 #undef LGK
 #undef LG
+#undef LGI
         hipLaunchKernelGGL(maf_dw_kernel, dim3((unsigned)tr->n_jobs), dim3(64 * DW_WAVES), 0, st, *m, *tr, n_wg,
                            set0 > 0 ? 1 : 0, grad, loss);
     }

@@ -25,6 +25,7 @@ from . import _lib
 from .maf_spec import MAFSpec, SPEC_BY_NAME, NSF_BY_NAME, spec_by_name, bf16_forward_refusal
 
 PMC_MAF_TABLES = 4             # pmc_maf_t.reserved: the metadata carries the two-wave affine sweep's table image
+PMC_MAF_VARIANT_LEAN_LDS = 8   # pmc_maf_t.reserved: the two-array instances also where the full ones fit (Flow.lean_lds)
 
 
 def torch_double_to_float(x: torch.Tensor, warn: bool = True) -> torch.Tensor:
@@ -104,7 +105,7 @@ class Flow:
             D=spec.n_dim, H=spec.hidden, T=spec.n_transforms, Hp=spec.Hp, Dp=spec.Dp,
             nT=spec.nT, nXT=spec.nXT, nOT=spec.nOT, pk_per_transform=spec.pk_per_transform,
             tri_ok=int(spec.tri_ok), n_out=spec.n_out,
-            reserved=PMC_MAF_TABLES if spec.has_sweep_tables else 0)
+            reserved=(PMC_MAF_TABLES if spec.has_sweep_tables else 0) | (PMC_MAF_VARIANT_LEAN_LDS if spec.lean_lds else 0))
         self.inverse_algo = 0          # PMC_INVERSE_AUTO
         if precision not in ("f32", "bf16"):
             raise ValueError("precision must be 'f32' or 'bf16'")
@@ -158,6 +159,26 @@ class Flow:
             self.inverse_guard = st.get("inverse_guard_result")
             self._desc.lane16 = None if st["inverse_fell_back"] else self._lane16.data_ptr()
         self.inverse_algo = st.get("inverse_algo", 0)
+
+    # ------------------------------------------------------------ LDS plan
+    @property
+    def lean_lds(self):
+        """The float32 kernels' two-array instances (``csrc/maf_forward_wg.hip``, ``csrc/maf_train.hip``) are forced on this
+        flow although the full ones fit (``PMC_MAF_VARIANT_LEAN_LDS``; also ``MAFSpec.lean_lds``).  The wide default flows
+        (``n_dim`` >= 86) take them by themselves; this switch exists so that tests reach them with small flows."""
+        return bool(self._desc.reserved & PMC_MAF_VARIANT_LEAN_LDS)
+
+    @lean_lds.setter
+    def lean_lds(self, on):
+        self._desc.reserved = (self._desc.reserved & ~PMC_MAF_VARIANT_LEAN_LDS) | (PMC_MAF_VARIANT_LEAN_LDS if on else 0)
+
+    def lds_plan(self):
+        """Which instance ``forward`` / ``log_prob``, the D-pass inverse and ``fit`` take for this flow
+        (``pmc_maf_lds_plan``): ``{"forward": ("full" | "lean", LDS bytes), "dpass": ..., "train": ...}``."""
+        p = _lib.pmc_flow_lds_plan_t()
+        _lib.check(self.lib.pmc_maf_lds_plan(C.byref(self._desc), C.byref(p)), "pmc_maf_lds_plan")
+        return {k: ("lean" if getattr(p, k + "_lean") else "full", int(getattr(p, k + "_lds_bytes")))
+                for k in ("forward", "dpass", "train")}
 
     # ------------------------------------------------------------ parameters
     def repack(self):

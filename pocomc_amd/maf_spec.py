@@ -65,6 +65,9 @@ class MAFSpec:
 
     # filled by __post_init__
     orders: list = field(default_factory=list, repr=False)
+    # test switch (pmc_maf_t.reserved & PMC_MAF_VARIANT_LEAN_LDS): the float32 kernels' two-array instances also where the
+    # full ones fit; the wide default flows take them by themselves
+    lean_lds: bool = field(default=False, repr=False, compare=False)
 
     def __post_init__(self):
         D = int(self.n_dim)
