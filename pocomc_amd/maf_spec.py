@@ -32,6 +32,7 @@ Canonical parameter layout (one flat fp32 vector, transform after transform):
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -51,6 +52,65 @@ def default_hidden(n_dim: int) -> int:
 
 def _ceil_to(x: int, m: int) -> int:
     return (x + m - 1) // m * m
+
+
+# ---------------------------------------------------------------------------------------------------- images and their parts
+# A device image is a gather map into the canonical parameter vector.  Every image is cut from the connection matrices of
+# MAFSpec.connections (canonical index, or -1: masked, padding slot, rank beyond D) by the helpers below and by nothing else.
+_Layout = namedtuple("_Layout", "shapes sizes offsets total")
+
+
+def _layout(parts):
+    """Ordered ``(name, shape)`` list of one transform's parts -> their shapes, sizes, offsets and the total, in elements."""
+    shapes = {name: tuple(int(d) for d in shape) for name, shape in parts}
+    sizes = {name: math.prod(shape) for name, shape in shapes.items()}
+    offsets, total = {}, 0
+    for name, sz in sizes.items():
+        offsets[name] = total
+        total += sz
+    return _Layout(shapes, sizes, offsets, total)
+
+
+def _fill(image, base, layout, parts):
+    """Write the arrays ``parts`` (name -> array of the part's shape) into ``image`` from element ``base`` on."""
+    for name, a in parts.items():
+        o = base + layout.offsets[name]
+        image[o:o + layout.sizes[name]].reshape(layout.shapes[name])[...] = a
+
+
+def _pad(a, shape):
+    """``a`` in the leading corner of an array of ``shape``, -1 elsewhere."""
+    out = np.full(shape, -1, dtype=a.dtype)
+    out[tuple(slice(n) for n in a.shape)] = a
+    return out
+
+
+def _frag_a4(w):
+    """A operands of ``mfma_f32_16x16x4f32`` of ``w [rows][k]``: ``[row tile][k tile][lane = 16 k + i][c]`` holds
+    ``w[16 row tile + i][16 k tile + 4 c + k]``."""
+    R, K = w.shape[0] // 16, w.shape[1] // 16
+    return w.reshape(R, 16, K, 4, 4).transpose(0, 2, 4, 1, 3).reshape(R, K, 64, 4)
+
+
+def _frag_a32(w):
+    """A operands of ``v_mfma_f32_16x16x32_bf16`` of ``w [rows][k]``, k padded to 32-wide tiles:
+    ``[row tile][k tile][lane = 16 g + i][e]`` holds ``w[16 row tile + i][32 k tile + 8 g + e]``."""
+    R, K = w.shape[0] // 16, -(-w.shape[1] // 32)
+    return _pad(w, (16 * R, 32 * K)).reshape(R, 16, K, 4, 8).transpose(0, 2, 3, 1, 4).reshape(R, K, 64, 8)
+
+
+def _frag_c(w):
+    """MFMA C layout of the 16 x 16 tiles of ``w [rows][cols]``: ``[row tile][col tile][lane = 16 q + j][r]`` holds
+    ``w[16 row tile + 4 q + r][16 col tile + j]``."""
+    R, K = w.shape[0] // 16, w.shape[1] // 16
+    return w.reshape(R, 4, 4, K, 16).transpose(0, 3, 1, 4, 2).reshape(R, K, 64, 4)
+
+
+def _frag_chain(blocks):
+    """A operands of ``v_mfma_f32_4x4x1_16b_f32`` of the per-tile ``blocks [tile][4 n rows][16 k slots]``:
+    ``[tile][lane = 4 k + i][a]`` holds ``blocks[tile][4 a + i][k]`` (one VGPR = a 4 x 16 block)."""
+    nT, n = blocks.shape[0], blocks.shape[1] // 4
+    return blocks.reshape(nT, n, 4, 16).transpose(0, 3, 2, 1).reshape(nT, 64, n)
 
 
 @dataclass
@@ -93,7 +153,6 @@ class MAFSpec:
             raise NotImplementedError("spline flows are built for bins in (4, 8, 16)")
         # hyper-network outputs per feature: (shift, raw log-scale) or (K widths, K heights, K-1 derivatives)
         self.n_out = 2 if self.univariate == "affine" else 3 * int(self.bins) - 1
-        NO = self.n_out
         # rank of every input feature, per transform (zuko MAF: orders[i % 2])
         ident = np.arange(D)
         self.orders = [ident.copy() if t % 2 == 0 else ident[::-1].copy()
@@ -101,15 +160,9 @@ class MAFSpec:
         # degree of every hidden unit (same for the three hidden layers)
         self.degree = 1 + (np.arange(H) % (D - 1))
         # canonical offsets inside one transform
-        sizes = [("W0", H * D), ("b0", H), ("W1", H * H), ("b1", H),
-                 ("W2", H * H), ("b2", H), ("W3", NO * D * H), ("b3", NO * D)]
-        off = 0
-        self.offsets = {}
-        for name, sz in sizes:
-            self.offsets[name] = (off, sz)
-            off += sz
-        self.params_per_transform = off
-        self.n_params = off * self.n_transforms
+        _, sizes, off, self.params_per_transform = _layout(self.shapes().items())
+        self.offsets = {name: (off[name], sizes[name]) for name in sizes}
+        self.n_params = self.params_per_transform * self.n_transforms
         self._build_device_layout()
 
     # ------------------------------------------------------------------ masks
@@ -215,25 +268,22 @@ class MAFSpec:
         # quad meta word: degree | last << 16
         self.quad_meta = (qdeg.astype(np.int32) | (qlast << 16)).astype(np.int32)
 
-        # ---- sizes of the packed arrays (floats), per transform
-        nT, nXT, nOT = self.nT, self.nXT, self.nOT
-        self.sz_f0 = nT * nXT * 256              # W0 fragments  [tile][xtile][lane][4]
-        self.sz_f12 = nT * nT * 256              # W1/W2 fragments [tile][ktile][lane][4]
-        self.sz_f3 = nOT * nT * 256              # W3 fragments  [otile][ktile][lane][4]
-        self.sz_w0n = self.Dp * Hp               # W0 natural    [rank][slot]
-        self.sz_b = Hp                           # b0,b1,b2      [slot]
-        self.sz_b3 = self.Op                     # b3            [2*rank + {0,1}]
-        parts = [("f0", self.sz_f0), ("f1", self.sz_f12), ("f2", self.sz_f12),
-                 ("f3", self.sz_f3), ("w0n", self.sz_w0n), ("b0", self.sz_b),
-                 ("b1", self.sz_b), ("b2", self.sz_b), ("b3", self.sz_b3)]
+        # ---- the parts of the packed image (floats), per transform
+        D, Hp, Dp, nT, nXT, nOT = self.n_dim, self.Hp, self.Dp, self.nT, self.nXT, self.nOT
+        parts = [("f0", (nT, nXT, 64, 4)),       # W0 fragments  [tile][xtile][lane][4]
+                 ("f1", (nT, nT, 64, 4)),        # W1/W2 fragments [tile][ktile][lane][4]
+                 ("f2", (nT, nT, 64, 4)),
+                 ("f3", (nOT, nT, 64, 4)),       # W3 fragments  [otile][ktile][lane][4]
+                 ("w0n", (Dp, Hp)),              # W0 natural    [rank][slot]
+                 ("b0", (Hp,)), ("b1", (Hp,)), ("b2", (Hp,)),    # b0,b1,b2 [slot]
+                 ("b3", (self.Op,))]             # b3            [n_out*rank + s]
         if self.univariate == "rqs" and self.bins == 8:
             # inverse sweep: the 23 output rows of every rank padded to two 16-row tiles of their own
-            self.sz_f3i = D * 2 * nT * 256       # [rank][half][ktile][lane][4]
-            self.sz_b3i = D * 32                 # [rank][32]
-            parts += [("f3i", self.sz_f3i), ("b3i", self.sz_b3i)]
+            parts += [("f3i", (D, 2, nT, 64, 4)),     # [rank][half][ktile][lane][4]
+                      ("b3i", (D, 32))]               # [rank][32]
             # the two-wave spline sweep (csrc/maf_inverse_nsf2.hip) shares the affine two-wave sweep's hidden part: the
             # layer-0 window columns (cw0), the masked layer-0 fragments (f0c), the transposed biases -- see below
-            parts += [("cw0", nT * 256), ("f0c", self.sz_f0), ("b0t", Hp), ("b1t", Hp), ("b2t", Hp)]
+            parts += [("cw0", (nT, 64, 4)), ("f0c", (nT, nXT, 64, 4)), ("b0t", (Hp,)), ("b1t", (Hp,)), ("b2t", (Hp,))]
         elif self.univariate == "affine":
             # chain image of the lane-per-walker inverse sweep (csrc/maf_inverse_tri6.hip): A operands of
             # v_mfma_f32_4x4x1_16b_f32 -- lane l holds W[out quad row l & 3][k slot l >> 2], one VGPR = a 4 x 16 block --
@@ -241,19 +291,55 @@ class MAFSpec:
             # ranks the previous and the own tile produce (cw0: k slots 0-3 / 4-7) and the output rows of the own
             # tile's ranks (cw3: [tile][lane][pair of groups]); f0c = f0 with the columns of those ranks zeroed (what
             # the helper wavefront multiplies while the chain adds the newest ranks from registers)
-            parts += [("cw1", nT * 256), ("cw2", nT * 256), ("cw0", nT * 256), ("cw3", nT * 128),
-                      ("f0c", self.sz_f0)]
+            parts += [("cw1", (nT, 64, 4)), ("cw2", (nT, 64, 4)), ("cw0", (nT, 64, 4)), ("cw3", (nT, 64, 2)),
+                      ("f0c", (nT, nXT, 64, 4))]
             # the hidden layers' biases with the rows of every tile transposed (slot 16 T + 4 q + r holds the bias of unit
             # 16 T + 4 r + q): what a lane of the two-wave sweep's transposed accumulators (csrc/maf_chain_rot.h) starts
             # from, one 16-byte load per tile
-            parts += [("b0t", Hp), ("b1t", Hp), ("b2t", Hp)]
-        off = 0
-        self.pk_offsets = {}
-        for name, sz in parts:
-            self.pk_offsets[name] = off
-            off += sz
-        self.pk_per_transform = off
-        self.pk_size = off * self.n_transforms
+            parts += [("b0t", (Hp,)), ("b1t", (Hp,)), ("b2t", (Hp,))]
+        self.pk_shapes, sizes, self.pk_offsets, self.pk_per_transform = _layout(parts)
+        self.pk_size = self.pk_per_transform * self.n_transforms
+        for attr, name in (("f0", "f0"), ("f12", "f1"), ("f3", "f3"), ("w0n", "w0n"), ("b", "b0"), ("b3", "b3"),
+                           ("f3i", "f3i"), ("b3i", "b3i")):
+            if name in sizes:
+                setattr(self, "sz_" + attr, sizes[name])
+
+    def packed_view(self, image: np.ndarray, t: int, name: str) -> np.ndarray:
+        """View of one part of transform t inside a packed image (or its gather map), in the part's shape
+        (``pk_shapes``): the sibling of :meth:`view` for the canonical vector."""
+        base = t * self.pk_per_transform + self.pk_offsets[name]
+        shape = self.pk_shapes[name]
+        return image[base:base + math.prod(shape)].reshape(shape)
+
+    # ------------------------------------------------------------- connections
+    def connections(self, by_rank: bool = True, tile: int = 16):
+        """Per transform, in turn, its index matrices in device coordinates: name -> canonical flat index of every entry of
+        ``W0 [Hp][Dp]  W1, W2 [Hp][Hp]  W3 [Op][Hp]  b0, b1, b2 [Hp]  b3 [Op]``, or -1 where the connection is masked, the
+        slot is padding or the rank is beyond ``D``.  Hidden units are addressed by slot, features by rank and output
+        rows are ``n_out * rank + s``; with ``by_rank=False`` features and output rows are in canonical order (the
+        row-major training image).  ``tile``: slots and features are padded to a multiple of it (16: ``Hp`` and ``Dp``).
+
+        Every device image is a re-tiling of these matrices: this is the one place that reads a mask or meets a padding
+        slot or a rank beyond ``D``; the canonical index of an entry is its position in :meth:`view`."""
+        D, NO = self.n_dim, self.n_out
+        su = _pad(self.slot_unit, (_ceil_to(self.Hp, tile),))            # canonical unit of every slot, -1 = padding
+        canonical, absent = np.arange(self.n_params, dtype=np.int32), np.full(1, -1, dtype=np.int32)
+        for t in range(self.n_transforms):
+            feat = _pad(np.argsort(self.orders[t]) if by_rank else np.arange(D), (_ceil_to(D, tile),))     # -1 beyond D
+            orow = np.where(feat[:, None] >= 0, NO * feat[:, None] + np.arange(NO), -1).reshape(-1)
+            M0, M1, M2, M3 = self.masks(t)
+            out = {}
+            for name, mask, rows, cols in (("W0", M0, su, feat), ("W1", M1, su, su), ("W2", M2, su, su), ("W3", M3, orow, su)):
+                # the canonical tensor's own indices where unmasked, behind them one more row and column of -1: what an
+                # index of -1 reads
+                v = self.view(canonical, t, name)
+                c = np.full((v.shape[0] + 1, v.shape[1] + 1), -1, dtype=np.int32)
+                np.copyto(c[:-1, :-1], v, where=mask)
+                out[name] = c.take(rows, axis=0).take(cols, axis=1)
+                # its bias: one per row
+                b = self.view(canonical, t, "b" + name[1])
+                out["b" + name[1]] = np.concatenate((b, absent)).take(rows)
+            yield out
 
     def pack_index(self) -> np.ndarray:
         """int32 gather map: ``packed[i] = flat[idx[i]] if idx[i] >= 0 else 0``.
@@ -261,136 +347,53 @@ class MAFSpec:
         Masked-out weights map to -1 (exact zeros in the packed image), so the
         kernels never need the masks.
         """
-        D, H, Hp, Dp = self.n_dim, self.hidden, self.Hp, self.Dp
-        nT, nXT, nOT = self.nT, self.nXT, self.nOT
-        idx = np.full(self.pk_size, -1, dtype=np.int64)
-        lane = np.arange(64)
-        lk, li = lane >> 4, lane & 15            # k within quad, row within tile
-        for t in range(self.n_transforms):
-            base_c = t * self.params_per_transform
-            base_p = t * self.pk_per_transform
-            rank = self.orders[t]
-            feat_of_rank = np.argsort(rank)
-            M0, M1, M2, M3 = self.masks(t)
-            su = self.slot_unit
-
-            def cidx(name, row, col, ncol, mask):
-                """canonical flat index of weight[row, col] or -1."""
-                off, _ = self.offsets[name]
-                ok = (row >= 0) & (col >= 0)
-                r = np.where(ok, row, 0)
-                c = np.where(ok, col, 0)
-                ok = ok & mask[r, c]
-                return np.where(ok, base_c + off + r * ncol + c, -1)
-
-            # --- W0 fragments: A[i][k] = W0[out slot 16*T+i][in rank 16*X + 4c + k]
-            f0 = np.full((nT, nXT, 64, 4), -1, dtype=np.int64)
+        D, NO, Hp, Dp, nT = self.n_dim, self.n_out, self.Hp, self.Dp, self.nT
+        idx = np.full(self.pk_size, -1, dtype=np.int32)
+        sweeps = "cw0" in self.pk_shapes                 # the sweeps' images (cw1 / cw2 / cw3: the affine one only)
+        if sweeps:
+            # per tile: the rank of every k slot of the layer-0 window (-1: none), the ranks its own groups produce and
+            # the first rank the chain adds itself
+            tg = self.tile_groups()                      # per tile: degrees of its groups (in order)
+            win = np.full((nT, 16), -1, dtype=np.int64)
+            own = np.full((nT, 4), -1, dtype=np.int64)
+            cut = np.zeros(nT, dtype=np.int64)
             for T in range(nT):
-                out_unit = su[16 * T + li]                       # (64,)
-                for X in range(nXT):
-                    for c in range(4):
-                        r_in = 16 * X + 4 * c + lk
-                        feat = np.where(r_in < D, feat_of_rank[np.minimum(r_in, D - 1)], -1)
-                        f0[T, X, :, c] = cidx("W0", out_unit, feat, D, M0)
-            # --- W1/W2 fragments: A[i][k] = W[out slot 16*T+i][in slot 16*K + 4c + k]
-            f12 = {}
-            for name, M in (("W1", M1), ("W2", M2)):
-                f = np.full((nT, nT, 64, 4), -1, dtype=np.int64)
-                for T in range(nT):
-                    out_unit = su[16 * T + li]
-                    for K in range(nT):
-                        for c in range(4):
-                            in_unit = su[16 * K + 4 * c + lk]
-                            f[T, K, :, c] = cidx(name, out_unit, in_unit, H, M)
-                f12[name] = f
-            # --- W3 fragments: A[i][k] = W3[out row of (rank, s)][in slot]
-            f3 = np.full((nOT, nT, 64, 4), -1, dtype=np.int64)
-            for O in range(nOT):
-                orow = 16 * O + li                               # packed out row
-                r_out = orow // self.n_out
-                s = orow % self.n_out
-                crow = np.where(r_out < D, self.n_out * feat_of_rank[np.minimum(r_out, D - 1)] + s, -1)
-                for K in range(nT):
-                    for c in range(4):
-                        in_unit = su[16 * K + 4 * c + lk]
-                        f3[O, K, :, c] = cidx("W3", crow, in_unit, H, M3)
-            # --- W0 natural [rank][slot]
-            w0n = np.full((Dp, Hp), -1, dtype=np.int64)
-            for r in range(D):
-                feat = np.full(Hp, feat_of_rank[r])
-                w0n[r] = cidx("W0", su, feat, D, M0)
-
-            def bidx(name):
-                off, _ = self.offsets[name]
-                return np.where(su >= 0, base_c + off + np.maximum(su, 0), -1)
-
-            b3 = np.full(self.Op, -1, dtype=np.int64)
-            off3, _ = self.offsets["b3"]
-            for r in range(D):
-                for j in range(self.n_out):
-                    b3[self.n_out * r + j] = base_c + off3 + self.n_out * feat_of_rank[r] + j
-
-            po = self.pk_offsets
-            def put(name, arr):
-                a = arr.reshape(-1)
-                idx[base_p + po[name]: base_p + po[name] + a.size] = a
-            put("f0", f0); put("f1", f12["W1"]); put("f2", f12["W2"]); put("f3", f3)
-            put("w0n", w0n); put("b0", bidx("b0")); put("b1", bidx("b1")); put("b2", bidx("b2"))
-            put("b3", b3)
-            if self.univariate == "affine" or self.bins == 8:   # the sweeps' images (cw1 / cw2 / cw3: the affine one only)
-                affine = self.univariate == "affine"
-                ci, ck = lane & 3, lane >> 2                # 4x4x1 A operand: row within the out quad, k slot
-                tg = self.tile_groups()                      # per tile: degrees of its groups (in order)
-                cw1 = np.full((nT, 64, 4), -1, dtype=np.int64)
-                cw2 = np.full((nT, 64, 4), -1, dtype=np.int64)
-                cw0 = np.full((nT, 64, 4), -1, dtype=np.int64)
-                cw3 = np.full((nT, 64, 2), -1, dtype=np.int64)
-                f0c = np.full((nT, nXT, 64, 4), -1, dtype=np.int64)
-                for T in range(nT):
-                    in_unit = su[16 * T + ck]
-                    prev = [0] if T == 0 else tg[T - 1]      # ranks produced before this tile's chain starts its own
-                    own = tg[T]
-                    win = np.full(16, -1, dtype=np.int64)    # rank of every k slot of the layer-0 window
-                    win[:len(prev)] = prev
-                    win[4:4 + len(own)] = own
-                    wfeat = np.where(win >= 0, feat_of_rank[np.clip(win, 0, D - 1)], -1)
-                    for a in range(4):
-                        out_unit = su[16 * T + 4 * a + ci]
-                        cw1[T, :, a] = cidx("W1", out_unit, in_unit, H, M1)
-                        cw2[T, :, a] = cidx("W2", out_unit, in_unit, H, M2)
-                        cw0[T, :, a] = cidx("W0", out_unit, wfeat[ck], D, M0)
-                    for sl in range(2):
-                        gi = 2 * sl + (ci >> 1)              # group of the tile this row belongs to
-                        rk = np.array([own[g] if g < len(own) else -1 for g in gi])
-                        crow = np.where(rk >= 0, self.n_out * feat_of_rank[np.clip(rk, 0, D - 1)] + (ci & 1), -1)
-                        cw3[T, :, sl] = cidx("W3", crow, in_unit, H, M3)
-                    cut = 0 if T == 0 else (prev[0] if len(prev) else D)   # first rank the chain adds itself
-                    for X in range(nXT):
-                        for c in range(4):
-                            r_in = 16 * X + 4 * c + lk
-                            f0c[T, X, :, c] = np.where(r_in < cut, f0[T, X, :, c], -1)
-                if affine:
-                    put("cw1", cw1); put("cw2", cw2); put("cw3", cw3)
-                put("cw0", cw0); put("f0c", f0c)
-                tr = (np.arange(Hp) & ~15) + 4 * (np.arange(Hp) & 3) + ((np.arange(Hp) >> 2) & 3)
-                for name in ("b0", "b1", "b2"):
-                    put(name + "t", bidx(name)[tr])
-            if self.univariate == "rqs" and self.bins == 8:
-                NO = self.n_out
-                f3i = np.full((D, 2, nT, 64, 4), -1, dtype=np.int64)
-                b3i = np.full((D, 32), -1, dtype=np.int64)
-                for r in range(D):
-                    feat = feat_of_rank[r]
-                    for half in range(2):
-                        j = 16 * half + li                           # output j of this rank held by row li
-                        crow = np.where(j < NO, NO * feat + np.minimum(j, NO - 1), -1)
-                        for K in range(nT):
-                            for c in range(4):
-                                in_unit = su[16 * K + 4 * c + lk]
-                                f3i[r, half, K, :, c] = cidx("W3", crow, in_unit, H, M3)
-                    b3i[r, :NO] = base_c + off3 + NO * feat + np.arange(NO)
-                put("f3i", f3i); put("b3i", b3i)
-        return idx.astype(np.int32)
+                prev = [0] if T == 0 else tg[T - 1]      # ranks produced before this tile's chain starts its own
+                win[T, :len(prev)] = prev
+                own[T, :len(tg[T])] = tg[T]
+                cut[T] = 0 if T == 0 else (prev[0] if prev else D)
+            win[:, 4:8] = own
+            before_cut = np.arange(Dp) < np.repeat(cut, 16)[:, None]     # [slot][rank]
+            tiles = np.arange(nT)
+            diagonal = lambda w: w.reshape(nT, 16, nT, 16)[tiles, :, tiles, :]      # [tile][out slot][in slot] of the tiles (T, T)
+        for t, c in enumerate(self.connections()):
+            W0, W1, W2, W3 = c["W0"], c["W1"], c["W2"], c["W3"]
+            # --- fragments: A[i][k] = W[out slot (row of (rank, s)) 16*T+i][in rank (slot) 16*K + 4c + k]
+            img = {"f0": _frag_a4(W0), "f1": _frag_a4(W1), "f2": _frag_a4(W2), "f3": _frag_a4(W3), "w0n": W0.T,
+                   "b0": c["b0"], "b1": c["b1"], "b2": c["b2"], "b3": c["b3"]}
+            if sweeps:
+                # layer 0: the window's columns as the chain's operand (column Dp: a k slot without a rank), and the
+                # fragments without the columns at and above the tile's cut
+                W0w = _pad(W0, (Hp, Dp + 1)).reshape(nT, 16, Dp + 1)
+                img["cw0"] = _frag_chain(np.take_along_axis(W0w, win[:, None, :], axis=2))
+                img["f0c"] = _frag_a4(np.where(before_cut, W0, -1))
+                for b in ("b0", "b1", "b2"):
+                    img[b + "t"] = c[b].reshape(nT, 4, 4).transpose(0, 2, 1).reshape(Hp)
+            if "cw1" in self.pk_shapes:
+                # the chain's diagonal tiles of the hidden layers, and the rows (rank, s) of the own tile's ranks against
+                # the own tile's slots (rank Dp: a group the tile does not have)
+                W3r = _pad(W3.reshape(Dp, NO, nT, 16), (Dp + 1, NO, nT, 16))
+                img["cw1"], img["cw2"] = _frag_chain(diagonal(W1)), _frag_chain(diagonal(W2))
+                img["cw3"] = _frag_chain(W3r[own, :, tiles[:, None], :].reshape(nT, 4 * NO, 16))
+            if "f3i" in self.pk_shapes:
+                # the NO output rows of every rank at the head of 32 rows of their own
+                W3i = _pad(W3[:NO * D].reshape(D, NO, Hp), (D, 32, Hp))
+                img["f3i"] = _frag_a4(W3i.reshape(32 * D, Hp)).reshape(D, 2, nT, 64, 4)
+                img["b3i"] = _pad(c["b3"][:NO * D].reshape(D, NO), (D, 32))
+            assert img.keys() == self.pk_shapes.keys()
+            for name, a in img.items():
+                self.packed_view(idx, t, name)[...] = a
+        return idx
 
     def tile_groups(self):
         """Per hidden tile: the degrees (= the ranks they produce) of its degree groups, in slot order."""
@@ -497,68 +500,21 @@ class MAFSpec:
         16-row out tile and the 8 consecutive k ``8 (l >> 4) .. + 7`` of a 32-wide k tile --
         ``g0 [nT][nX2]``, ``g1 / g2 [nT][nK2]``, ``g3 [nOT][nK2]``, each ``[64 lanes][8]``; biases stay float32 (they are
         read from the float32 image)."""
+        nX2, nK2, (_, sz, off, total) = self._bf16_parts()
+        return dict(nX2=nX2, nK2=nK2, sz=sz, off=off, per_transform=total)
+
+    def _bf16_parts(self):
         nX2, nK2 = -(-self.Dp // 32), -(-self.Hp // 32)
-        sz = {"g0": self.nT * nX2 * 512, "g1": self.nT * nK2 * 512, "g2": self.nT * nK2 * 512, "g3": self.nOT * nK2 * 512}
-        off, o = {}, 0
-        for k, v in sz.items():
-            off[k] = o
-            o += v
-        return dict(nX2=nX2, nK2=nK2, sz=sz, off=off, per_transform=o)
+        return nX2, nK2, _layout([("g0", (self.nT, nX2, 64, 8)), ("g1", (self.nT, nK2, 64, 8)),
+                                  ("g2", (self.nT, nK2, 64, 8)), ("g3", (self.nOT, nK2, 64, 8))])
 
     def pack_index_bf16(self) -> np.ndarray:
         """int32 gather map of the bf16 fragment image: ``image[i] = bf16(flat[idx[i]]) if idx[i] >= 0 else 0``."""
-        D, H = self.n_dim, self.hidden
-        L = self.bf16_layout()
-        nX2, nK2, nT, nOT = L["nX2"], L["nK2"], self.nT, self.nOT
-        idx = np.full(L["per_transform"] * self.n_transforms, -1, dtype=np.int64)
-        lane = np.arange(64)
-        li, lg = lane & 15, lane >> 4
-        su = self.slot_unit
-        for t in range(self.n_transforms):
-            base_c = t * self.params_per_transform
-            rank = self.orders[t]
-            feat_of_rank = np.argsort(rank)
-            M0, M1, M2, M3 = self.masks(t)
-
-            def cidx(name, row, col, ncol, mask):
-                off, _ = self.offsets[name]
-                ok = (row >= 0) & (col >= 0)
-                r = np.where(ok, row, 0)
-                c = np.where(ok, col, 0)
-                ok = ok & mask[r, c]
-                return np.where(ok, base_c + off + r * ncol + c, -1)
-
-            def in_slot(k):                       # canonical hidden unit of packed slot k (or -1)
-                return np.where(k < self.Hp, su[np.minimum(k, self.Hp - 1)], -1)
-
-            g0 = np.full((nT, nX2, 64, 8), -1, dtype=np.int64)
-            g1 = np.full((nT, nK2, 64, 8), -1, dtype=np.int64)
-            g2 = np.full((nT, nK2, 64, 8), -1, dtype=np.int64)
-            g3 = np.full((nOT, nK2, 64, 8), -1, dtype=np.int64)
-            for T in range(nT):
-                out_unit = su[16 * T + li]
-                for X in range(nX2):
-                    for e in range(8):
-                        r_in = 32 * X + 8 * lg + e
-                        feat = np.where(r_in < D, feat_of_rank[np.minimum(r_in, D - 1)], -1)
-                        g0[T, X, :, e] = cidx("W0", out_unit, feat, D, M0)
-                for K in range(nK2):
-                    for e in range(8):
-                        iu = in_slot(32 * K + 8 * lg + e)
-                        g1[T, K, :, e] = cidx("W1", out_unit, iu, H, M1)
-                        g2[T, K, :, e] = cidx("W2", out_unit, iu, H, M2)
-            for O in range(nOT):
-                orow = 16 * O + li
-                r_out, sft = orow // self.n_out, orow % self.n_out
-                crow = np.where(r_out < D, self.n_out * feat_of_rank[np.minimum(r_out, D - 1)] + sft, -1)
-                for K in range(nK2):
-                    for e in range(8):
-                        g3[O, K, :, e] = cidx("W3", crow, in_slot(32 * K + 8 * lg + e), H, M3)
-            b = t * L["per_transform"]
-            for name, arr in (("g0", g0), ("g1", g1), ("g2", g2), ("g3", g3)):
-                a = arr.reshape(-1)
-                idx[b + L["off"][name]: b + L["off"][name] + a.size] = a
-        return idx.astype(np.int32)
+        *_, layout = self._bf16_parts()
+        idx = np.full(layout.total * self.n_transforms, -1, dtype=np.int32)
+        for t, c in enumerate(self.connections()):
+            _fill(idx, t * layout.total, layout, {"g" + k: _frag_a32(c["W" + k]) for k in "0123"})
+        return idx
 
     # ------------------------------------------- bf16 training image (wide flows)
     def wide_layout(self):
@@ -566,47 +522,27 @@ class MAFSpec:
         ``W0f [HK][DK]  W0b = W0f^T  W1f [HK][HK]  W1b  W2f  W2b  W3f [OK][HK]  W3b`` and of its float32 bias image
         ``b0 b1 b2 [HK]  b3 [OK]``; hidden units in slot order, features in canonical order, ``OK = n_out DK`` and W3 rows
         ``n_out feature + s`` (the canonical order: shift, raw for the affine map; widths, heights, derivatives for a spline)."""
+        DK, HK, OK, weights, biases = self._wide_parts()
+        return dict(DK=DK, HK=HK, OK=OK, per_transform=weights.total, bias_per_transform=biases.total)
+
+    def _wide_parts(self):
         DK, HK = _ceil_to(self.n_dim, 32), _ceil_to(self.Hp, 32)
         OK = self.n_out * DK
-        return dict(DK=DK, HK=HK, OK=OK, per_transform=2 * (HK * DK + 2 * HK * HK + OK * HK),
-                    bias_per_transform=3 * HK + OK)
+        shapes = {"W0": (HK, DK), "W1": (HK, HK), "W2": (HK, HK), "W3": (OK, HK)}
+        weights = _layout([(k + d, s if d == "f" else s[::-1]) for k, s in shapes.items() for d in "fb"])
+        return DK, HK, OK, weights, _layout([("b0", (HK,)), ("b1", (HK,)), ("b2", (HK,)), ("b3", (OK,))])
 
     def wide_index(self):
         """``(image_idx, bias_idx)`` int32: canonical index of every element of the two images, -1 where masked or
         padded.  ``image[i] = bf16(flat[idx[i]])``; the ``W?f`` parts double as the scatter map of the weight gradients."""
-        D, H, NO = self.n_dim, self.hidden, self.n_out
-        L = self.wide_layout()
-        DK, HK, OK = L["DK"], L["HK"], L["OK"]
-        su = np.full(HK, -1, dtype=np.int64)
-        su[:self.Hp] = self.slot_unit
-        hv = su >= 0
-        u = np.where(hv, su, 0)
-        feat = np.arange(DK)
-        fv = feat < D
-        fc = np.where(fv, feat, 0)
-        orow = np.arange(OK)                                  # n_out feature + s
-        ov = (orow // NO) < D
-        oc = np.where(ov, orow, 0)
-        img = np.full(self.n_transforms * L["per_transform"], -1, dtype=np.int64)
-        bias = np.full(self.n_transforms * L["bias_per_transform"], -1, dtype=np.int64)
-        for t in range(self.n_transforms):
-            base = t * self.params_per_transform
-            M0, M1, M2, M3 = self.masks(t)
-            off = {k: base + v[0] for k, v in self.offsets.items()}
-            w0 = np.where(hv[:, None] & fv[None, :] & M0[u][:, fc], off["W0"] + u[:, None] * D + fc[None, :], -1)
-            w1 = np.where(hv[:, None] & hv[None, :] & M1[u][:, u], off["W1"] + u[:, None] * H + u[None, :], -1)
-            w2 = np.where(hv[:, None] & hv[None, :] & M2[u][:, u], off["W2"] + u[:, None] * H + u[None, :], -1)
-            w3 = np.where(ov[:, None] & hv[None, :] & M3[oc][:, u], off["W3"] + oc[:, None] * H + u[None, :], -1)
-            parts = [w0, w0.T, w1, w1.T, w2, w2.T, w3, w3.T]
-            o = t * L["per_transform"]
-            for a in parts:
-                img[o:o + a.size] = np.ascontiguousarray(a).reshape(-1)
-                o += a.size
-            ob = t * L["bias_per_transform"]
-            for k, name in enumerate(("b0", "b1", "b2")):
-                bias[ob + k * HK: ob + (k + 1) * HK] = np.where(hv, off[name] + u, -1)
-            bias[ob + 3 * HK: ob + 3 * HK + OK] = np.where(ov, off["b3"] + oc, -1)
-        return img.astype(np.int32), bias.astype(np.int32)
+        *_, weights, biases = self._wide_parts()
+        img = np.full(self.n_transforms * weights.total, -1, dtype=np.int32)
+        bias = np.full(self.n_transforms * biases.total, -1, dtype=np.int32)
+        for t, c in enumerate(self.connections(by_rank=False, tile=32)):     # (slots and features padded to the 32-wide k tiles)
+            _fill(img, t * weights.total, weights, {k + d: c[k] if d == "f" else c[k].T
+                                                 for k in ("W0", "W1", "W2", "W3") for d in "fb"})
+            _fill(bias, t * biases.total, biases, {k: c[k] for k in biases.shapes})
+        return img, bias
 
     # ------------------------------------------------------------- training
     def train_layout(self):
@@ -619,20 +555,15 @@ class MAFSpec:
         layout (lane (q, j) reg r <-> W[out 16*To + 4q + r][in 16*Ti + j]), -1 = masked / padding:
         g0 [nT][nXT], g1/g2 [nT][nT], g3 [nOT][nT], then the bias maps b0,b1,b2 [Hp], b3 [Op].
         """
+        (_, szT, offT, pkT), (_, szG, offG, gmap) = self._train_parts()
+        return dict(szT=szT, offT=offT, pkT_per_transform=pkT, szG=szG, offG=offG, gmap_per_transform=gmap)
+
+    def _train_parts(self):
         nT, nXT, nOT = self.nT, self.nXT, self.nOT
-        szT = {"f0T": nXT * nT * 256, "f1T": nT * nT * 256, "f2T": nT * nT * 256, "f3T": nT * nOT * 256}
-        szG = {"g0": nT * nXT * 256, "g1": nT * nT * 256, "g2": nT * nT * 256, "g3": nOT * nT * 256,
-               "gb0": self.Hp, "gb1": self.Hp, "gb2": self.Hp, "gb3": self.Op}
-        offT, o = {}, 0
-        for k, v in szT.items():
-            offT[k] = o
-            o += v
-        pkT = o
-        offG, o = {}, 0
-        for k, v in szG.items():
-            offG[k] = o
-            o += v
-        return dict(szT=szT, offT=offT, pkT_per_transform=pkT, szG=szG, offG=offG, gmap_per_transform=o)
+        return (_layout([("f0T", (nXT, nT, 64, 4)), ("f1T", (nT, nT, 64, 4)), ("f2T", (nT, nT, 64, 4)),
+                         ("f3T", (nT, nOT, 64, 4))]),
+                _layout([("g0", (nT, nXT, 64, 4)), ("g1", (nT, nT, 64, 4)), ("g2", (nT, nT, 64, 4)), ("g3", (nOT, nT, 64, 4)),
+                         ("gb0", (self.Hp,)), ("gb1", (self.Hp,)), ("gb2", (self.Hp,)), ("gb3", (self.Op,))]))
 
     def par_per_transform(self) -> int:
         """Floats of the hyper-network's outputs kept per row set and transform (``pmc_maf_train_t.par_scratch``):
@@ -746,87 +677,15 @@ class MAFSpec:
         return self._train_index
 
     def _build_train_index(self):
-        D, H, Hp = self.n_dim, self.hidden, self.Hp
-        nT, nXT, nOT = self.nT, self.nXT, self.nOT
-        L = self.train_layout()
-        pT = np.full(L["pkT_per_transform"] * self.n_transforms, -1, dtype=np.int64)
-        gm = np.full(L["gmap_per_transform"] * self.n_transforms, -1, dtype=np.int64)
-        lane = np.arange(64)
-        li, lk = lane & 15, lane >> 4
-        su = self.slot_unit
-        for t in range(self.n_transforms):
-            base_c = t * self.params_per_transform
-            rank = self.orders[t]
-            feat_of_rank = np.argsort(rank)
-            M0, M1, M2, M3 = self.masks(t)
-
-            def cidx(name, row, col, ncol, mask):
-                off, _ = self.offsets[name]
-                ok = (row >= 0) & (col >= 0)
-                r = np.where(ok, row, 0)
-                c = np.where(ok, col, 0)
-                ok = ok & mask[r, c]
-                return np.where(ok, base_c + off + r * ncol + c, -1)
-
-            def feat(r_in):
-                return np.where(r_in < D, feat_of_rank[np.minimum(r_in, D - 1)], -1)
-
-            def orow(o):
-                r_out, s = o // self.n_out, o % self.n_out
-                return np.where(r_out < D, self.n_out * feat_of_rank[np.minimum(r_out, D - 1)] + s, -1)
-
-            # ---- transposed fragments: A[i = lane&15][k = lane>>4], component c
-            f0T = np.full((nXT, nT, 64, 4), -1, dtype=np.int64)
-            f1T = np.full((nT, nT, 64, 4), -1, dtype=np.int64)
-            f2T = np.full((nT, nT, 64, 4), -1, dtype=np.int64)
-            f3T = np.full((nT, nOT, 64, 4), -1, dtype=np.int64)
-            # (the inner tile index is broadcast: one numpy call per (tile, component) instead of one per tile pair)
-            in_all = su[16 * np.arange(nT)[:, None] + li[None, :]]                 # [Ti][lane]: hidden unit of the in slot
-            x_all = feat(16 * np.arange(nXT)[:, None] + li[None, :])               # [Xi][lane]: feature of the in rank
-            for To in range(nT):
-                for c in range(4):
-                    out_u = su[16 * To + 4 * c + lk][None, :]
-                    f0T[:, To, :, c] = cidx("W0", np.broadcast_to(out_u, x_all.shape), x_all, D, M0)
-                    f1T[:, To, :, c] = cidx("W1", np.broadcast_to(out_u, in_all.shape), in_all, H, M1)
-                    f2T[:, To, :, c] = cidx("W2", np.broadcast_to(out_u, in_all.shape), in_all, H, M2)
-            for O in range(nOT):
-                for c in range(4):
-                    crow = orow(16 * O + 4 * c + lk)[None, :]
-                    f3T[:, O, :, c] = cidx("W3", np.broadcast_to(crow, in_all.shape), in_all, H, M3)
-            # ---- gradient scatter: lane (q = lane>>4, j = lane&15), reg r
-            g0 = np.full((nT, nXT, 64, 4), -1, dtype=np.int64)
-            g1 = np.full((nT, nT, 64, 4), -1, dtype=np.int64)
-            g2 = np.full((nT, nT, 64, 4), -1, dtype=np.int64)
-            g3 = np.full((nOT, nT, 64, 4), -1, dtype=np.int64)
-            for To in range(nT):
-                for r in range(4):
-                    out_u = su[16 * To + 4 * lk + r][None, :]
-                    g0[To, :, :, r] = cidx("W0", np.broadcast_to(out_u, x_all.shape), x_all, D, M0)
-                    g1[To, :, :, r] = cidx("W1", np.broadcast_to(out_u, in_all.shape), in_all, H, M1)
-                    g2[To, :, :, r] = cidx("W2", np.broadcast_to(out_u, in_all.shape), in_all, H, M2)
-            for O in range(nOT):
-                for r in range(4):
-                    crow = orow(16 * O + 4 * lk + r)[None, :]
-                    g3[O, :, :, r] = cidx("W3", np.broadcast_to(crow, in_all.shape), in_all, H, M3)
-
-            def bidx(name):
-                off, _ = self.offsets[name]
-                return np.where(su >= 0, base_c + off + np.maximum(su, 0), -1)
-
-            gb3 = np.full(self.Op, -1, dtype=np.int64)
-            off3, _ = self.offsets["b3"]
-            for r in range(D):
-                for j in range(self.n_out):
-                    gb3[self.n_out * r + j] = base_c + off3 + self.n_out * feat_of_rank[r] + j
-            bT, bG = t * L["pkT_per_transform"], t * L["gmap_per_transform"]
-            for name, arr in (("f0T", f0T), ("f1T", f1T), ("f2T", f2T), ("f3T", f3T)):
-                a = arr.reshape(-1)
-                pT[bT + L["offT"][name]: bT + L["offT"][name] + a.size] = a
-            for name, arr in (("g0", g0), ("g1", g1), ("g2", g2), ("g3", g3), ("gb0", bidx("b0")),
-                              ("gb1", bidx("b1")), ("gb2", bidx("b2")), ("gb3", gb3)):
-                a = arr.reshape(-1)
-                gm[bG + L["offG"][name]: bG + L["offG"][name] + a.size] = a
-        return pT.astype(np.int32), gm.astype(np.int32)
+        packT, gmap = self._train_parts()
+        pT = np.full(packT.total * self.n_transforms, -1, dtype=np.int32)
+        gm = np.full(gmap.total * self.n_transforms, -1, dtype=np.int32)
+        for t, c in enumerate(self.connections()):
+            # transposed fragments: A operands of W^T; gradient scatter: the tiles of W in C layout
+            _fill(pT, t * packT.total, packT, {f"f{k}T": _frag_a4(c["W" + k].T) for k in "0123"})
+            _fill(gm, t * gmap.total, gmap, {**{"g" + k: _frag_c(c["W" + k]) for k in "0123"},
+                                          **{"gb" + k: c["b" + k] for k in "0123"}})
+        return pT, gm
 
     # ------------------------------------------------------------ accounting
     def flops_forward_dense(self) -> int:

@@ -85,19 +85,20 @@ def test_pack_index_reproduces_masked_weights(D, T):
     assert packed.size == spec.pk_size
     for t in range(T):
         M0, M1, M2, M3 = spec.masks(t)
-        base = t * spec.pk_per_transform
         rank = spec.orders[t]
         feat_of_rank = np.argsort(rank)
         su = spec.slot_unit
         # W0 natural [rank][slot]
-        w0n = packed[base + spec.pk_offsets["w0n"]: base + spec.pk_offsets["w0n"] + spec.sz_w0n].reshape(spec.Dp, spec.Hp)
+        w0n = spec.packed_view(packed, t, "w0n")
+        assert w0n.shape == (spec.Dp, spec.Hp)
         W0 = spec.view(flat, t, "W0") * M0
         for s in range(spec.Hp):
             for r in range(D):
                 exp = W0[su[s], feat_of_rank[r]] if su[s] >= 0 else 0.0
                 assert w0n[r, s] == exp
         # fragment arrays reproduce W1 (A[i][k] of tile T, K-tile K, chunk c)
-        f1 = packed[base + spec.pk_offsets["f1"]: base + spec.pk_offsets["f1"] + spec.sz_f12].reshape(spec.nT, spec.nT, 64, 4)
+        f1 = spec.packed_view(packed, t, "f1")
+        assert f1.shape == (spec.nT, spec.nT, 64, 4)
         W1 = spec.view(flat, t, "W1") * M1
         lane = np.arange(64)
         for Tt in range(spec.nT):
@@ -180,10 +181,8 @@ def test_spline_flow_packing(D, T):
         W3 = spec.view(flat, t, "W3") * M3
         b3 = spec.view(flat, t, "b3")
         feat_of_rank = np.argsort(spec.orders[t])
-        base = t * spec.pk_per_transform
-        f3i = packed[base + spec.pk_offsets["f3i"]: base + spec.pk_offsets["f3i"] + spec.sz_f3i].reshape(D, 2, spec.nT, 64, 4)
-        b3i = packed[base + spec.pk_offsets["b3i"]: base + spec.pk_offsets["b3i"] + spec.sz_b3i].reshape(D, 32)
-        f3 = packed[base + spec.pk_offsets["f3"]: base + spec.pk_offsets["f3"] + spec.sz_f3].reshape(spec.nOT, spec.nT, 64, 4)
+        f3i, b3i, f3 = (spec.packed_view(packed, t, k) for k in ("f3i", "b3i", "f3"))
+        assert (f3i.shape, b3i.shape, f3.shape) == ((D, 2, spec.nT, 64, 4), (D, 32), (spec.nOT, spec.nT, 64, 4))
         for r in range(D):
             feat = feat_of_rank[r]
             np.testing.assert_array_equal(b3i[r, :23], b3[23 * feat: 23 * feat + 23])
@@ -251,9 +250,9 @@ def _tri6_emulate(spec, flat, z):
     ladj = np.zeros(n)
     tg = spec.tile_groups()
     for t in reversed(range(spec.n_transforms)):
-        P = packed[t * spec.pk_per_transform:(t + 1) * spec.pk_per_transform]
-        po = spec.pk_offsets
-        sec = lambda name, shape: P[po[name]:po[name] + int(np.prod(shape))].reshape(shape)
+        def sec(name, shape):
+            assert spec.pk_shapes[name] == shape
+            return spec.packed_view(packed, t, name)
 
         def frag_block(f):           # [lane][4] -> dense 16 x 16 block, rows = out slot, cols = in slot
             B = np.zeros((16, 16))
@@ -361,9 +360,9 @@ def _nsf2_emulate(spec, flat, z):
     ladj = np.zeros(n)
     src = None                                              # the previous transform's x, by ITS ranks
     for t in reversed(range(T_)):
-        P = packed[t * spec.pk_per_transform:(t + 1) * spec.pk_per_transform]
-        po = spec.pk_offsets
-        sec = lambda name, shape: P[po[name]:po[name] + int(np.prod(shape))].reshape(shape)
+        def sec(name, shape):
+            assert spec.pk_shapes[name] == shape
+            return spec.packed_view(packed, t, name)
 
         def frag_block(f):           # [lane][4] -> dense 16 x 16 block, rows = out slot, cols = in slot
             B = np.zeros((16, 16))
