@@ -88,6 +88,11 @@ typedef struct pmc_maf {
                                         * with float32 accumulation; two walker subsets share a workgroup at D = 128 (BASELINE config
                                         * 5: 5000 walkers in one round).  AUTO takes it when the image is attached and the flow is
                                         * one the lane sweep is preferred for; _LANE (8) always multiplies in float32 */
+#define PMC_INVERSE_TRIANGULAR_WG 10 /* right-looking sweep of the affine flows with a workgroup of eight wavefronts per 16 rows and two
+                                      * hidden-width LDS arrays (csrc/maf_inverse_wg.hip): an explicit opt-in (Flow(inverse_sweep=
+                                      * "workgroup")), AUTO never takes it.  It covers every affine flow whose degree groups fit a tile
+                                      * and whose arrays fit 160 KiB of LDS -- among them the default-width flows at D = 92-114, which
+                                      * no other sweep fits.  Workgroup barriers only between its wavefronts, float32 throughout */
 #define PMC_INVERSE_TRIANGULAR_DUO 7  /* the same sweep with a second, burst wavefront per 16 rows, right-looking (AUTO: affine flows of < 16 hidden tiles, spline flows with D <= 64) */
 
 /* packed[i] = idx[i] >= 0 ? flat[idx[i]] : 0   (canonical fp32 params -> kernel layout) */
@@ -149,6 +154,7 @@ int pmc_maf_inverse_auto_is_nsf2(const pmc_maf_t* m);
 #define PMC_SWEEP_NSF_DUO 7
 #define PMC_SWEEP_DPASS_LEAN 8     /* the D-pass algorithm through the lean instance of the forward workgroup kernel (affine and
                                     * spline flows): AUTO / NAIVE where no sweep and no other D-pass kernel fits the LDS */
+#define PMC_SWEEP_WG 9             /* the workgroup sweep (PMC_INVERSE_TRIANGULAR_WG): sweep and lds_bytes set, every other field 0 */
 typedef struct pmc_inverse_plan {
     int32_t sweep, fused, epilogue, maxo, fm, subsets, waves, helper_fmt, lds_bytes;
 } pmc_inverse_plan_t;

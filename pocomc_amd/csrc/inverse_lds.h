@@ -75,6 +75,13 @@ static inline size_t pmc_wg_instance(const pmc_maf_t* m, int nw, int inverse, in
     return lds <= PMC_LDS_CAP ? lds : 0;
 }
 
+// ---- workgroup sweep of the affine flows (maf_inverse_wg.hip): x and y by rank, the partial pre-activations of hidden layers
+// 1 and 2, the partial output rows, the current hidden tile's h0 | h1 | h2, the log-determinant words of 8 wavefronts
+#define WGS_NW 8
+static inline size_t pmc_lds_wg_sweep(const pmc_maf_t* m) {
+    return (size_t)(2 * m->Dp * 16 + 2 * m->Hp * 16 + m->nOT * 256 + 3 * 256 + 16 * WGS_NW) * sizeof(float);
+}
+
 // A launch with dynamic LDS: hipFuncSetAttribute first when it is more than 48 KiB (every such launch: nothing is remembered)
 template <typename K, typename... A>
 static int pmc_launch_lds(K kernel, const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {

@@ -1,8 +1,9 @@
 // Which flow-inverse kernel runs: the one place that decides it (host code only, no kernel).
 //
-// Seven kernels invert a flow (pocomc/mcmc.py:88, every preconditioned step): the two D-pass kernels of the reference's
+// Eight kernels invert a flow (pocomc/mcmc.py:88, every preconditioned step): the two D-pass kernels of the reference's
 // algorithm (the workgroup one in a full and a lean instance), the register-chain sweeps of the affine flows with one (SOLO) or two (DUO) wavefronts per 16 walkers, the
-// lane-per-walker sweep (LANE), the spline sweeps with one (NSF_SOLO) or two (NSF_DUO) wavefronts.  pmc_plan_inverse maps
+// lane-per-walker sweep (LANE), the spline sweeps with one (NSF_SOLO) or two (NSF_DUO) wavefronts, the workgroup sweep of the affine flows
+// (WG: on request only).  pmc_plan_inverse maps
 // (flow, rows, algo) to the instance pmc_maf_inverse / pmc_step_pre launch -- or, asked for the fused launch, to the
 // proposal + inverse (+ scaler epilogue) instance of the step, if there is one.  What a sweep covers is a predicate below;
 // AUTO's preferences are measured.  The measurement builds' A/B switches are read here only.
@@ -34,6 +35,9 @@ static bool duo_covers(const pmc_maf_t* m) {
 // resident walker sets simply runs its surplus workgroups as they find a CU: it is taken whenever its LDS fits.
 static bool duo_wanted(const pmc_maf_t* m) {
     return duo_mode() >= 0 ? duo_mode() != 0 : pmc_lds_duo(m, chain_maxo(m)) <= PMC_LDS_CAP;
+}
+static bool wg_sweep_covers(const pmc_maf_t* m) {
+    return affine_tri(m) && transform_offsets_ok(m) && pmc_lds_wg_sweep(m) <= PMC_LDS_CAP;
 }
 static bool nsf_duo_covers(const pmc_maf_t* m) {
     return !nsf_duo_off() && m->n_out == 23 && m->tri_ok && m->D <= 64 && m->D >= 2 && image_offsets_ok(m) &&
@@ -202,6 +206,11 @@ static const char* plan_affine(const pmc_maf_t* m, int64_t n, int algo, pmc_inve
         set_lane(p, m, n, false, hb);
         return nullptr;
     }
+    case PMC_INVERSE_TRIANGULAR_WG:                      // (an opt-in: AUTO never comes here)
+        if (!m->tri_ok) return "pmc_maf_inverse: triangular sweep needs degree groups <= one tile";
+        if (!wg_sweep_covers(m)) return "pmc_maf_inverse: the workgroup sweep needs its arrays in 160 KiB of LDS";
+        set_plain(p, PMC_SWEEP_WG, pmc_lds_wg_sweep(m));
+        return nullptr;
     case PMC_INVERSE_NAIVE: return set_dpass(p, m);
     default: return "pmc_maf_inverse: unknown algo";
     }

@@ -26,6 +26,7 @@ from .maf_spec import MAFSpec, SPEC_BY_NAME, NSF_BY_NAME, spec_by_name, bf16_for
 
 PMC_MAF_TABLES = 4             # pmc_maf_t.reserved: the metadata carries the two-wave affine sweep's table image
 PMC_MAF_VARIANT_LEAN_LDS = 8   # pmc_maf_t.reserved: the two-array instances also where the full ones fit (Flow.lean_lds)
+PMC_INVERSE_TRIANGULAR_WG = 10 # pmc_maf_inverse algo: the workgroup sweep of the affine flows (Flow(inverse_sweep="workgroup"))
 
 
 def torch_double_to_float(x: torch.Tensor, warn: bool = True) -> torch.Tensor:
@@ -52,7 +53,7 @@ class Flow:
     """Masked autoregressive flow resident on one MI355X."""
 
     def __init__(self, n_dim, flow="nsf3", device=None, seed=None, precision="f32", train_engine=None,
-                 inverse_precision=None, inverse_guard=True):                                                                 # default flow as pocomc/flow.py:46
+                 inverse_precision=None, inverse_guard=True, inverse_sweep="auto"):                                           # default flow as pocomc/flow.py:46
         """``precision="bf16"`` (affine flows; spline flows of hidden width >= ``train.WIDE_MIN_HIDDEN``, the rule of
         ``maf_spec.bf16_forward_refusal``): ``forward`` / ``log_prob`` run on the bf16 matrix cores with fp32
         accumulation (``csrc/maf_forward_bf16.h``; BASELINE config 5 names this precision; the spline itself is evaluated in
@@ -78,6 +79,12 @@ class Flow:
         drawn from the step's own proposal law at the current sigma / mu -- ``mcmc._proposal_draws`` -- i.e. the
         heavy-tailed points ``mcmc.py:88`` actually inverts), so a rare outlier proposal can still see a 16-bit error
         beyond the bounds within a call.
+        ``inverse_sweep`` ("auto" | "workgroup"): "workgroup" inverts with the workgroup sweep of the affine flows
+        (``csrc/maf_inverse_wg.hip``, ``PMC_INVERSE_TRIANGULAR_WG``: eight wavefronts per 16 rows, two hidden-width LDS
+        arrays, float32) instead of the library's own choice -- the triangular sweep that fits the default-width flows at
+        ``n_dim`` 92-114, which otherwise take the D-pass algorithm.  An explicit opt-in: ``ValueError`` with the library's
+        message where the sweep does not cover the flow (spline flows, ``n_dim`` 2, layouts beyond 160 KiB of LDS), and
+        with any ``inverse_precision`` but "f32".
         Default: float32 everywhere, like the reference."""
         self.n_dim = int(n_dim)
         if isinstance(flow, MAFSpec):
@@ -131,6 +138,16 @@ class Flow:
                                        device=self.device)
             self._desc.lane16 = self._lane16.data_ptr()
             self._desc.lane16_fmt = 1 if inverse_precision == "bf16" else 2
+        if inverse_sweep not in ("auto", "workgroup"):
+            raise ValueError("inverse_sweep must be 'auto' or 'workgroup'")
+        if inverse_sweep == "workgroup":
+            if inverse_precision != "f32":
+                raise ValueError("inverse_sweep='workgroup' is a float32 sweep: it needs inverse_precision='f32'")
+            plan = _lib.pmc_inverse_plan_t()
+            if self.lib.pmc_maf_inverse_plan(C.byref(self._desc), 16, PMC_INVERSE_TRIANGULAR_WG, 0, C.byref(plan)):
+                raise ValueError(self.lib.pmc_last_error().decode())
+            self.inverse_algo = PMC_INVERSE_TRIANGULAR_WG
+        self.inverse_sweep = inverse_sweep
         self._bf16 = None              # (gather map, image, elements per transform), built on first use
         self.inverse_guard = None      # last result of check_inverse_precision
         self.inverse_guard_enabled = bool(inverse_guard)
@@ -145,6 +162,7 @@ class Flow:
                 "params": self.params.detach().cpu().numpy(), "inverse_algo": self.inverse_algo,
                 "precision": self.precision, "train_engine": self.train_engine,
                 "inverse_precision": self.inverse_precision, "inverse_guard": self.inverse_guard_enabled,
+                "inverse_sweep": self.inverse_sweep,
                 # the guard's last verdict travels with the parameters: a flow that fell back to float32 resumes in float32
                 # (re-checking on reload would use other points than the run's and could decide otherwise)
                 "inverse_fell_back": bool(self._lane16 is not None and not self._desc.lane16),
@@ -153,7 +171,8 @@ class Flow:
     def __setstate__(self, st):
         spec = MAFSpec(*st["spec"])
         self.__init__(st["n_dim"], spec, precision=st.get("precision", "f32"), train_engine=st.get("train_engine"),
-                      inverse_precision=st.get("inverse_precision"), inverse_guard=st.get("inverse_guard", True))
+                      inverse_precision=st.get("inverse_precision"), inverse_guard=st.get("inverse_guard", True),
+                      inverse_sweep=st.get("inverse_sweep", "auto"))
         self.set_params(st["params"], check=("inverse_fell_back" not in st))
         if "inverse_fell_back" in st and self._lane16 is not None:
             self.inverse_guard = st.get("inverse_guard_result")
