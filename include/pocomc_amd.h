@@ -93,6 +93,12 @@ typedef struct pmc_maf {
                                       * "workgroup")), AUTO never takes it.  It covers every affine flow whose degree groups fit a tile
                                       * and whose arrays fit 160 KiB of LDS -- among them the default-width flows at D = 92-114, which
                                       * no other sweep fits.  Workgroup barriers only between its wavefronts, float32 throughout */
+#define PMC_INVERSE_TRIANGULAR_WG_NSF 11 /* the spline counterpart (csrc/maf_inverse_wg_nsf.hip): the same workgroup of eight wavefronts per
+                                          * 16 rows and two hidden-width LDS arrays, the 23 parameters of a rank by a left-looking product over
+                                          * the final h2 tiles that all wavefronts share.  An explicit opt-in (Flow(inverse_sweep=
+                                          * "workgroup_spline")), AUTO never takes it.  It covers every 8-bin spline flow whose degree groups
+                                          * fit a tile and whose arrays fit 160 KiB of LDS -- among them the default-width flows at
+                                          * D = 97-108, which no other spline sweep fits.  Affine flows do not know it */
 #define PMC_INVERSE_TRIANGULAR_DUO 7  /* the same sweep with a second, burst wavefront per 16 rows, right-looking (AUTO: affine flows of < 16 hidden tiles, spline flows with D <= 64) */
 
 /* packed[i] = idx[i] >= 0 ? flat[idx[i]] : 0   (canonical fp32 params -> kernel layout) */
@@ -155,6 +161,7 @@ int pmc_maf_inverse_auto_is_nsf2(const pmc_maf_t* m);
 #define PMC_SWEEP_DPASS_LEAN 8     /* the D-pass algorithm through the lean instance of the forward workgroup kernel (affine and
                                     * spline flows): AUTO / NAIVE where no sweep and no other D-pass kernel fits the LDS */
 #define PMC_SWEEP_WG 9             /* the workgroup sweep (PMC_INVERSE_TRIANGULAR_WG): sweep and lds_bytes set, every other field 0 */
+#define PMC_SWEEP_WG_NSF 10        /* the workgroup sweep of the spline flows (PMC_INVERSE_TRIANGULAR_WG_NSF): sweep and lds_bytes set, every other field 0 */
 typedef struct pmc_inverse_plan {
     int32_t sweep, fused, epilogue, maxo, fm, subsets, waves, helper_fmt, lds_bytes;
 } pmc_inverse_plan_t;

@@ -82,6 +82,14 @@ static inline size_t pmc_lds_wg_sweep(const pmc_maf_t* m) {
     return (size_t)(2 * m->Dp * 16 + 2 * m->Hp * 16 + m->nOT * 256 + 3 * 256 + 16 * WGS_NW) * sizeof(float);
 }
 
+// ---- workgroup sweep of the spline flows (maf_inverse_wg_nsf.hip): x and y by rank, the partial pre-activations of hidden
+// layer 1, the array that holds layer 2's partial pre-activations beyond the current tile and the final h2 up to it, the
+// current tile's h0 | h1 | h2, one output-partial tile per wavefront, the rank's parameter panel [16][32] and knot tables
+// [16][24], the log-determinant words
+static inline size_t pmc_lds_wg_nsf_sweep(const pmc_maf_t* m) {
+    return (size_t)(2 * m->Dp * 16 + 2 * m->Hp * 16 + 3 * 256 + WGS_NW * 256 + 16 * 32 + 16 * 24 + 16 * WGS_NW) * sizeof(float);
+}
+
 // A launch with dynamic LDS: hipFuncSetAttribute first when it is more than 48 KiB (every such launch: nothing is remembered)
 template <typename K, typename... A>
 static int pmc_launch_lds(K kernel, const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {

@@ -1,9 +1,9 @@
 // Which flow-inverse kernel runs: the one place that decides it (host code only, no kernel).
 //
-// Eight kernels invert a flow (pocomc/mcmc.py:88, every preconditioned step): the two D-pass kernels of the reference's
+// Nine kernels invert a flow (pocomc/mcmc.py:88, every preconditioned step): the two D-pass kernels of the reference's
 // algorithm (the workgroup one in a full and a lean instance), the register-chain sweeps of the affine flows with one (SOLO) or two (DUO) wavefronts per 16 walkers, the
-// lane-per-walker sweep (LANE), the spline sweeps with one (NSF_SOLO) or two (NSF_DUO) wavefronts, the workgroup sweep of the affine flows
-// (WG: on request only).  pmc_plan_inverse maps
+// lane-per-walker sweep (LANE), the spline sweeps with one (NSF_SOLO) or two (NSF_DUO) wavefronts, the workgroup sweeps of the affine flows
+// (WG) and of the spline flows (WG_NSF), both on request only.  pmc_plan_inverse maps
 // (flow, rows, algo) to the instance pmc_maf_inverse / pmc_step_pre launch -- or, asked for the fused launch, to the
 // proposal + inverse (+ scaler epilogue) instance of the step, if there is one.  What a sweep covers is a predicate below;
 // AUTO's preferences are measured.  The measurement builds' A/B switches are read here only.
@@ -38,6 +38,9 @@ static bool duo_wanted(const pmc_maf_t* m) {
 }
 static bool wg_sweep_covers(const pmc_maf_t* m) {
     return affine_tri(m) && transform_offsets_ok(m) && pmc_lds_wg_sweep(m) <= PMC_LDS_CAP;
+}
+static bool wg_nsf_sweep_covers(const pmc_maf_t* m) {
+    return m->n_out == 23 && m->tri_ok && transform_offsets_ok(m) && pmc_lds_wg_nsf_sweep(m) <= PMC_LDS_CAP;
 }
 static bool nsf_duo_covers(const pmc_maf_t* m) {
     return !nsf_duo_off() && m->n_out == 23 && m->tri_ok && m->D <= 64 && m->D >= 2 && image_offsets_ok(m) &&
@@ -156,6 +159,13 @@ static const char* plan_spline(const pmc_maf_t* m, int algo, pmc_inverse_plan_t*
     const bool any = algo == PMC_INVERSE_AUTO;
     if (any) algo = (m->tri_ok && m->n_out == 23) ? PMC_INVERSE_TRIANGULAR : PMC_INVERSE_NAIVE;
     if (algo == PMC_INVERSE_NAIVE) return set_dpass(p, m);
+    if (algo == PMC_INVERSE_TRIANGULAR_WG_NSF) {          // (an opt-in: AUTO never comes here)
+        if (!m->tri_ok) return "pmc_maf_inverse: triangular sweep needs degree groups <= one tile";
+        if (m->n_out != 23) return "pmc_maf_inverse: the spline sweeps are built for 8 bins (PMC_INVERSE_NAIVE covers the others)";
+        if (!wg_nsf_sweep_covers(m)) return "pmc_maf_inverse: the workgroup spline sweep needs its arrays in 160 KiB of LDS";
+        set_plain(p, PMC_SWEEP_WG_NSF, pmc_lds_wg_nsf_sweep(m));
+        return nullptr;
+    }
     if (algo != PMC_INVERSE_TRIANGULAR && algo != PMC_INVERSE_TRIANGULAR_SOLO && algo != PMC_INVERSE_TRIANGULAR_DUO)
         return "pmc_maf_inverse: spline flows know PMC_INVERSE_TRIANGULAR (_SOLO, _DUO) and PMC_INVERSE_NAIVE";
     if (!m->tri_ok) return "pmc_maf_inverse: triangular sweep needs degree groups <= one tile";

@@ -38,16 +38,6 @@
 #define WGS_NU 7                   // hidden tiles / output tiles of a wavefront's update whose fragments are requested before the
 #define WGS_NUO 3                  // diagonal phase (flows of <= 57 hidden tiles, D <= 192; beyond: in place)
 
-// acc += W[16 x 16 fragment held in registers] * act[one operand tile in LDS]
-__device__ __forceinline__ f32x4 frag_mac(f32x4 acc, const float4& a, const float* act_tile, int lane) {
-    const float4 b = *reinterpret_cast<const float4*>(act_tile + (lane << 2));
-    acc = MFMA(a.x, b.x, acc);
-    acc = MFMA(a.y, b.y, acc);
-    acc = MFMA(a.z, b.z, acc);
-    acc = MFMA(a.w, b.w, acc);
-    return acc;
-}
-
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_sweep_kernel(pmc_maf_t m, const float* __restrict__ in,
                                                                        float* __restrict__ out,

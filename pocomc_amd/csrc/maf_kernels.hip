@@ -205,6 +205,7 @@ int pmc_launch_inverse(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, co
         case PMC_SWEEP_NSF_DUO: return pmc_launch_nsf2(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_NSF_SOLO: return pmc_launch_inverse_tri_nsf(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_WG: return pmc_launch_inverse_wg_sweep(plan, pa, m, z, x, ladj, n, stream);
+        case PMC_SWEEP_WG_NSF: return pmc_launch_inverse_wg_nsf_sweep(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_DPASS_SPLINE:
         case PMC_SWEEP_DPASS_LEAN: return pmc_launch_inverse_dpass_wg(plan, pa, m, z, x, ladj, n, stream);
         case PMC_SWEEP_DPASS_AFFINE: if (pa) break;

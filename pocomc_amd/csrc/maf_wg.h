@@ -30,6 +30,16 @@ __device__ __forceinline__ f32x4 rows_of(const float* H, int T, int q, int p) {
     return a;
 }
 
+// acc += W[16 x 16 fragment held in registers] * act[one operand tile in LDS]
+__device__ __forceinline__ f32x4 frag_mac(f32x4 acc, const float4& a, const float* act_tile, int lane) {
+    const float4 b = *reinterpret_cast<const float4*>(act_tile + (lane << 2));
+    acc = MFMA(a.x, b.x, acc);
+    acc = MFMA(a.y, b.y, acc);
+    acc = MFMA(a.z, b.z, acc);
+    acc = MFMA(a.w, b.w, acc);
+    return acc;
+}
+
 __device__ __forceinline__ f32x4 relu_gate(f32x4 a, const float* H, int T, int q, int p) {
     const f32x4 h = rows_of(H, T, q, p);
 #pragma unroll

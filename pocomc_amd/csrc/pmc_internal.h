@@ -48,6 +48,8 @@ int pmc_launch_inverse_dpass_wg(const pmc_inverse_plan_t* plan, const ProposeArg
                                 float* x, float* ladj, int64_t n, hipStream_t stream);
 int pmc_launch_inverse_wg_sweep(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
                                 float* x, float* ladj, int64_t n, hipStream_t stream);
+int pmc_launch_inverse_wg_nsf_sweep(const pmc_inverse_plan_t* plan, const ProposeArgs* pa, const pmc_maf_t* m, const float* z,
+                                    float* x, float* ladj, int64_t n, hipStream_t stream);
 // The float32 trainer's chain-kernel instance (maf_train.hip): the launch's LDS bytes, or 0 where neither the full nor the
 // lean buffer plan fits; *lean which one, *ksplit (may be NULL) the partial-tile staging, *full_bytes the full plan's size
 size_t pmc_train_instance(const pmc_maf_t* m, int* lean, int* ksplit, size_t* full_bytes);

@@ -27,6 +27,7 @@ from .maf_spec import MAFSpec, SPEC_BY_NAME, NSF_BY_NAME, spec_by_name, bf16_for
 PMC_MAF_TABLES = 4             # pmc_maf_t.reserved: the metadata carries the two-wave affine sweep's table image
 PMC_MAF_VARIANT_LEAN_LDS = 8   # pmc_maf_t.reserved: the two-array instances also where the full ones fit (Flow.lean_lds)
 PMC_INVERSE_TRIANGULAR_WG = 10 # pmc_maf_inverse algo: the workgroup sweep of the affine flows (Flow(inverse_sweep="workgroup"))
+PMC_INVERSE_TRIANGULAR_WG_NSF = 11 # ... of the 8-bin spline flows (Flow(inverse_sweep="workgroup_spline"))
 
 
 def torch_double_to_float(x: torch.Tensor, warn: bool = True) -> torch.Tensor:
@@ -79,12 +80,17 @@ class Flow:
         drawn from the step's own proposal law at the current sigma / mu -- ``mcmc._proposal_draws`` -- i.e. the
         heavy-tailed points ``mcmc.py:88`` actually inverts), so a rare outlier proposal can still see a 16-bit error
         beyond the bounds within a call.
-        ``inverse_sweep`` ("auto" | "workgroup"): "workgroup" inverts with the workgroup sweep of the affine flows
-        (``csrc/maf_inverse_wg.hip``, ``PMC_INVERSE_TRIANGULAR_WG``: eight wavefronts per 16 rows, two hidden-width LDS
-        arrays, float32) instead of the library's own choice -- the triangular sweep that fits the default-width flows at
-        ``n_dim`` 92-114, which otherwise take the D-pass algorithm.  An explicit opt-in: ``ValueError`` with the library's
+        ``inverse_sweep`` ("auto" | "workgroup" | "workgroup_spline"): "workgroup" inverts with the workgroup sweep of the
+        affine flows (``csrc/maf_inverse_wg.hip``, ``PMC_INVERSE_TRIANGULAR_WG``: eight wavefronts per 16 rows, two
+        hidden-width LDS arrays, float32) instead of the library's own choice -- the triangular sweep that fits the
+        default-width flows at ``n_dim`` 92-114, which otherwise take the D-pass algorithm.  An explicit opt-in: ``ValueError`` with the library's
         message where the sweep does not cover the flow (spline flows, ``n_dim`` 2, layouts beyond 160 KiB of LDS), and
-        with any ``inverse_precision`` but "f32".
+        with any ``inverse_precision`` but "f32".  "workgroup_spline" is the same opt-in for the 8-bin spline flows
+        (``csrc/maf_inverse_wg_nsf.hip``, ``PMC_INVERSE_TRIANGULAR_WG_NSF``: the same workgroup and LDS arrays, the 23
+        parameters of a rank by a left-looking product that the eight wavefronts share) -- the triangular sweep that fits the
+        default-width spline flows at ``n_dim`` 97-108, which otherwise take the D-pass algorithm.  ``ValueError`` with the
+        library's message where it does not cover the flow (affine flows, ``n_dim`` 2, other bin counts than 8, layouts
+        beyond 160 KiB of LDS); spline flows are float32 sweeps, so ``inverse_precision`` is "f32" already.
         Default: float32 everywhere, like the reference."""
         self.n_dim = int(n_dim)
         if isinstance(flow, MAFSpec):
@@ -138,15 +144,16 @@ class Flow:
                                        device=self.device)
             self._desc.lane16 = self._lane16.data_ptr()
             self._desc.lane16_fmt = 1 if inverse_precision == "bf16" else 2
-        if inverse_sweep not in ("auto", "workgroup"):
-            raise ValueError("inverse_sweep must be 'auto' or 'workgroup'")
-        if inverse_sweep == "workgroup":
+        if inverse_sweep not in ("auto", "workgroup", "workgroup_spline"):
+            raise ValueError("inverse_sweep must be 'auto', 'workgroup' or 'workgroup_spline'")
+        if inverse_sweep != "auto":
             if inverse_precision != "f32":
-                raise ValueError("inverse_sweep='workgroup' is a float32 sweep: it needs inverse_precision='f32'")
+                raise ValueError(f"inverse_sweep='{inverse_sweep}' is a float32 sweep: it needs inverse_precision='f32'")
+            algo = PMC_INVERSE_TRIANGULAR_WG if inverse_sweep == "workgroup" else PMC_INVERSE_TRIANGULAR_WG_NSF
             plan = _lib.pmc_inverse_plan_t()
-            if self.lib.pmc_maf_inverse_plan(C.byref(self._desc), 16, PMC_INVERSE_TRIANGULAR_WG, 0, C.byref(plan)):
+            if self.lib.pmc_maf_inverse_plan(C.byref(self._desc), 16, algo, 0, C.byref(plan)):
                 raise ValueError(self.lib.pmc_last_error().decode())
-            self.inverse_algo = PMC_INVERSE_TRIANGULAR_WG
+            self.inverse_algo = algo
         self.inverse_sweep = inverse_sweep
         self._bf16 = None              # (gather map, image, elements per transform), built on first use
         self.inverse_guard = None      # last result of check_inverse_precision

@@ -149,9 +149,10 @@ class Sampler:
         """Arguments and defaults of ``pocomc/sampler.py:154-185``, plus
 
         ``flow``          a name (``"nsf6"``, ``"maf3"`` ...) or a ready ``Flow``, taken as it is with everything it was built
-                          with -- e.g. ``Flow(D, "maf6", inverse_sweep="workgroup")``: every preconditioned step then
-                          inverts with the workgroup sweep (the triangular sweep that fits the default-width affine flows
-                          at ``n_dim`` 92 - 114; ``Flow``), with no further argument here;
+                          with -- e.g. ``Flow(D, "maf6", inverse_sweep="workgroup")`` or ``Flow(D, "nsf6",
+                          inverse_sweep="workgroup_spline")``: every preconditioned step then inverts with the workgroup
+                          sweep (the triangular sweeps that fit the default-width affine flows at ``n_dim`` 92 - 114 and
+                          the spline flows at 97 - 108; ``Flow``), with no further argument here;
         ``group``         a ``torch.distributed`` process group (default: the initialised default group): one process
                           per GPU, ``n_active`` a multiple of the number of ranks, ``random_state`` required (the ranks
                           replicate the pool bookkeeping from the same numpy / torch streams);
@@ -272,8 +273,8 @@ class Sampler:
         self.metric, self.sample, self.resample, self.dynamic = metric, sample, resample, dynamic
         self.preconditioned = precondition
 
-        # (a ready Flow -- e.g. Flow(D, MAFSpec(D, 8), precision="bf16") or Flow(D, "maf6", inverse_sweep="workgroup") -- is taken
-        #  as it is, like the reference takes a zuko flow)
+        # (a ready Flow -- e.g. Flow(D, MAFSpec(D, 8), precision="bf16"), Flow(D, "maf6", inverse_sweep="workgroup") or
+        #  Flow(D, "nsf6", inverse_sweep="workgroup_spline") -- is taken as it is, like the reference takes a zuko flow)
         self.flow = flow if isinstance(flow, Flow) else Flow(D, flow)
         if self.flow.n_dim != D:
             raise ValueError("flow has the wrong number of dimensions")
