@@ -981,6 +981,32 @@ int pmc_resample_multinomial(const double* w, int64_t P, const double* uniforms,
 int pmc_resample_systematic(const double* w, int64_t P, double offset, int64_t n_out, double* cdf,
                             int64_t* idx, void* stream);
 
+/* ----------------------------------------------------------------- flow prior */
+
+/* A finished run's flow and scaler as a normalised density on the prior's box (pocomc_amd.FlowPrior):
+ *   log p(x) = flow.log_prob(u(x)) - log|dx/du|,  u = Reparameterize.forward(x),
+ * as two launches around the flow's own forward call (pmc_maf_forward / pmc_maf_forward_bf16 with log_prob on u32).
+ *
+ * pmc_flow_prior_pre: Reparameterize.forward (scaler.py:180-202) of n rows with its log-determinant, in one launch.
+ * x: f64, element (r, j) at x[r * row_stride + j * col_stride] (strides in elements, >= 0).  The loads are coalesced for
+ * (row_stride, col_stride) = (D, 1) -- a C-contiguous [n][D] -- and (1, n) -- the MCMC step's column-major view; other
+ * pairs are read correctly, slowly.  s->bc is not read: the forward map has no boundary conditions.
+ * u32 f32 [n][D]: u for the flow; a row with inside == 0 is written as zeros (the flow never reads a NaN or an inf).
+ * ldj f64 [n]: log|dx/du| = sum_j J_j (+ sum_log_sigma when s->scale), J_j the Jacobian term of the inverse map at the
+ * unscaled value the forward map has just computed (no second inversion), added j = 0, 1, ..., D - 1 by one lane: a row's
+ * bits depend on its values alone -- not on the layout, on n or on the row's place in the call.
+ * inside int32 [n]: 1 iff every x_j and every u_j (as float32) is finite and every bounded x_j lies strictly inside its
+ * bounds.
+ * Width limit: D <= 157 (the widest MCMC step; a block keeps 64 rows of x / J and of u32 in LDS: 64 * ((D | 1) * 8 + D * 4)
+ * + 256 bytes).  A wider call fails with "n_dim too large" before anything is launched or written. */
+int pmc_flow_prior_pre(const pmc_scaler_t* s, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
+                       float* u32, double* ldj, int32_t* inside, void* stream);
+
+/* logp[r] = (double)lp32[r] - ldj[r] where inside[r] and that value is finite, -inf everywhere else: never NaN, never
+ * +inf.  lp32 f32 [n] (the flow's log_prob of u32), ldj f64 [n], inside int32 [n], logp f64 [n]. */
+int pmc_flow_prior_post(const float* lp32, const double* ldj, const int32_t* inside, double* logp, int64_t n,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ gfx950 kernels behind the C ABI of ``include/pocomc_amd.h``.
 """
 from .maf_spec import MAFSpec  # noqa: F401
 
-__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "mcmc", "tools"]
+__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "mcmc", "tools"]
 
 
 def __getattr__(name):
@@ -29,4 +29,7 @@ def __getattr__(name):
     if name == "DevicePrior":
         from .prior import DevicePrior
         return DevicePrior
+    if name == "FlowPrior":
+        from .prior import FlowPrior
+        return FlowPrior
     raise AttributeError(name)

@@ -227,6 +227,8 @@ SIGNATURES = {
     "pmc_gather": (C.c_int, [c_p, i64, i32] + [c_p] * 10 + [c_p]),
     "pmc_resample_multinomial": (C.c_int, [c_p, i64, c_p, i64, c_p, c_p, c_p]),
     "pmc_resample_systematic": (C.c_int, [c_p, i64, f64, i64, c_p, c_p, c_p]),
+    "pmc_flow_prior_pre": (C.c_int, [P(pmc_scaler_t), c_p, i64, i64, i64, c_p, c_p, c_p, c_p]),
+    "pmc_flow_prior_post": (C.c_int, [c_p, c_p, c_p, c_p, i64, c_p]),
 }
 
 _lib = None

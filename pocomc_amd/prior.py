@@ -9,7 +9,10 @@ The MCMC step can evaluate it on the device instead (``device_descriptor``, ``in
 ``device=False`` never.
 
 ``DevicePrior`` is the other kind of prior: any joint density, written once as a GPU function (``logpdf_device``), that the
-MCMC step calls on the device like a device likelihood (``Sampler(device_likelihood=True, device_prior=True)``)."""
+MCMC step calls on the device like a device likelihood (``Sampler(device_likelihood=True, device_prior=True)``).
+
+``FlowPrior`` is such a prior made of a finished run: its trained flow and fitted scaler are a normalised density on the
+prior's box, evaluated by two launches around the flow's own forward kernel (``csrc/flow_prior.hip``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -252,3 +255,183 @@ class DevicePrior:
     @property
     def dim(self):
         return len(self._bounds)
+
+
+class FlowPrior:
+    """The density a finished run leaves behind, as a prior: a trained ``Flow`` and a fitted diagonal ``Reparameterize``,
+
+        ``log p(x) = flow.log_prob(u(x)) - log|dx/du|``,   ``u = scaler.forward(x)``,
+
+    normalised on the scaler's box.  The posterior of one experiment becomes the prior of the next; the evidence of the second
+    run is then that of its data given the first run's.
+
+    ``logpdf_device(x)``  the ``DevicePrior`` contract: an ``(n, D)`` float64 tensor on the flow's device in, an ``(n,)``
+                          float64 tensor out, on the current stream, in three launches -- ``pmc_flow_prior_pre`` (u as
+                          float32, the scaler's log-determinant, the support test), the flow's own forward call with
+                          ``log_prob`` (so a ``precision="bf16"`` flow keeps its matrix-core kernel), ``pmc_flow_prior_post``.
+                          No host synchronisation; no copy of ``x`` when it is C-contiguous or the MCMC step's column-major
+                          view (any other layout is made contiguous first).  -inf outside the support, on a bound and for
+                          rows with a NaN or an inf; never NaN, never +inf.  A row's value does not depend on the layout, on
+                          ``n`` or on its place in ``x``.
+    ``logpdf(x)``         numpy in, numpy out, through the same function.
+    ``rvs(size)``         base draw from torch's global CPU generator (as ``Flow.sample``), ``flow.inverse``, ``scaler.inverse``.
+    ``bounds``, ``dim``   the scaler's.
+
+    The density is float32 flow arithmetic: ``log p`` carries the flow kernels' relative error (1e-5 affine, 1e-4 spline).
+    The prior owns copies of both parts: later ``set_params`` / ``fit`` calls on the source flow or scaler do not move it.  The
+    scaler's boundary flags (periodic / reflective) are ignored: the forward map does not use them.  There is no
+    ``device_descriptor``: the step calls the function."""
+
+    MAX_DIM = 157            # the widest MCMC step (pmc_flow_prior_pre refuses wider calls)
+    RVS_ROUNDS = 8           # redraws of rows that land outside the support before rvs gives up
+    _WORKSPACES = 8          # row counts whose workspaces are kept
+
+    def __init__(self, flow, scaler):
+        from .flow import Flow
+        from .scaler import Reparameterize
+        if not isinstance(flow, Flow):
+            raise ValueError(f"FlowPrior: flow must be a pocomc_amd.Flow, got {type(flow).__name__}")
+        if not isinstance(scaler, Reparameterize):
+            raise ValueError(f"FlowPrior: scaler must be a pocomc_amd.Reparameterize, got {type(scaler).__name__}")
+        if not scaler.diagonal:
+            raise ValueError("FlowPrior: the scaler must be diagonal (diagonal=False scalers transform arrays only)")
+        if scaler.mu is None or scaler.sigma is None:
+            raise ValueError("FlowPrior: the scaler is not fitted (mu is None)")
+        if flow.n_dim != scaler.ndim:
+            raise ValueError(f"FlowPrior: the flow has {flow.n_dim} dimensions, the scaler {scaler.ndim}")
+        if flow.n_dim > self.MAX_DIM:
+            raise ValueError(f"FlowPrior: n_dim = {flow.n_dim} is too large (n_dim <= {self.MAX_DIM})")
+        self._restore(flow.__getstate__(), self._scaler_state(scaler), flow.device)
+
+    @classmethod
+    def from_sampler(cls, sampler):
+        """The prior a finished ``Sampler`` run leaves: ``sampler.flow`` and ``sampler.scaler``.  ``ValueError`` unless the
+        sampler is preconditioned, has run to beta = 1 and has trained its flow."""
+        if not getattr(sampler, "preconditioned", False):
+            raise ValueError("FlowPrior.from_sampler: the sampler is not preconditioned (precondition=False): it trains no flow")
+        walkers = getattr(sampler, "walkers", None)
+        beta = None if walkers is None else walkers.get("beta")
+        if beta is None or 1.0 - float(beta) >= 1e-4:
+            raise ValueError("FlowPrior.from_sampler: the sampler has not run to beta = 1"
+                             + ("" if beta is None else f" (beta = {float(beta):.6g})"))
+        if getattr(sampler, "flow_untrained", True):
+            raise ValueError("FlowPrior.from_sampler: the sampler's flow has not been trained")
+        return cls(sampler.flow, sampler.scaler)
+
+    # ----------------------------------------------------------------- state
+    @staticmethod
+    def _scaler_state(s):
+        return dict(low=np.array(s.low, dtype=np.float64), high=np.array(s.high, dtype=np.float64), transform=s.transform,
+                    scale=bool(s.scale), mu=np.array(s.mu, dtype=np.float64), sigma=np.array(s.sigma, dtype=np.float64))
+
+    def _restore(self, flow_state, scaler_state, device=None):
+        import copy
+        import torch
+        from .flow import Flow
+        from .scaler import Reparameterize
+        st = copy.deepcopy(scaler_state)
+        D = len(st["low"])
+        if device is None:
+            from . import _lib
+            device = _lib.require_gpu()
+        with torch.cuda.device(device):
+            self.flow = Flow.__new__(Flow)
+            self.flow.__setstate__(copy.deepcopy(flow_state))
+        self.scaler = Reparameterize(D, bounds=np.stack([st["low"], st["high"]], axis=1), transform=st["transform"],
+                                     scale=st["scale"], diagonal=True, device=self.flow.device)
+        self.scaler.mu, self.scaler.sigma = st["mu"], st["sigma"]
+        self._sdesc = self.scaler.device_descriptor()       # (the scaler keeps the tensors it points to)
+        self._ws = {}
+
+    def __getstate__(self):
+        return {"flow": self.flow.__getstate__(), "scaler": self._scaler_state(self.scaler)}
+
+    def __setstate__(self, st):
+        self._restore(st["flow"], st["scaler"])
+
+    # ----------------------------------------------------------------- density
+    def _workspace(self, n):
+        import torch
+        ws = self._ws.get(n)
+        if ws is None:
+            dev = self.flow.device
+            ws = (torch.empty(n, self.dim, dtype=torch.float32, device=dev),      # u32
+                  torch.empty(n, self.dim, dtype=torch.float32, device=dev),      # z (the flow writes it; not used)
+                  torch.empty(n, dtype=torch.float32, device=dev),                # the flow's log_prob
+                  torch.empty(n, dtype=torch.float64, device=dev),                # the scaler's log-determinant
+                  torch.empty(n, dtype=torch.int32, device=dev))                  # inside the support
+            while len(self._ws) >= self._WORKSPACES:
+                self._ws.pop(next(iter(self._ws)))
+            self._ws[n] = ws
+        return ws
+
+    def logpdf_device(self, x):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        D = self.dim
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"FlowPrior.logpdf_device: expected an (n, {D}) float64 tensor, got {what}")
+        _on_device(x, self.flow.device, "FlowPrior.logpdf_device")
+        n = x.shape[0]
+        out = torch.empty(n, dtype=torch.float64, device=self.flow.device)
+        if n == 0:
+            return out
+        # the two layouts the kernel reads with coalesced loads; everything else is copied once
+        if x.is_contiguous():
+            strides = (D, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (D, 1)
+        u32, z, lp32, ldj, inside = self._workspace(n)
+        lib = self.flow.lib
+        with torch.cuda.device(self.flow.device):
+            _lib.check(lib.pmc_flow_prior_pre(C.byref(self._sdesc), C.c_void_p(x.data_ptr()), strides[0], strides[1], n,
+                                              _lib.ptr(u32), _lib.ptr(ldj), _lib.ptr(inside), _lib.stream_handle()),
+                       "pmc_flow_prior_pre")
+            self.flow._forward_call(u32, z, None, lp32, n)
+            _lib.check(lib.pmc_flow_prior_post(_lib.ptr(lp32), _lib.ptr(ldj), _lib.ptr(inside), _lib.ptr(out), n,
+                                               _lib.stream_handle()), "pmc_flow_prior_post")
+        return out
+
+    def logpdf(self, x):
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"FlowPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
+        return self.logpdf_device(torch.from_numpy(x).to(self.flow.device)).cpu().numpy()
+
+    # ----------------------------------------------------------------- draws
+    def _inside(self, x):
+        lo = np.where(np.isfinite(self.scaler.low), self.scaler.low, -np.inf)
+        hi = np.where(np.isfinite(self.scaler.high), self.scaler.high, np.inf)
+        return np.all(np.isfinite(x) & (x > lo) & (x < hi), axis=1)
+
+    def rvs(self, size=1):
+        import torch
+        size = int(size)
+        x = np.empty((size, self.dim), dtype=np.float64)
+        todo = np.arange(size)
+        for _ in range(1 + self.RVS_ROUNDS):
+            if len(todo) == 0:
+                return x
+            z = torch.randn(len(todo), self.dim, dtype=torch.float32)
+            u, _ = self.flow.inverse(z)
+            xi, _ = self.scaler.inverse(u.numpy().astype(np.float64))
+            x[todo] = xi
+            todo = todo[~self._inside(xi)]
+        if len(todo):
+            raise RuntimeError(f"FlowPrior.rvs: {len(todo)} of {size} rows are still outside the support after "
+                               f"{self.RVS_ROUNDS} redraws")
+        return x
+
+    @property
+    def bounds(self):
+        return np.stack([self.scaler.low, self.scaler.high], axis=1)
+
+    @property
+    def dim(self):
+        return self.scaler.ndim
