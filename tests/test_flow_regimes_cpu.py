@@ -78,6 +78,52 @@ def test_float32_evaluations_meet_the_criterion(name):
             R.check(q, v, f"cpu oracle32 inverse, {name}")
 
 
+@pytest.mark.parametrize("name", list(fr.WIDE_GAIN))
+def test_the_wide_gain_fixtures_are_not_vacuous(name):
+    """The scaled-up default-width flows of ``tests/test_gpu_flow_regimes.py`` (D = 102: 51 hidden tiles; D = 128, 86) on their
+    fixed rows -- the rows the GPU test uses: the latent images are the float32 oracle's.  A condition on the inputs, not a
+    tolerance: every counted forward row, and at least 3/4 of the counted inverse rows, has ``C e_i <= 1e-2`` in every
+    quantity, so the criterion binds there.  Measured: gain 2 every inverse row (both families, D = 102 and 128); gain 3:
+    x 15 of 16 rows (affine), 38 of 42 (spline), ladj all -- gain 3 stays 3.  On those rows the float32 numpy oracle (spline
+    flows: and the kernels' spline formulas) has no row beyond ``max(bound, C e_i)``; its median ``err/e`` exceeds
+    ``MEDIAN_BOUND`` on the forward z of the affine gain-3 flow alone (2.5), which is what ``check`` takes its median bound
+    from.  ``check`` then holds the kernels' formulas to the numpy oracle the way it holds a kernel."""
+    spec, flat, data = fr.wide_gain_fixture(name)
+    ev = [OracleMAF(spec, flat)] + ([fr.KernelSplineOracle(spec, flat)] if spec.univariate == "rqs" else [])
+    for direction in ("forward",) if name in fr.WIDE_FORWARD_ONLY else ("forward", "inverse"):
+        if direction == "forward":
+            inp = fr.forward_inputs(spec, flat, data)
+            f32 = [dict(zip(("z", "ladj"), e.forward(inp)), log_prob=e.log_prob(inp)) for e in ev]
+        else:
+            inp = fr.inverse_inputs(spec, flat, data, fr.oracle_latent(spec, flat))
+            f32 = [dict(zip(("x", "ladj"), e.inverse(inp))) for e in ev]
+        R = fr.Reference(spec, flat, inp, direction, k=fr.n_perturb(spec))
+        assert R.ok.sum() >= fr.ROWS[spec.n_dim][direction == "inverse"]
+        shares = fr.assert_non_vacuous(R, name)
+        for q in R.ref:
+            well = np.flatnonzero(R.ok & (fr.C * R.env[q] <= fr.WELL))
+            for d in f32:
+                s = R.check(q, d[q], f"cpu float32 {direction}, {name}", rows=well, raise_=False, record=False)
+                assert s["failing"] == 0, (name, direction, q, s)
+            s = fr.check(R, q, f32[-1][q], f"cpu float32 {direction}, {name}", [d[q] for d in f32])
+            print(f"{name} {direction} {q}: share {shares[q]:.3f} ({len(well)} of {int(R.ok.sum())} rows)")
+
+
+def test_the_wide_fixtures_reach_their_regime_and_width():
+    """Default width at D = 102 is the largest padded width there is (Hp = 816, 51 hidden tiles, Dp = 112); the gains push
+    the log-scales / the derivatives where the D = 10 gain fixtures have them."""
+    spec, flat, data = fr.wide_gain_fixture("maf3-d102-g16")
+    assert (spec.Hp, spec.nT, spec.Dp, spec.hidden) == (816, 51, 112, 512)
+    assert fr.regime_stats(spec, flat, data[:64])["big_log_scale_share"] > 0.2
+    spec, flat, data = fr.wide_gain_fixture("nsf3-d102-g4")
+    s = fr.regime_stats(spec, flat, data[:64])
+    assert (spec.Hp, spec.nT) == (816, 51) and s["deriv_min"] < 0.1 and s["deriv_max"] > 10
+    assert fr.wide_gain_fixture("nsf3-d128-g2")[0].nT == 33 and fr.wide_gain_fixture("nsf3-d86-g2")[0].nT == 43
+    # which widths deal output products of the workgroup spline sweep by K range: not D = 128, whose tiles hold 3-4 groups
+    assert [fr.k_split_tiles(MAFSpec(D, 3, univariate="rqs")) for D in (10, 32, 86, 102, 128)] == [0, 0, 27, 35, 0]
+    assert max(MAFSpec(D, 3).Hp for D in range(86, 158)) == 816
+
+
 def test_the_envelope_needs_the_knots_of_the_spline():
     """Inputs and parameters alone (``knots=False``) do not bound the float32 oracle's error on a trained spline flow: the
     knot rounding is a float32 evaluation's own, and the envelope has to carry it."""
@@ -190,3 +236,65 @@ def test_the_kernels_spline_formulas_carry_a_larger_median_than_numpy():
     assert s_k["median_ratio"] > 1.15 * s_np["median_ratio"]
     x = fr.two_modes(10, 128, 1)
     np.testing.assert_allclose(fr.KernelSplineOracle(spec, flat).forward(x)[0], OracleMAF(spec, flat).forward(x)[0], rtol=0, atol=1e-4)
+
+
+def test_every_fixture_lists_the_sweeps_the_plan_admits():
+    """``algorithms`` of ``tests/test_gpu_flow_regimes.py`` asks the inverse plan, which reads a descriptor's layout fields
+    only -- so which sweeps every fixture's spec runs under the regime tests is pinned here, without a GPU: every fixture
+    from before lists what it listed and its family's workgroup sweep (algorithm 10 / 11), D = 102 lists AUTO, NAIVE (both
+    the lean D-pass kernel) and the workgroup sweep, the D = 128 spline flow AUTO's lone-wave sweep, NAIVE and 11."""
+    import ctypes as C
+    import types
+    import test_gpu_flow_regimes as g
+    from pocomc_amd import _lib
+
+    def fake_flow(s):
+        d = _lib.pmc_maf_t(packed=None, meta=None, lane16=None, lane16_fmt=0, reserved=0, D=s.n_dim, H=s.hidden,
+                           T=s.n_transforms, Hp=s.Hp, Dp=s.Dp, nT=s.nT, nXT=s.nXT, nOT=s.nOT,
+                           pk_per_transform=s.pk_per_transform, tri_ok=int(s.tri_ok), n_out=s.n_out)
+        return types.SimpleNamespace(spec=s, lib=_lib.load(), _desc=d)
+
+    specs = {name: mk() for name, (mk, _) in list(g.FITTED.items()) + list(g.GAIN.items())}
+    specs.update({name: MAFSpec(D, 3, univariate=uni) for name, (D, uni, _) in fr.WIDE_GAIN.items()})
+    assert sorted(specs) == sorted(g.FIXTURES) and set(g.LISTED_BEFORE) == set(g.FIXTURES) - set(g.WIDE)
+    expect = dict(g.LISTED_BEFORE)
+    for name, s in specs.items():
+        wg = g.WG_NSF if s.univariate == "rqs" else g.WG
+        f = fake_flow(s)
+        for n in (64, 4096):
+            algos = g.algorithms(f, n)
+            if name in expect:
+                assert algos == expect[name] + [wg], (name, n, algos)
+            elif s.n_dim == 102:
+                assert algos == [g.AUTO, g.NAIVE, wg], (name, n, algos)
+                assert [g.plan_of(f, n, a).sweep for a in algos] == [g.S_DPASS_LEAN, g.S_DPASS_LEAN, g.S_WG_NSF if wg == g.WG_NSF else g.S_WG]
+            else:
+                assert name in ("nsf3-d128-g2", "nsf3-d86-g2") and algos == [0, 1, 2, 6, g.WG_NSF], (name, n, algos)
+                dpass = 2 if s.n_dim == 128 else g.S_DPASS_LEAN          # (the full D-pass instance fits at D = 128, not at 86)
+                assert [g.plan_of(f, n, a).sweep for a in algos] == [g.S_NSF_SOLO, g.S_NSF_SOLO, dpass, g.S_NSF_SOLO, g.S_WG_NSF]
+        g._assert_the_listed_sweeps(name, f, g.algorithms(f, 64))
+
+
+def test_the_relu_margin_finds_the_kink_the_trainer_test_met():
+    """Row 4 of the five rows ``default_rng(36)`` draws from ``nsf3-d102-g2``'s data has a layer-1 pre-activation of the last
+    transform (unit 97) at -1.5e-7 in float64, among units of ~0.3.  The float32 numpy oracle computes it as +4.1e-7 in a
+    product of the five rows and as -1.3e-7 in a product of that row alone: its sign is a matter of the order of additions.
+    ``relu_margin`` puts that row, and no other of the five, below ``RELU_MARGIN``; about one row in twenty of the
+    fixture's data is."""
+    spec, flat, data = fr.wide_gain_fixture("nsf3-d102-g2")
+    x = data[np.random.default_rng(5 + 31).choice(len(data), 5, replace=False)]
+    m = fr.relu_margin(spec, flat, x)
+    assert (m <= fr.RELU_MARGIN).tolist() == [False, False, False, False, True]
+    pre = {}
+    for dt in (np.float64, np.float32):
+        o = OracleMAF(spec, flat, dtype=dt)
+        cur = x.astype(dt)
+        for t in range(2):
+            cur, _ = o._fwd(t, cur)
+        w = o._mats[2]
+        h0 = np.maximum(cur @ w["W0"].T + w["b0"], 0)
+        pre[dt] = h0 + (h0 @ w["W1"].T + w["b1"])
+    assert -1e-6 < pre[np.float64][4, 97] < 0 and abs(pre[np.float32][4, 97]) < 1e-6
+    assert np.median(np.abs(pre[np.float64])) > 0.1
+    share = (fr.relu_margin(spec, flat, data) <= fr.RELU_MARGIN).mean()
+    assert 0.01 < share < 0.15

@@ -18,7 +18,9 @@ x4 / x16), the kernel is held to be as good a float32 evaluation as those (``che
 evaluations of the same rows: the numpy oracle and, for spline flows, ``KernelSplineOracle`` -- the kernels' spline
 formulas in float32 (reciprocals, exp2 of a rounded product, running-sum knots), whose median on a trained nsf6 inverse is
 ~1.9 against numpy's 1.5 (tests/test_flow_regimes_cpu.py): the kernels' ~2.0 there comes from those formulas."""
+import ctypes as C
 import functools
+import time
 
 import numpy as np
 import pytest
@@ -39,6 +41,10 @@ FITTED = {
     "nsf3-d32-fit": (lambda: MAFSpec(32, 3, univariate="rqs"), lambda: fr.rosenbrock_draws(32, 4000, 4)),
     "maf6-d50-fit": (lambda: MAFSpec(50, 6), lambda: fr.bimodal_draws(50, 4000, 5)),
     "maf8-d128-fit": (lambda: MAFSpec(128, 8), lambda: config5_rows()),          # config 5: H = 512
+    # default width at D = 102: Hp = 816, 51 hidden tiles -- AUTO is the lean D-pass kernel, the workgroup sweeps (algorithms
+    # 10 / 11) the only triangular ones.  maf6-d102-fit: the flow of test_a_sampler_runs_with_the_workgroup_sweep_at_100_dimensions
+    "maf6-d102-fit": (lambda: MAFSpec(102, 6), lambda: fr.bimodal_draws(102, 4000, 6)),
+    "nsf3-d102-fit": (lambda: MAFSpec(102, 3, univariate="rqs"), lambda: fr.two_modes(102, 4000, 7)),
 }
 EPOCHS = {"maf8-d128-fit": 10}      # config 5's validation loss is best near epoch 5 and diverges by 50 (bench.py)
 
@@ -47,7 +53,24 @@ EPOCHS = {"maf8-d128-fit": 10}      # config 5's validation loss is best near ep
 # AUTO never takes it for these flows) on the affine flow with its output layer x16 misses C e_i on the inverse
 # log-determinant on 15 of 192 rows (worst 0.09), where float32 evaluations in two other orders of addition miss up to 6
 # (worst 0.09): the same magnitude, more than twice the rows.  Not explained yet.
-OPEN_FINDINGS = {("maf3-d10-g16", 2)}
+#
+# ("maf3-d10-g16", 10): the affine workgroup sweep on the same rows misses THE SAME 15 rows (worst 0.093; the float32
+# evaluations: 6 rows, worst 0.093; limit 2 x 6).  Measured since: the numpy oracle, the sequential oracle and eight more
+# float32 evaluations of the hyper-network on the host (bias first, terms in index order, reversed, six random orders) miss
+# 4 to 6 rows each, every one of them among these 15; the register-chain and lane sweeps (algorithms 0, 1, 6, 7, 8) miss
+# 2 or 3 of them.  What the D-pass kernel and the workgroup sweep share, and no other evaluation has, is the dense kernels'
+# order -- bias first, K tiles ascending on two accumulators -- with the IEEE forms of the soft clip and the division.
+# Which of the two it is, is not found.
+#
+# ("maf3-d102-g16", "forward z"): the lean forward kernel at 51 hidden tiles and gain 16 meets the row criterion on every
+# row (worst err 2.3e-06, worst err/e 7.0) and misses the MEDIAN rule: median err/e 2.43 against 1.25 x the numpy
+# oracle's 1.92 = 2.40 (32 rows, k = 4).  Over three envelope seeds and k = 4 / 8 the kernel's median is 1.21 - 1.35 x
+# numpy's; the host's sequential float32 evaluation (one rounded product and one rounded sum per term) has 2.76 on the same
+# rows, so the kernel lies between two float32 orders of addition.  The criterion takes only the numpy oracle here; at
+# gain 2 and 3 the same kernel's median is below numpy's (1.51 / 1.73, 2.32 / 2.48).  ("maf3-d102-g16", "forward log_prob"):
+# the same rows, the same rule, through -z^2 / 2 -- no row beyond (worst err 2.3e-06), median 2.45 against 1.25 x 1.92.
+# The log-determinant meets the criterion (median 0.5).
+OPEN_FINDINGS = {("maf3-d10-g16", 2), ("maf3-d10-g16", 10), ("maf3-d102-g16", "forward z"), ("maf3-d102-g16", "forward log_prob")}
 
 
 def config5_rows():
@@ -60,14 +83,26 @@ def config5_rows():
     return np.asarray(sc.forward(x[:5000]), np.float32)
 GAIN = {"maf3-d10-g4": (lambda: MAFSpec(10, 3), 4.0), "maf3-d10-g16": (lambda: MAFSpec(10, 3), 16.0),
         "nsf6-d10-g4": (lambda: MAFSpec(10, 6, univariate="rqs"), 4.0)}
-FIXTURES = list(FITTED) + list(GAIN)
-ROWS = {10: (384, 192), 32: (256, 96), 50: (256, 96), 128: (64, 8)}          # forward / inverse rows per D (float64 D-pass cost)
+FIXTURES = list(FITTED) + list(GAIN) + list(fr.WIDE_GAIN)
+WIDE = ("maf6-d102-fit", "nsf3-d102-fit") + tuple(fr.WIDE_GAIN)          # default width, n_dim 86 / 102 / 128: the non-vacuity condition holds
+FORWARD_ONLY = fr.WIDE_FORWARD_ONLY                                      # forward, log_prob and the trainer's loss only
+ROWS = fr.ROWS                                                           # forward / inverse rows per D (float64 D-pass cost)
+
+AUTO, NAIVE, WG, WG_NSF = 0, 2, 10, 11
+S_NSF_SOLO, S_DPASS_LEAN, S_WG, S_WG_NSF = 6, 8, 9, 10                    # include/pocomc_amd.h PMC_SWEEP_*
+DPASS_SWEEPS = (1, 2, S_DPASS_LEAN)
+# what ``algorithms`` listed for each fixture before it asked the plan: it lists at least these
+LISTED_BEFORE = {"maf3-d10-fit": [0, 1, 2, 8, 6, 7], "maf3-d32-fit": [0, 1, 2, 8, 6, 7], "nsf6-d10-fit": [0, 1, 2, 6, 7],
+                 "nsf3-d32-fit": [0, 1, 2, 6, 7], "maf6-d50-fit": [0, 1, 2, 8, 6, 7], "maf8-d128-fit": [0, 1, 2, 8],
+                 "maf3-d10-g4": [0, 1, 2, 8, 6, 7], "maf3-d10-g16": [0, 1, 2, 8, 6, 7], "nsf6-d10-g4": [0, 1, 2, 6, 7]}
 
 
 @functools.lru_cache(maxsize=None)
 def fixture(name):
     """(spec, float32 parameters, data rows)."""
     from pocomc_amd import Flow
+    if name in fr.WIDE_GAIN:
+        return fr.wide_gain_fixture(name)
     if name in GAIN:
         mk, g = GAIN[name]
         spec = mk()
@@ -89,87 +124,132 @@ def flow(spec, flat):
     return f
 
 
-def algorithms(spec):
-    """Every inverse the spec admits (tests/test_gpu_flow.py), AUTO first."""
+def plan_of(f, n, algo, fused=0):
+    """The plan of ``f``'s inverse of ``n`` rows with ``algo`` (csrc/inverse_plan.hip), or None where ``pmc_maf_inverse``
+    refuses the call."""
+    from pocomc_amd import _lib
+    p = _lib.pmc_inverse_plan_t()
+    return p if f.lib.pmc_maf_inverse_plan(C.byref(f._desc), n, algo, fused, C.byref(p)) == 0 else None
+
+
+def algorithms(f, n=64):
+    """Every inverse the plan admits for the flow ``f`` and a call of ``n`` rows, AUTO first: the candidates of
+    tests/test_gpu_flow.py that the plan does not refuse (the default-width flows at D = 102 keep AUTO and NAIVE, both the
+    lean D-pass kernel), and the workgroup sweep of the flow's family -- algorithm 10 / 11 -- where the plan gives it
+    ``PMC_SWEEP_WG`` / ``PMC_SWEEP_WG_NSF``."""
+    spec = f.spec
     if not spec.tri_ok:
-        return [0, 2]
-    if spec.univariate == "rqs":
-        return [0, 1, 2, 6, 7]
-    small = spec.nOT <= 8 and 2 * spec.Dp + 3 * spec.Hp + 176 <= 2560
-    return [0, 1, 2, 8] + ([6, 7] if small else [])
+        cand = [0, 2]
+    elif spec.univariate == "rqs":
+        cand = [0, 1, 2, 6, 7]
+    else:
+        small = spec.nOT <= 8 and 2 * spec.Dp + 3 * spec.Hp + 176 <= 2560
+        cand = [0, 1, 2, 8] + ([6, 7] if small else [])
+    out = [a for a in cand if plan_of(f, n, a) is not None]
+    wg, sweep = (WG_NSF, S_WG_NSF) if spec.univariate == "rqs" else (WG, S_WG)
+    p = plan_of(f, n, wg)
+    if p is not None and p.sweep == sweep:
+        out.append(wg)
+    return out
 
 
 def forward_inputs(spec, flat, data):
-    n = ROWS[spec.n_dim][0]
-    x = data[np.random.default_rng(11).choice(len(data), n, replace=False)]
-    parts = [x]
-    if spec.univariate == "rqs":
-        parts += [fr.knot_rows(spec, flat, x)[0], fr.all_knot_rows(spec, flat, x[:16])[0], fr.box_rows(spec, flat, x)[0]]
-    return np.ascontiguousarray(np.concatenate(parts), np.float32)
+    return fr.forward_inputs(spec, flat, data)
 
 
 def inverse_inputs(spec, flat, data, f):
-    n = ROWS[spec.n_dim][1]
-    rng = np.random.default_rng(12)
-    x = data[rng.choice(len(data), n // 2, replace=False)]
-    z = np.concatenate([f.forward(torch.from_numpy(x))[0].numpy(),                    # latent images of the flow's own rows
-                        (rng.normal(size=(n - n // 2, spec.n_dim)) * 1.2).astype(np.float32)])
-    parts = [z]
+    """(latent images: the device's forward map of the flow's own rows)"""
+    return fr.inverse_inputs(spec, flat, data, lambda x: f.forward(torch.from_numpy(x))[0].numpy())
+
+
+check = fr.check            # (the criterion with its float32 evaluations: tests/flow_regimes.py)
+
+
+def evaluations(spec, flat):
+    """The float32 evaluations ``check`` holds a kernel against: the numpy oracle, the kernels' spline formulas (spline
+    flows), the sequential dot products (a python loop per term: D <= 10 only)."""
+    ev = [OracleMAF(spec, flat)]
     if spec.univariate == "rqs":
-        parts += [fr.knot_rows(spec, flat, z, inverse=True)[0], fr.box_rows(spec, flat, z, inverse=True)[0]]
-    return np.ascontiguousarray(np.concatenate(parts), np.float32)
+        ev.append(fr.KernelSplineOracle(spec, flat))
+    if spec.n_dim <= 10:
+        ev.append(fr.SequentialOracle(spec, flat))
+    return ev
 
 
-def check(R, q, got, what, f32):
-    """The criterion on ``got``.  ``f32``: float32 evaluations of the same rows (numpy oracle first).  Where one of them
-    fails the row criterion, the quantity is ill-conditioned beyond the envelope on these rows (tests/test_flow_regimes_cpu.py:
-    BEYOND_F32), and WHICH rows a float32 evaluation misses depends on its order of additions (numpy and the sequential
-    oracle miss different rows of the affine x16 inverse by the same ~0.12).  There the kernel is held to be as good a
-    float32 evaluation as those: at most twice as many rows beyond ``C e_i`` as the worst of them, a worst error at most
-    twice theirs, and the median criterion on the rows every evaluation meets."""
-    lim = np.maximum(fr.bounds(R.spec)[q], fr.C * R.env[q])
-    bad = [R.ok & ~(R.err(q, v) <= lim) for v in f32]
-    beyond = np.logical_or.reduce(bad)
-    if not beyond.any():
-        s = R.check(q, got, what, f32=f32)
-    else:
-        held = np.flatnonzero(~beyond)
-        s = R.check(q, got, what, rows=held, f32=f32, raise_=False)
-        assert s["median_ratio"] <= s["median_bound"], (what, q, s)
-        err = R.err(q, got)
-        bad_k = R.ok & ~(err <= lim)
-        n_e = max(int(b.sum()) for b in bad)
-        worst_e = max(float(R.err(q, v)[b].max()) for v, b in zip(f32, bad) if b.any())
-        worst_k = float(err[bad_k].max()) if bad_k.any() else 0.0
-        key = f"{what.split(',')[0]} {q} rows beyond C e (kernel / float32)"
-        print(f"{what} {q}: beyond C e_i on {int(bad_k.sum())} rows (worst err {worst_k:.3g}); float32 evaluations: up to "
-              f"{n_e} rows (worst err {worst_e:.3g})")
-        parity.MEASURED[key] = max(parity.MEASURED.get(key, 0.0), float(bad_k.sum()))
-        assert bad_k.sum() <= 2 * n_e and worst_k <= 2 * worst_e, (what, q, int(bad_k.sum()), n_e, worst_k, worst_e)
-    print(f"{what} {q}: worst err/e {s['worst_ratio']:.3g}, median {s['median_ratio']:.3g} (bound {s['median_bound']:.3g}), "
-          f"worst err {s['worst']:.2e}, well-conditioned rows {s['worst_well']:.2e}")
+def _evaluated(ev, inp, direction):
+    if direction == "forward":
+        return [dict(zip(("z", "ladj"), e.forward(inp)), log_prob=e.log_prob(inp)) for e in ev]
+    return [dict(zip(("x", "ladj"), e.inverse(inp))) for e in ev]
+
+
+@functools.lru_cache(maxsize=None)
+def wide_reference(name, direction):
+    """(rows, Reference, float32 evaluations) of a default-width fixture, once per session (the float64 D-pass inverse of a
+    spline flow at D = 102 takes ~10 s of host time): its fixed rows do not pass through a kernel -- the latent images are
+    the float32 oracle's -- and the non-vacuity condition is asserted on them before any kernel is judged."""
+    spec, flat, data = fixture(name)
+    t0 = time.perf_counter()
+    inp = fr.forward_inputs(spec, flat, data) if direction == "forward" else fr.inverse_inputs(spec, flat, data, fr.oracle_latent(spec, flat))
+    R = fr.Reference(spec, flat, inp, direction, k=fr.n_perturb(spec))
+    shares = fr.assert_non_vacuous(R, name)
+    f32 = _evaluated(evaluations(spec, flat), inp, direction)
+    print(f"reference, {name} {direction}: {len(inp)} rows, {int(R.ok.sum())} counted, share with C e_i <= {fr.WELL:g}: "
+          + ", ".join(f"{q} {s:.3f}" for q, s in shares.items()) + f"; {time.perf_counter() - t0:.1f} s of host time")
+    return inp, R, f32
+
+
+def reference(name, direction, f):
+    if name in WIDE:
+        return wide_reference(name, direction)
+    spec, flat, data = fixture(name)
+    inp = forward_inputs(spec, flat, data) if direction == "forward" else inverse_inputs(spec, flat, data, f)
+    R = fr.Reference(spec, flat, inp, direction, k=fr.n_perturb(spec))
+    return inp, R, _evaluated(evaluations(spec, flat), inp, direction)
+
+
+def _assert_the_listed_sweeps(name, f, algos):
+    """What the plan admits, by name: the old fixtures list at least what they listed before and their family's workgroup
+    sweep; at D = 102 AUTO and NAIVE are the lean D-pass kernel and the workgroup sweep is the only triangular one; at
+    D = 128 (spline) AUTO is the lone-wave sweep.  And which regime of ``output_partials`` (csrc/maf_inverse_wg_nsf.hip) a
+    spline flow reaches: products of >= 16 K tiles, dealt by K range, need 17 hidden tiles."""
+    spec = f.spec
+    wg = WG_NSF if spec.univariate == "rqs" else WG
+    assert algos[0] == AUTO and wg in algos, (name, algos)
+    if name in LISTED_BEFORE:
+        assert set(LISTED_BEFORE[name]) <= set(algos), (name, algos)
+    if spec.n_dim == 102:
+        assert algos == [AUTO, NAIVE, wg], (name, algos)
+        assert plan_of(f, 64, AUTO).sweep == S_DPASS_LEAN and plan_of(f, 64, NAIVE).sweep == S_DPASS_LEAN
+    if name in ("nsf3-d128-g2", "nsf3-d86-g2"):
+        assert plan_of(f, 64, AUTO).sweep == S_NSF_SOLO and {NAIVE, WG_NSF} <= set(algos), (name, algos)
+    if spec.univariate == "rqs":
+        # 17 hidden tiles are needed for a product of 16 K tiles, and a tile of one or two degree groups for the split
+        split = fr.k_split_tiles(spec)
+        if spec.n_dim in (86, 102):
+            assert spec.nT >= 17 and split >= 16, (name, spec.nT, split)
+        if spec.n_dim == 10:
+            assert spec.nT < 17 and split == 0, (name, spec.nT, split)
+        if spec.n_dim == 128:
+            assert spec.nT >= 17 and split == 0, (name, spec.nT, split)          # (long products, none of them split)
 
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_forward_log_prob_and_every_inverse_meet_the_criterion(name, only_algo=None):
     spec, flat, data = fixture(name)
     f = flow(spec, flat)
-    o = OracleMAF(spec, flat)
-    k = fr.KernelSplineOracle(spec, flat) if spec.univariate == "rqs" else None
-    seq = fr.SequentialOracle(spec, flat) if spec.n_dim <= 10 else None          # (python loop per term: small flows only)
-    x = forward_inputs(spec, flat, data)
-    kp = min(fr.N_PERTURB, 4) if spec.n_dim >= 128 else fr.N_PERTURB          # (float64 D-pass cost at D = 128)
-    R = fr.Reference(spec, flat, x, "forward", k=kp)
+    x, R, f32 = reference(name, "forward", f)
     z, l = (t.numpy() for t in f.forward(torch.from_numpy(x)))
     lp = f.log_prob(torch.from_numpy(x)).numpy()
-    ev = [o] + [e for e in (k, seq) if e is not None]
-    f32 = [dict(zip(("z", "ladj"), e.forward(x)), log_prob=e.log_prob(x)) for e in ev]
     for q, v in (("z", z), ("ladj", l), ("log_prob", lp)):
-        check(R, q, v, f"forward, {name}", [d[q] for d in f32])
-    u = inverse_inputs(spec, flat, data, f)
-    R = fr.Reference(spec, flat, u, "inverse", k=kp)
-    f32 = [dict(zip(("x", "ladj"), e.inverse(u))) for e in ev]
-    for algo in algorithms(spec):
+        if (only_algo is None) != ((name, f"forward {q}") in OPEN_FINDINGS) and only_algo in (None, f"forward {q}"):
+            check(R, q, v, f"forward, {name}", [d[q] for d in f32])
+    algos = algorithms(f, ROWS[spec.n_dim][1])
+    _assert_the_listed_sweeps(name, f, algos)
+    if name in FORWARD_ONLY or isinstance(only_algo, str):
+        return
+    u, R, f32 = reference(name, "inverse", f)
+    assert algos == algorithms(f, len(u))
+    for algo in algos:
         if (only_algo is None) == ((name, algo) in OPEN_FINDINGS) or (only_algo is not None and algo != only_algo):
             continue
         f.inverse_algo = algo
@@ -179,11 +259,36 @@ def test_forward_log_prob_and_every_inverse_meet_the_criterion(name, only_algo=N
         check(R, "ladj", li, f"{fam}, {name}", [d["ladj"] for d in f32])
 
 
+@pytest.mark.parametrize("name", ["nsf3-d128-g2", "nsf3-d86-g2"])
+def test_the_two_spline_sweeps_agree_on_the_same_rows(name):
+    """The lone-wave spline sweep (AUTO) and the workgroup spline sweep on the same rows, at the two width classes where both
+    run: D = 128 (33 hidden tiles, every output product unsplit) and D = 86 (43 tiles, 27 of them with their products dealt
+    by K range and added by wavefront 0).  Each meets the criterion on the fixture's inverse rows; their distance from each
+    other, by the criterion's own row measure, is recorded -- a measurement with no bound of its own."""
+    spec, flat, _ = fixture(name)
+    f = flow(spec, flat)
+    u, R, f32 = wide_reference(name, "inverse")
+    assert plan_of(f, len(u), AUTO).sweep == S_NSF_SOLO and plan_of(f, len(u), WG_NSF).sweep == S_WG_NSF and spec.nT >= 17
+    assert (fr.k_split_tiles(spec) > 0) == (name == "nsf3-d86-g2")
+    got = {}
+    for algo in (AUTO, WG_NSF):
+        f.inverse_algo = algo
+        got[algo] = [t.numpy() for t in f.inverse(torch.from_numpy(u))]
+        for q, v in zip(("x", "ladj"), got[algo]):
+            check(R, q, v, f"two sweeps algorithm {algo}, {name}", [d[q] for d in f32])
+    f.inverse_algo = AUTO
+    dx = fr.row_err(got[WG_NSF][0], got[AUTO][0])[R.ok].max()
+    dl = fr.row_err(got[WG_NSF][1], got[AUTO][1], R.cancel["ladj"])[R.ok].max()
+    print(f"workgroup spline sweep vs lone-wave sweep, {name}: x {dx:.2e} ladj {dl:.2e} (row_err, {int(R.ok.sum())} rows)")
+    for key, v in ((f"workgroup vs lone-wave spline sweep x ({name})", dx), (f"workgroup vs lone-wave spline sweep ladj ({name})", dl)):
+        parity.MEASURED[key] = max(parity.MEASURED.get(key, 0.0), float(v))
+
+
 @pytest.mark.xfail(strict=True, reason="open finding: see OPEN_FINDINGS")
-@pytest.mark.parametrize("name,algo", sorted(OPEN_FINDINGS))
+@pytest.mark.parametrize("name,algo", sorted(OPEN_FINDINGS, key=lambda p: (p[0], str(p[1]).zfill(2))))
 def test_open_finding_the_criterion_on_the_listed_inverses(name, algo):
-    """The listed (flow, inverse algorithm) pairs fail the criterion today; strict: the test fails once they meet it, so
-    that the list stays true."""
+    """The listed (flow, inverse algorithm) pairs -- and (flow, "forward <quantity>") -- fail the criterion today; strict:
+    the test fails once they meet it, so that the list stays true."""
     test_forward_log_prob_and_every_inverse_meet_the_criterion(name, only_algo=algo)
 
 
@@ -200,27 +305,37 @@ def test_coordinates_outside_the_spline_box_come_back_bit_for_bit(name):
     z, l = (t.numpy() for t in f.forward(torch.from_numpy(x)))
     np.testing.assert_array_equal(z[out], x[out])
     np.testing.assert_array_equal(l[allout], 0.0)
-    for algo in algorithms(spec):
+    algos = algorithms(f, len(x))
+    assert WG_NSF in algos
+    for algo in ([] if name in FORWARD_ONLY else algos):
         f.inverse_algo = algo
         xi, li = (t.numpy() for t in f.inverse(torch.from_numpy(x)))
         np.testing.assert_array_equal(xi[out], x[out], err_msg=f"algorithm {algo}")
         np.testing.assert_array_equal(li[allout], 0.0, err_msg=f"algorithm {algo}")
 
 
-@pytest.mark.parametrize("name", ["maf3-d10-fit", "maf3-d32-fit", "nsf6-d10-fit", "nsf3-d32-fit", "maf6-d50-fit", "maf3-d10-g16"])
+@pytest.mark.parametrize("name", ["maf3-d10-fit", "maf3-d32-fit", "nsf6-d10-fit", "nsf3-d32-fit", "maf6-d50-fit", "maf3-d10-g16",
+                                  "maf3-d102-g2", "nsf3-d102-g2", "maf6-d102-fit"])
 @pytest.mark.parametrize("n", [64, 4096])
 def test_non_finite_rows_stay_in_their_rows(name, n):
     """NaN / +inf / -inf in one coordinate of rows 0, 15, 16, 17 and n-1: every other row is bit-identical to the same batch
-    with those rows finite, for the forward, log_prob, AUTO and every inverse (same n: AUTO picks its sweep by n)."""
+    with those rows finite, for the forward, log_prob, AUTO and every inverse (same n: AUTO picks its sweep by n).  At
+    D = 102 the D-pass inverses (AUTO, NAIVE: 103 passes of a 51-tile network, the 300 ms class at 4096 rows) run at n = 64
+    only; the forward and the workgroup sweep run at both."""
     spec, flat, data = fixture(name)
     f = flow(spec, flat)
+    algos = algorithms(f, n)
+    if spec.n_dim >= 102 and n > 64:
+        algos = [a for a in algos if plan_of(f, n, a).sweep not in DPASS_SWEEPS]
+        assert algos == [WG_NSF if spec.univariate == "rqs" else WG]
+    assert (WG_NSF if spec.univariate == "rqs" else WG) in algos
     good = data[np.random.default_rng(n).choice(len(data), n, replace=n > len(data))]
     f.inverse_algo = 0
     lat = f.forward(torch.from_numpy(good))[0].numpy()
     for what, base in (("forward", good), ("inverse", lat)):
         bad, rows = fr.with_nonfinite(base)
         keep = np.setdiff1d(np.arange(n), rows)
-        runs = [("forward", None), ("log_prob", None)] if what == "forward" else [("inverse", a) for a in algorithms(spec)]
+        runs = [("forward", None), ("log_prob", None)] if what == "forward" else [("inverse", a) for a in algos]
         for kind, algo in runs:
             res = []
             for inp in (base, bad):
@@ -254,16 +369,39 @@ def test_trainer_loss_and_gradient_per_block(name, n, weighted):
     oracle's knots for the LOSS; the gradient is taken on rows off the knots, because the loss is not differentiable in
     the spline's parameters there -- the two one-sided gradients differ (measured: 1e-2 of the block t0.b3) and which one
     a float32 evaluation returns depends on which side of its own rounded knot the input falls."""
+    _trainer_case(name, n, weighted)
+
+
+@pytest.mark.parametrize("name", ["maf3-d102-g2", "nsf3-d102-g2", "maf6-d102-fit", "nsf3-d102-fit", "maf3-d102-g16", "nsf3-d102-g4"])
+@pytest.mark.parametrize("n", [5, 100])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_trainer_loss_and_gradient_per_block_at_default_width(name, n, weighted):
+    """The same test with the same envelope rule on the default-width flows at D = 102 (51 hidden tiles: the wide
+    training instances), scaled up and trained.  The gain-16 / gain-4 flows are held on the loss only.  The rows are
+    drawn off the ReLU kinks: with 3 x 512 x T pre-activations a row, one of 5 rows of ``nsf3-d102-g2`` has a layer-1
+    pre-activation of -1.5e-7 (float64) that the float32 numpy oracle computes as +4.1e-7 -- the kernel and the twin took
+    different sides, and that unit's bias gradient differed by 2.4e-3 of its block while every other unit agreed to 4e-6."""
+    _trainer_case(name, n, weighted, gradient=name not in FORWARD_ONLY, off_kinks=True)
+
+
+def _trainer_case(name, n, weighted, gradient=True, off_kinks=False):
     spec, flat, data = fixture(name)
     f = flow(spec, flat)
     rng = np.random.default_rng(n + 31 * weighted)
-    x = np.ascontiguousarray(data[rng.choice(len(data), n, replace=False)], np.float32)
+    x = np.ascontiguousarray(data[rng.choice(len(data), 2 * n + 8 if off_kinks else n, replace=False)], np.float32)
+    if off_kinks:
+        # like the knots below: the rows of the gradient stay off the ReLU kinks (fr.relu_margin), where the loss is not
+        # differentiable in the parameters and the twin's error is no envelope of another float32 evaluation's
+        keep = fr.relu_margin(spec, flat, x) > fr.RELU_MARGIN
+        assert keep.sum() >= n, (name, n, int(keep.sum()))
+        print(f"trainer, {name} n={n} w={int(weighted)}: {int((~keep[: np.flatnonzero(keep)[n - 1] + 1]).sum())} drawn rows on a ReLU kink replaced")
+        x = np.ascontiguousarray(x[keep][:n])
     w = rng.uniform(0.1, 1.0, size=n).astype(np.float32) if weighted else None
-    batches = [(x, True)]
+    batches = [(x, gradient)]
     if spec.univariate == "rqs":
         batches.append((np.ascontiguousarray(np.concatenate([fr.knot_rows(spec, flat, x)[0][: max(n // 4, 1)], x])[:n]), False))
-    for xb, grad in batches:
-        _loss_and_gradient(spec, flat, f, xb, w, grad, f"trainer, {name} n={n} w={int(weighted)}{'' if grad else ' knots'}")
+    for i, (xb, grad) in enumerate(batches):
+        _loss_and_gradient(spec, flat, f, xb, w, grad, f"trainer, {name} n={n} w={int(weighted)}{' knots' if i else ''}")
 
 
 def _loss_and_gradient(spec, flat, f, x, w, grad, tag):
@@ -304,6 +442,12 @@ STEP_FAMILIES = {       # sweep family: fixture, case (tests/golden/cases.py: tp
     "lane (maf3, D=32, N=10000)": ("maf3-d32-fit", "tpcn_n10000_d32_corr"),
     "nsf2 (nsf6, D=10)": ("nsf6-d10-fit", "tpcn_n256_d10_nsf6"),
     "tri6 (maf6, D=50, N=10000)": ("maf6-d50-fit", "tpcn_n10000_d50_bimodal"),
+    # default width at D = 102, the flow inverting with its family's workgroup sweep (inverse algorithm 10 / 11; the step
+    # launches proposal, sweep and scaler one by one whatever PMC_NO_FUSE says): a case of 64 walkers that is in no table
+    "workgroup (maf6, D=102)": ("maf6-d102-fit", dict(kind="preconditioned_pcn", N=64, D=102, T=6, beta=0.5, nu=5.0, prior="uniform",
+                                                      target="bimodal", seed=23, n_max=2), WG),
+    "workgroup spline (nsf3, D=102)": ("nsf3-d102-fit", dict(kind="preconditioned_pcn", N=64, D=102, T=3, beta=1.0, nu=5.0, prior="normal",
+                                                             target="gauss", seed=24, n_max=2, flow="rqs"), WG_NSF),
 }
 
 
@@ -322,15 +466,22 @@ def test_one_teacher_forced_step_on_a_trained_flow(family, no_fuse, monkeypatch)
     from pocomc_amd.mcmc import StepEngine
     import cases
     monkeypatch.setenv("PMC_NO_FUSE", no_fuse)
-    fx, name = STEP_FAMILIES[family]
+    fx, name, *algo = STEP_FAMILIES[family]
     spec, flat, _ = fixture(fx)
     monkeypatch.setattr(cases, "flow_params", lambda s, seed, gain=1.2: flat)
-    c = cases.find_case(name)
+    c = name if isinstance(name, dict) else cases.find_case(name)
+    name = family if isinstance(name, dict) else name                # (a case of its own: the name is a label)
     N, D = c["N"], c["D"]
-    state, funcs, opts, aux = cases.build_case(name, Reparameterize)
+    state, funcs, opts, aux = cases.build_case(name, Reparameterize, case=c)
     assert (aux["spec"].n_dim, aux["spec"].n_transforms, aux["spec"].univariate) == (spec.n_dim, spec.n_transforms, spec.univariate)
     f = flow(spec, flat)
-    ostate, ofuncs, oopts, _ = cases.build_case(name, OracleScaler)
+    if algo:
+        # the engine's sweep: the workgroup sweep of the flow's family, and no fused proposal + inverse instance
+        f.inverse_algo = algo[0]
+        plain, fused = plan_of(f, N, algo[0]), plan_of(f, N, algo[0], fused=1)
+        assert plain.sweep == {WG: S_WG, WG_NSF: S_WG_NSF}[algo[0]] and plain.fused == 0
+        assert fused is not None and fused.sweep == 0 and fused.fused == 0
+    ostate, ofuncs, oopts, _ = cases.build_case(name, OracleScaler, case=c)
     omaf = OracleMAF(spec, flat)
     geo = funcs["theta_geometry"]
     nu, sigma, mu = float(geo.t_nu), min(float(opts["proposal_scale"]), 0.99), np.array(geo.t_mean, float)
@@ -343,8 +494,12 @@ def test_one_teacher_forced_step_on_a_trained_flow(family, no_fuse, monkeypatch)
     sub = np.arange(N)[:: max(1, N // ROWS[D][1])][: ROWS[D][1]]
     # theta = forward(u): the device's, under the criterion; then both steps start from the float32 oracle's
     th0, l0 = omcmc.flow_numpy_wrapper(TorchFlowAdapter(omaf)).forward(state["u"])
-    R = fr.Reference(spec, flat, state["u"][sub].astype(np.float32), "forward")
-    check(R, "z", eng.theta32.cpu().numpy()[sub], f"step theta = forward(u), {family}", [th0[sub]])
+    R = fr.Reference(spec, flat, state["u"][sub].astype(np.float32), "forward", k=fr.n_perturb(spec))
+    # (the float32 evaluations: the numpy oracle; the new families' spline flow: and the kernels' spline formulas, as in
+    #  the criterion test -- on these 16 rows the forward kernel's median err/e is 4.0, the formulas' 3.6, numpy's 2.9)
+    model = fr.KernelSplineOracle(spec, flat) if algo and spec.univariate == "rqs" else None
+    extra = [] if model is None else [model.forward(state["u"][sub].astype(np.float32))[0]]
+    check(R, "z", eng.theta32.cpu().numpy()[sub], f"step theta = forward(u), {family}", [th0[sub]] + extra)
     eng.theta32.copy_(torch.from_numpy(th0.astype(np.float32)))
     eng.ldjf.copy_(torch.from_numpy(l0.astype(np.float32)))
     eng.propose(sigma, nu, rec)
@@ -361,10 +516,11 @@ def test_one_teacher_forced_step_on_a_trained_flow(family, no_fuse, monkeypatch)
     tr = trace[0]
     parity.close_rel(p_theta, tr["theta_prime"], 2e-7, f"step theta', {family}")
     t32 = p_theta[sub].astype(np.float32)
-    R = fr.Reference(spec, flat, t32, "inverse")
+    R = fr.Reference(spec, flat, t32, "inverse", k=fr.n_perturb(spec))
     ev = omaf.inverse(t32)
-    check(R, "x", p_u[sub], f"step u' = inverse(theta'), {family}", [ev[0]])
-    check(R, "ladj", p_ldjf[sub], f"step u' = inverse(theta'), {family}", [ev[1]])
+    evk = ([], []) if model is None else tuple([v] for v in model.inverse(t32))
+    check(R, "x", p_u[sub], f"step u' = inverse(theta'), {family}", [ev[0]] + evk[0])
+    check(R, "ladj", p_ldjf[sub], f"step u' = inverse(theta'), {family}", [ev[1]] + evk[1])
     parity.close_rel(eng.p_x.cpu().numpy(), tr["x_prime"], fr.AFFINE_BOUND["x"], f"step x', {family}")
     parity.close_rel(eng.p_logdetj.cpu().numpy(), tr["logdetj_prime"], fr.AFFINE_BOUND["ladj"], f"step scaler logdetj', {family}",
                      cancel=1.0 + np.sum(np.where(np.isfinite(p_u), p_u, 0.0) ** 2, axis=1))

@@ -8,7 +8,14 @@ Against the oracle's D-pass inverse with the measures and the tolerances the sui
 more than one round of workgroups and against the lone-wave spline sweep; what it writes and that it writes the same bits
 twice; that a non-finite row leaves every other row's bits alone (the kernel's control flow reads no data, the spline's bin
 is picked by selects); outside the spline box; the regime criterion of ``tests/test_gpu_flow_regimes.py``; inside the MCMC
-step; through ``Flow``, a pickle and a ``Sampler`` run."""
+step; through ``Flow``, a pickle and a ``Sampler`` run.
+
+The regime test of this file runs at D = 10 (2-3 hidden tiles: products that are never split by K range).  The split
+products -- 16 K tiles and more, the partials added by wavefront 0 -- meet the criterion in
+``tests/test_gpu_flow_regimes.py``, whose ``algorithms`` lists algorithm 11 for every spline fixture the plan gives this
+sweep: scaled-up and trained flows at D = 102 (51 hidden tiles, 35 of them split; it is the only triangular sweep there),
+D = 86 (43 tiles, 27 split, on the same rows as the lone-wave sweep) and D = 128 (33 tiles of three or four degree groups:
+long products, none split), with the non-finite rows, the rows outside the box and one teacher-forced step."""
 import ctypes as C
 import functools
 import pickle

@@ -5,7 +5,12 @@ and so fits the default-width flows at n_dim 92 - 114, which AUTO hands to the D
 Against the oracle's D-pass inverse with the measures and the tolerance ``tests/test_gpu_wide_default_flows.py`` holds AUTO
 to; against the device's own D-pass at more than one round of workgroups; what it writes and that it writes the same bits
 twice; that a row of NaN leaves every other row's bits alone (the kernel's control flow reads no data); inside the MCMC
-step; through ``Flow``, a pickle and a ``Sampler`` run."""
+step; through ``Flow``, a pickle and a ``Sampler`` run.
+
+Every flow here is default-initialised (``cases.flow_params``).  The sweep on trained and scaled-up flows -- the regime
+criterion, the non-finite rows at 64 and 4096 rows, one teacher-forced step -- is in ``tests/test_gpu_flow_regimes.py``:
+``algorithms`` lists algorithm 10 for every affine fixture the plan gives this sweep, from D = 10 to the default-width
+flows at D = 102 (51 hidden tiles), where it is the only triangular sweep."""
 import ctypes as C
 import functools
 import pickle
