@@ -1,42 +1,17 @@
-// Triangular-sweep MAF inverse for the affine flows, a WORKGROUP of eight wavefronts per 16 rows, right-looking, with two
-// hidden-width arrays in LDS (PMC_INVERSE_TRIANGULAR_WG -> PMC_SWEEP_WG; an opt-in, AUTO never takes it).
+// Workgroup inverse sweep of the affine flows (PMC_INVERSE_TRIANGULAR_WG -> PMC_SWEEP_WG; an opt-in, AUTO never takes it).
+// The skeleton, the LDS arrays it works on and the synchronisation contract are in maf_wg_sweep.h: read that first.  Here:
+// the kernel, its LDS carve-up and its output stage, which is RIGHT-looking like the hidden layers --
 //
-// The lane-per-walker sweep keeps three hidden-width activation arrays per walker subset; at the default width they exceed
-// 160 KiB of LDS for n_dim 92-114 (51 hidden tiles at D = 102), and those flows fell to the D-pass algorithm: D + 1 full
-// passes of the hyper-network per transform.  This sweep keeps no activation array at all.  Units are sorted by degree and
-// hidden tile T reads tiles <= T only, so once tile J is final its whole contribution to every later tile can be added at
-// once -- what stays in LDS is the PARTIAL pre-activation of every unit:
+//   Oacc   [nOT 16][16]   b3 + sum_{K<J} W3[., K] h2[K]          (shift, raw log-scale) rows, behind X | Y | H1acc | H2acc
 //
-//   X, Y   [Dp][16]       x found so far by rank (zeros where unknown), the transform's input by rank
-//   H1acc  [Hp][16]       b1 + sum_{K<J} W1[., K] h0[K]
-//   H2acc  [Hp][16]       b2 + sum_{K<J} W2[., K] h1[K]
-//   Oacc   [nOT 16][16]   b3 + sum_{K<J} W3[., K] h2[K]          (shift, raw log-scale) rows
-//   HT     3 x [16][16]   h0 | h1 | h2 of the current hidden tile J;   RED [NW][16] log-determinant words
-//
-// all in the 16-row MFMA operand layout of maf_common.h (lidx / store_rows), which is also how an accumulator tile is
-// read back (rows_of).  Layer 0 has no array: h0[J] = relu(b0 + W0[J, :] X) is formed when tile J is reached (<= 10 K tiles).
-//
-// Per transform (last to first), per hidden tile J:
-//   DIAGONAL phase, wavefront 0: one mini-pass per distinct degree g of the tile (the quad meta words), each
-//       h0[J] (the product over X once per tile; every later mini-pass adds the one rank the last one found, from w0n),
-//       h1[J] = relu(H1acc[J] + W1[J, J] h0[J] + h0[J]),  h2[J] likewise,
-//       (shift, raw) of rank g = Oacc rows + W3[rows, J] h2[J],  x = (y - shift) / exp(soft_ls(raw)),  ladj -= soft_ls(raw).
-//     Masked weights are exact zeros: the units of a higher degree in the tile are finite garbage until their own
-//     mini-pass and enter as 0 * finite.  A dependent chain of one wavefront's LDS round trips and MFMAs; the other
-//     seven wait at the barrier.
-//   UPDATE phase, all wavefronts: H1acc[T] += W1[T, J] h0[J], H2acc[T] += W2[T, J] h1[J] for the tiles T > J and
-//     Oacc[O] += W3[O, J] h2[J] for the output tiles with a rank still to come, dealt by T mod NW / O mod NW (every
-//     accumulator tile has one owner).
-//
-// SYNCHRONISATION: lds_barrier() and nothing else.  Every wavefront reaches every barrier: no early return (rows past n
-// are zeros on the way in and masked on the way out), every loop bound and every branch around a barrier comes from
-// the descriptor and the meta words, none from a value computed from z.
-#include "maf_wg.h"
-#include "inverse_lds.h"
+//   DIAGONAL phase, after a mini-pass's hidden chain: (shift, raw) of rank g = Oacc rows + W3[rows, J] h2[J] from ONE
+//     output tile, x = (y - shift) / exp(soft_ls(raw)),  ladj -= soft_ls(raw).
+//   UPDATE phase: Oacc[O] += W3[O, J] h2[J] for the output tiles with a rank still to come, dealt by O mod NW.  The
+//     fragments of a wavefront's first WGS_NUO output tiles are requested with those of its hidden update.
+#include "maf_wg_sweep.h"
 
-#define WGS_PX 8                   // x tiles whose layer-0 fragments wavefront 0 requests one tile ahead (D <= 128; beyond: in place)
-#define WGS_NU 7                   // hidden tiles / output tiles of a wavefront's update whose fragments are requested before the
-#define WGS_NUO 3                  // diagonal phase (flows of <= 57 hidden tiles, D <= 192; beyond: in place)
+#define WGS_NUO 3                  // output tiles of a wavefront's update whose fragments are requested before the diagonal
+                                   // phase (D <= 192; beyond: in place)
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_sweep_kernel(pmc_maf_t m, const float* __restrict__ in,

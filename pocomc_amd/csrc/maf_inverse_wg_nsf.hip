@@ -1,47 +1,29 @@
-// Triangular-sweep inverse of the 8-bin spline flows, a WORKGROUP of eight wavefronts per 16 rows, with two hidden-width
-// arrays in LDS (PMC_INVERSE_TRIANGULAR_WG_NSF -> PMC_SWEEP_WG_NSF; an opt-in, AUTO never takes it).
+// Workgroup inverse sweep of the 8-bin spline flows (PMC_INVERSE_TRIANGULAR_WG_NSF -> PMC_SWEEP_WG_NSF; an opt-in, AUTO
+// never takes it).  The skeleton, the LDS arrays it works on and the synchronisation contract are in maf_wg_sweep.h: read
+// that first.  Here: the kernel, its LDS carve-up and its output stage.  A spline rank has 23 output rows: right-looking
+// output accumulators for every rank (the affine kernel's Oacc) would be 161 tiles at D = 102, more than the whole LDS.
+// The output stage is therefore LEFT-looking, over the per-rank image parts f3i [rank][half][ktile][lane][4] and b3i
+// [rank][32] that the other spline sweeps read:
 //
-// The lone-wave spline sweep (maf_inverse_tri_nsf.hip) keeps three hidden-width activation arrays; at the default width
-// they exceed 160 KiB of LDS for n_dim 97-108, and those flows fell to the D-pass algorithm.  This is the workgroup sweep of
-// the affine flows (maf_inverse_wg.hip: read its header first, the skeleton and the invariants are the same) with another
-// output stage.  A spline rank has 23 output rows: right-looking output accumulators for every rank would be 161 tiles at
-// D = 102, more than the whole LDS.  The output stage is therefore LEFT-looking, over the per-rank image parts f3i
-// [rank][half][ktile][lane][4] and b3i [rank][32] that the other spline sweeps read:
-//
-//   X, Y   [Dp][16]       x found so far by rank (zeros where unknown), the transform's input by rank
-//   H1acc  [Hp][16]       b1 + sum_{K<J} W1[., K] h0[K]
-//   H2     [Hp][16]       tiles > J: b2 + sum_{K<J} W2[., K] h1[K];  tiles <= J: the FINAL h2, written over the slot when the
+//   H2     [Hp][16]       tiles > J: the skeleton's partial;  tiles <= J: the FINAL h2, written over the slot when the
 //                         tile's diagonal phase is over (the partial is dead by then)
-//   HT     3 x [16][16]   h0 | h1 | h2 of the current hidden tile J
 //   OP     [NW][16][16]   output partials of the NEXT tile's degree groups, one tile per wavefront (below)
-//   PAR [16][32], TAB [16][24]   the rank's 23 parameters and its knot tables (rqs_inverse_coop);  RED [NW][16]
+//   PAR [16][32], TAB [16][24]   the rank's 23 parameters and its knot tables (rqs_inverse_coop)
 //
-// all hidden and output tiles in the 16-row MFMA operand layout (lidx / store_rows / rows_of).
-//
-// Per transform (last to first), per live hidden tile J:
-//   DIAGONAL phase, wavefront 0: one mini-pass per distinct degree g of the tile, each the hidden chain of the affine kernel
-//       (h0[J] from X once per tile, then one column of W0 per rank found; h1[J], h2[J] from the partials and the diagonal
-//       fragments), then the rank's two output tiles = its OP tiles, added in slot order, + f3i[g][half][J] h2[J], exchanged
-//       through PAR, solved by rqs_inverse_coop: X[g] = x, ladj -= l.  Before the barrier h2[J] goes into H2's slot J.
-//   UPDATE phase, all wavefronts: H1acc[T] += W1[T, J] h0[J], H2[T] += W2[T, J] h1[J] for the tiles T > J (T mod NW), and
-//       the output partials of tile J + 1's groups: b3i[g] + sum_{K<=J} f3i[g][half][K] H2[K].  A tile has 1-4 groups, so
-//       2-8 (group, half) products of J + 1 fragment products each; they are dealt over the eight wavefronts by (group,
-//       half) and, for tiles of one or two groups and products of >= WGN_KSPLIT_MIN K tiles, by four or two K ranges.
-//       Every wavefront writes its own OP tile (the first K range carries the bias); wavefront 0 adds the ranges in K
-//       order: no atomics, the same bits every call.
+//   DIAGONAL phase, after a mini-pass's hidden chain: the rank's two output tiles = its OP tiles, added in slot order,
+//       + f3i[g][half][J] h2[J], exchanged through PAR, solved by rqs_inverse_coop: X[g] = x, ladj -= l.  Before the barrier
+//       h2[J] goes into H2's slot J.
+//   UPDATE phase, after the hidden update: the output partials of tile J + 1's groups, b3i[g] + sum_{K<=J} f3i[g][half][K]
+//       H2[K].  A tile has 1-4 groups, so 2-8 (group, half) products of J + 1 fragment products each; they are dealt over
+//       the eight wavefronts by (group, half) and, for tiles of one or two groups and products of >= WGN_KSPLIT_MIN K tiles,
+//       by four or two K ranges.  Every wavefront writes its own OP tile (the first K range carries the bias); wavefront 0
+//       adds the ranges in K order: no atomics, the same bits every call.
 //   The partials of tile 0's groups (bias only) are formed before the transform's first barrier.
 //
-// SYNCHRONISATION: lds_barrier() and nothing else.  Every wavefront reaches every barrier: no early return (rows past n
-// are zeros on the way in and masked on the way out), every loop bound and every branch around a barrier comes from
-// the descriptor and the meta words, none from a value computed from z.  The spline's bin is picked by selects and indexes
-// the row's own PAR / TAB words only (rqs.h).
-#include "maf_wg.h"
-#include "inverse_lds.h"
+// The contract's "no bound or branch from a value computed from z" holds in the solve too: the spline's bin is picked by
+// selects and indexes the row's own PAR / TAB words only (rqs.h).
+#include "maf_wg_sweep.h"
 #include "rqs.h"
-
-#define WGN_PX 8                   // x tiles whose layer-0 fragments wavefront 0 requests one tile ahead (D <= 128; beyond: in place)
-#define WGN_NU 7                   // hidden tiles of a wavefront's update whose fragments are requested before the diagonal phase
-                                   // (flows of <= 57 hidden tiles; beyond: in place)
 
 #define WGN_KSPLIT_MIN 16          // K tiles of a (group, half) product from which it is dealt by K range as well: below, the
                                    // product is no longer than the wavefront's hidden update next to it, and unsplit it adds in
@@ -185,9 +167,9 @@ __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_nsf_sweep_kernel(pmc_m
         // fragments and bias of tile J + 1 are requested while tile J runs, and every wavefront requests the fragments of its
         // hidden update of tile J before the diagonal phase, which it spends waiting at the barrier anyway
         const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 nfr1 = zero4, nfr2 = zero4, nb0 = zero4, pf0[WGN_PX];
+        float4 nfr1 = zero4, nfr2 = zero4, nb0 = zero4, pf0[WGS_PX];
 #pragma unroll
-        for (int k = 0; k < WGN_PX; ++k) pf0[k] = zero4;
+        for (int k = 0; k < WGS_PX; ++k) pf0[k] = zero4;
         // per group of the tile: the diagonal fragments of its two output tiles, and the column of W0 of the rank it finds
         float4 fo0[4], fo1[4], col[4];
 #pragma unroll
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_nsf_sweep_kernel(pmc_m
             nfr1 = w.f1[lane]; nfr2 = w.f2[lane];
             nb0 = *reinterpret_cast<const float4*>(w.b0 + 4 * q);
 #pragma unroll
-            for (int k = 0; k < WGN_PX; ++k) pf0[k] = w.f0[(size_t)min(k, nXT - 1) * 64 + lane];
+            for (int k = 0; k < WGS_PX; ++k) pf0[k] = w.f0[(size_t)min(k, nXT - 1) * 64 + lane];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int gi = dgn[i] < D ? dgn[i] : 0;
@@ -216,9 +198,9 @@ __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_nsf_sweep_kernel(pmc_m
 
             // ---- the hidden update's fragments: tiles T > J with T mod NW == wv
             const int Tf = J + 1 + ((wv - (J + 1)) & (NW - 1));
-            float4 U1[WGN_NU], U2[WGN_NU];
+            float4 U1[WGS_NU], U2[WGS_NU];
 #pragma unroll
-            for (int k = 0; k < WGN_NU; ++k) {
+            for (int k = 0; k < WGS_NU; ++k) {
                 const size_t at = ((size_t)min(Tf + k * NW, nT - 1) * nT + J) * 64 + lane;
                 U1[k] = w.f1[at];
                 U2[k] = w.f2[at];
@@ -229,17 +211,17 @@ __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_nsf_sweep_kernel(pmc_m
                 const f32x4 p1 = rows_of(H1acc, J, q, p), p2 = rows_of(H2, J, q, p);
                 f32x4 a0 = {nb0.x, nb0.y, nb0.z, nb0.w}, a0b = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int k = 0; k < WGN_PX; ++k) {
+                for (int k = 0; k < WGS_PX; ++k) {
                     if (k < nXT) {
                         if (k & 1) a0b = frag_mac(a0b, pf0[k], X + (k << 8), lane);
                         else a0 = frag_mac(a0, pf0[k], X + (k << 8), lane);
                     }
                 }
                 a0 += a0b;
-                a0 = mac_range<4>(a0, w.f0 + (size_t)J * nXT * 64, X, WGN_PX, nXT, lane);
+                a0 = mac_range<4>(a0, w.f0 + (size_t)J * nXT * 64, X, WGS_PX, nXT, lane);
                 nb0 = *reinterpret_cast<const float4*>(w.b0 + 16 * Jn + 4 * q);
 #pragma unroll
-                for (int k = 0; k < WGN_PX; ++k) pf0[k] = w.f0[((size_t)Jn * nXT + min(k, nXT - 1)) * 64 + lane];
+                for (int k = 0; k < WGS_PX; ++k) pf0[k] = w.f0[((size_t)Jn * nXT + min(k, nXT - 1)) * 64 + lane];
                 int g_prev = -1, slot = 0;               // slot: the group's first OP tile
                 float4 c_prev = zero4;
                 f32x4 h2 = {0.f, 0.f, 0.f, 0.f};
@@ -298,7 +280,7 @@ __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_nsf_sweep_kernel(pmc_m
 
             // ---- update phase: tile J is final
 #pragma unroll
-            for (int k = 0; k < WGN_NU; ++k) {
+            for (int k = 0; k < WGS_NU; ++k) {
                 const int Tt = Tf + k * NW;
                 if (Tt < nTl) {
                     f32x4 a1 = rows_of(H1acc, Tt, q, p), a2 = rows_of(H2, Tt, q, p);
@@ -308,7 +290,7 @@ __global__ __launch_bounds__(64 * NW) void maf_inverse_wg_nsf_sweep_kernel(pmc_m
                     store_rows(H2, Tt, q, p, a2);
                 }
             }
-            for (int Tt = Tf + WGN_NU * NW; Tt < nTl; Tt += NW) {            // (flows of more than 8 WGN_NU + 1 hidden tiles)
+            for (int Tt = Tf + WGS_NU * NW; Tt < nTl; Tt += NW) {            // (flows of more than 8 WGS_NU + 1 hidden tiles)
                 const size_t at = ((size_t)Tt * nT + J) * 64 + lane;
                 f32x4 a1 = rows_of(H1acc, Tt, q, p), a2 = rows_of(H2, Tt, q, p);
                 a1 = frag_mac(a1, w.f1[at], HT0, lane);

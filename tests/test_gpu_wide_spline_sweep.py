@@ -40,10 +40,15 @@ S_WG_NSF = 10
 NSF_INV, NSF_LADJ = 5e-5, 1e-4                           # tests/test_gpu_flow.py
 SHAPES = {f"D{D}": (D, None) for D in (3, 10, 17, 33, 65, 86, 97, 102, 108, 128, 157)}
 SHAPES.update({"D10-nsf3": (10, "nsf3"), "D32-nsf6": (32, "nsf6")})
+# beyond the fragments held in registers, where the kernel loads in place: 64 live hidden tiles (the hidden update past
+# 8 * 7 + 1 tiles)
+SHAPES.update({"D65-H1024": (65, MAFSpec(65, 2, hidden=1024, univariate="rqs"))})
 
 
 def _spec(name):
     D, chain = SHAPES[name]
+    if isinstance(chain, MAFSpec):
+        return chain
     return spec_by_name(D, chain) if chain else MAFSpec(D, 2, univariate="rqs")
 
 

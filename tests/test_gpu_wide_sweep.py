@@ -32,10 +32,15 @@ WG, NAIVE = 10, 2
 S_WG = 9
 SHAPES = {f"D{D}": (D, None) for D in (3, 10, 17, 33, 65, 92, 102, 114, 128, 157)}
 SHAPES.update({"D10-maf3": (10, "maf3"), "D32-maf6": (32, "maf6")})
+# beyond the fragments held in registers, where the kernel loads in place: 64 live hidden tiles (the hidden update past
+# 8 * 7 + 1 tiles), and 25 output tiles over 13 x tiles (the output update past 3 * 8 tiles, layer 0 past 8 x tiles)
+SHAPES.update({"D65-H1024": (65, MAFSpec(65, 2, hidden=1024)), "D193-H208": (193, MAFSpec(193, 2, hidden=208))})
 
 
 def _spec(name):
     D, chain = SHAPES[name]
+    if isinstance(chain, MAFSpec):
+        return chain
     return spec_by_name(D, chain) if chain else MAFSpec(D, 2)
 
 
