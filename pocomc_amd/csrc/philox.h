@@ -18,6 +18,9 @@ struct Philox {
     uint32_t key[2];
     uint32_t ctr[4];
 
+    // The layout is a promise ("RNG"): a seeded run and a resumed checkpoint continue identically across
+    // builds.  tests/philox_model.py states it independently and tests/test_gpu_philox_model.py holds every stream to it.
+    // streams: 0 gamma scale, 1 normal noise, 2 accept uniform, 3 bootstrap (pool.hip), 4 fit noise (maf_train.hip)
     __device__ __forceinline__ Philox(uint64_t seed, uint64_t step, uint64_t particle, uint32_t stream) {
         key[0] = (uint32_t)seed;
         key[1] = (uint32_t)(seed >> 32);
@@ -42,7 +45,10 @@ struct Philox {
         ++ctr[0];
     }
 
-    // two uniforms in (0,1) with 53 random bits each
+    // two uniforms in [2^-54, 1] from 53 random bits each: k + 0.5 (k = x >> 11) is exact below 2^52 and rounds to even
+    // from there on, so above 1/2 two values of k share a result and k = 2^53 - 1 gives exactly 1.0 (probability 2^-53).
+    // Every consumer tolerates 1.0: log(1.0) = 0 is finite (a Box-Muller pair (0, 0), an ordinary gamma candidate),
+    // the bootstrap clamps i >= n to n - 1, and u < alpha with alpha <= 1 merely rejects.  (tests/philox_model.py)
     __device__ __forceinline__ void uniform2(double& a, double& b) {
         uint32_t r[4];
         next4(r);

@@ -9,6 +9,10 @@ moments, and independence between seeds / steps / walkers / variate families.
 ``pmc_rng_fill`` writes exactly the variates the kernels draw inline for the same (seed, step, offset)
 (``test_gpu_mcmc.py::test_variates_drawn_ahead_equal_inline_draws``), so these are the kernels' numbers.
 Everything is deterministic (fixed seeds): the KS thresholds are p > 1e-3 for every one of the fixed draws.
+
+The laws are pinned here; the VALUES -- which number a (seed, step, walker, stream, draw) yields: the cipher, the
+counter layout, the conversions -- are pinned by the host model ``tests/philox_model.py``
+(``tests/test_philox_model_cpu.py``, ``tests/test_gpu_philox_model.py``).
 """
 import ctypes as C
 
