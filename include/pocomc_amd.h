@@ -1007,6 +1007,44 @@ int pmc_flow_prior_pre(const pmc_scaler_t* s, const double* x, int64_t row_strid
 int pmc_flow_prior_post(const float* lp32, const double* ldj, const int32_t* inside, double* logp, int64_t n,
                         void* stream);
 
+/* ----------------------------------------------------------------- joint prior */
+
+/* A flow prior on Df columns of x and a table of scipy factors on the other Dr (pocomc_amd.JointPrior), D = Df + Dr:
+ *   log p(x) = [flow.log_prob(u(x_F)) - log|dx_F/du|] + sum_m dist_m.logpdf(x[rest_cols[m]]),  u = Reparameterize.forward(x_F),
+ *   x_F[k] = x[flow_cols[k]],
+ * as two launches around the flow's own forward call, like the flow prior's.
+ *
+ * pmc_joint_prior_pre: pmc_flow_prior_pre on the flow block's columns and pmc_prior_logpdf on the others, in ONE launch that
+ * reads the tile of x once.  s: the flow block's scaler (s->D = Df features; s->bc is not read).  rest: the table of the
+ * other factors (rest->D = Dr).  flow_cols int32 [Df], rest_cols int32 [Dr], device memory: the column of x that is flow
+ * feature k / rest factor m; together a permutation of 0 .. D - 1.  The entry does not read them (device memory: the caller
+ * checks their content, JointPrior.layout); the kernel does not follow an entry outside [0, D): every row of the call's
+ * blocks then gets inside = 0.
+ * x: f64, element (r, j) at x[r * row_stride + j * col_stride], j < D, with the two coalesced layouts (D, 1) and (1, n) of
+ * pmc_flow_prior_pre; other strides are read correctly, slowly.
+ * u32 f32 [n][Df], ldj f64 [n]: what pmc_flow_prior_pre writes for the gathered C-contiguous flow columns, bit for bit
+ * (the same element routine, the Jacobian terms added k = 0, 1, ..., Df - 1 by one lane).
+ * rest_logp f64 [n]: lp = 0.0; lp += term_m, m = 0, 1, ..., Dr - 1 -- the bits of pmc_prior_logpdf on the gathered rest
+ * columns.  Outside a factor's support its term, and so the sum, is -inf; at a pole of a family the sum may be +inf
+ * (pmc_joint_prior_post maps it).
+ * inside int32 [n]: 1 iff every x_j of the row (flow and rest) is finite, every flow column passes pmc_flow_prior_pre's test
+ * (strictly inside the scaler's bounds, a finite float32 u) and no rest term is NaN.  A rest factor's own support is not
+ * part of it.  A row with inside == 0 is written as zeros to u32 and as -inf to rest_logp.
+ * A row's bits depend on its values alone -- not on the layout, on n or on the row's place in the call.
+ * Refused before anything is launched or written, each with a text of its own: a NULL pointer or a negative count or
+ * stride; Df < 2; Dr < 1; Df + Dr > 157 ("n_dim too large"; a block keeps 64 rows of x and of u32 in LDS:
+ * 64 * ((D | 1) * 8 + Df * 4) + 256 + 4 D bytes); rest->n_extended > 0 without rest->par; s->scale without mu / sigma; more
+ * than 2^31 - 1 blocks of 64 rows.  n == 0 returns 0. */
+int pmc_joint_prior_pre(const pmc_scaler_t* s, const int32_t* flow_cols, const pmc_prior_t* rest, const int32_t* rest_cols,
+                        const double* x, int64_t row_stride, int64_t col_stride, int64_t n, float* u32, double* ldj,
+                        double* rest_logp, int32_t* inside, void* stream);
+
+/* v = ((double)lp32[r] - ldj[r]) + rest_logp[r], in this order; logp[r] = v where inside[r] and v is finite, -inf everywhere
+ * else: never NaN, never +inf (a pole of a table family, such as gamma(a < 1) at its loc, is -inf).  lp32 f32 [n] (the
+ * flow's log_prob of u32), ldj, rest_logp f64 [n], inside int32 [n], logp f64 [n]. */
+int pmc_joint_prior_post(const float* lp32, const double* ldj, const double* rest_logp, const int32_t* inside, double* logp,
+                         int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,8 @@ SIGNATURES = {
     "pmc_resample_systematic": (C.c_int, [c_p, i64, f64, i64, c_p, c_p, c_p]),
     "pmc_flow_prior_pre": (C.c_int, [P(pmc_scaler_t), c_p, i64, i64, i64, c_p, c_p, c_p, c_p]),
     "pmc_flow_prior_post": (C.c_int, [c_p, c_p, c_p, c_p, i64, c_p]),
+    "pmc_joint_prior_pre": (C.c_int, [P(pmc_scaler_t), c_p, P(pmc_prior_t), c_p, c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p]),
+    "pmc_joint_prior_post": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, c_p]),
 }
 
 _lib = None

@@ -3,41 +3,10 @@
 // Two launches around the flow's own forward kernel: flow_prior_pre_kernel maps the rows (u as float32 for the flow, the
 // scaler's log-determinant, the support test), flow_prior_post_kernel joins the flow's float32 log-density with them.
 #include "pmc_internal.h"
-#include "scaler_body.h"
-
-#define FP_ROWS 64
-#define FP_THREADS 512
-#define FP_MAX_D 157                              // the widest MCMC step
+#include "flow_prior_body.h"
 
 static inline size_t flow_prior_lds_bytes(int D) {
     return (size_t)FP_ROWS * (D | 1) * sizeof(double) + (size_t)FP_ROWS * D * sizeof(float) + FP_ROWS * sizeof(int);
-}
-
-// The elements of one thread: feature j of the rows r0, r0 + rpp, ...; KIND / LOGIT: the feature's kind and the transform,
-// as constants.  x in T is replaced by the Jacobian term, u goes to U as float32, a row with an element outside the
-// support is marked in rowin.
-template <int KIND, int LOGIT>
-__device__ __forceinline__ void flow_prior_elements(const ScalerFeat& feat, int scale, double* T, float* U, int* rowin,
-                                                    int r0, int rpp, int rows, int j, int D, int LD) {
-    ScalerFeat f = feat;
-    f.kind = KIND;
-#pragma unroll 1
-    for (int r = r0; r < rows; r += rpp) {
-        const double xv = T[r * LD + j];
-        // Reparameterize.forward: the bounded -> unbounded map, then the affine part; the Jacobian term is that of the
-        // inverse map at the unscaled value just computed
-        const double t = bound_forward(f, LOGIT, 0, xv);
-        double xb, J;
-        bound_inverse(f, LOGIT, t, xb, J);
-        const double u = scale ? (t - f.mu) / f.sigma : t;
-        const float uf = (float)u;
-        bool in = isfinite(xv) && isfinite(uf);
-        if (KIND == 1 || KIND == 3) in = in && xv > f.low;
-        if (KIND == 2 || KIND == 3) in = in && xv < f.high;
-        T[r * LD + j] = J;
-        U[r * D + j] = uf;
-        if (!in) rowin[r] = 0;
-    }
 }
 
 // One block: 64 rows through LDS.  x is read with element strides: (row_stride, col_stride) = (1, n) -- the step's
@@ -84,13 +53,7 @@ __global__ __launch_bounds__(FP_THREADS) void flow_prior_pre_kernel(
     __syncthreads();
     if (act) {
         scaler_feat_finish(f, s, false);
-        // (a loop per kind: with the kind a run-time value inside one loop the compiler keeps the polynomial constants of
-        //  erfinv, log and exp in registers all at once, and spills)
-        if (f.kind == 0) flow_prior_elements<0, 0>(f, s.scale, T, U, rowin, r0, rpp, rows, j, D, LD);
-        else if (f.kind == 1) flow_prior_elements<1, 0>(f, s.scale, T, U, rowin, r0, rpp, rows, j, D, LD);
-        else if (f.kind == 2) flow_prior_elements<2, 0>(f, s.scale, T, U, rowin, r0, rpp, rows, j, D, LD);
-        else if (s.logit) flow_prior_elements<3, 1>(f, s.scale, T, U, rowin, r0, rpp, rows, j, D, LD);
-        else flow_prior_elements<3, 0>(f, s.scale, T, U, rowin, r0, rpp, rows, j, D, LD);
+        flow_prior_feature(f, s, T, U, rowin, r0, rpp, rows, j, j, D, LD);      // (a loop per kind: flow_prior_body.h)
     }
     __syncthreads();
     if (tid < rows) {

@@ -12,7 +12,10 @@ The MCMC step can evaluate it on the device instead (``device_descriptor``, ``in
 MCMC step calls on the device like a device likelihood (``Sampler(device_likelihood=True, device_prior=True)``).
 
 ``FlowPrior`` is such a prior made of a finished run: its trained flow and fitted scaler are a normalised density on the
-prior's box, evaluated by two launches around the flow's own forward kernel (``csrc/flow_prior.hip``)."""
+prior's box, evaluated by two launches around the flow's own forward kernel (``csrc/flow_prior.hip``).
+
+``JointPrior`` puts such a flow prior on some columns of ``x`` and a table of scipy factors on the others, in the same number
+of launches (``csrc/joint_prior.hip``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -280,7 +283,11 @@ class FlowPrior:
     The density is float32 flow arithmetic: ``log p`` carries the flow kernels' relative error (1e-5 affine, 1e-4 spline).
     The prior owns copies of both parts: later ``set_params`` / ``fit`` calls on the source flow or scaler do not move it.  The
     scaler's boundary flags (periodic / reflective) are ignored: the forward map does not use them.  There is no
-    ``device_descriptor``: the step calls the function."""
+    ``device_descriptor``: the step calls the function.
+
+    ``from_sampler(s)`` takes a finished run's own flow and scaler; ``from_samples(x, weights, bounds)`` and
+    ``from_sampler(s, columns=...)`` fit a new flow on weighted samples -- the run's density on a subset of its parameters,
+    for ``JointPrior``."""
 
     MAX_DIM = 157            # the widest MCMC step (pmc_flow_prior_pre refuses wider calls)
     RVS_ROUNDS = 8           # redraws of rows that land outside the support before rvs gives up
@@ -303,20 +310,104 @@ class FlowPrior:
             raise ValueError(f"FlowPrior: n_dim = {flow.n_dim} is too large (n_dim <= {self.MAX_DIM})")
         self._restore(flow.__getstate__(), self._scaler_state(scaler), flow.device)
 
-    @classmethod
-    def from_sampler(cls, sampler):
-        """The prior a finished ``Sampler`` run leaves: ``sampler.flow`` and ``sampler.scaler``.  ``ValueError`` unless the
-        sampler is preconditioned, has run to beta = 1 and has trained its flow."""
-        if not getattr(sampler, "preconditioned", False):
-            raise ValueError("FlowPrior.from_sampler: the sampler is not preconditioned (precondition=False): it trains no flow")
+    @staticmethod
+    def _finished(sampler):
         walkers = getattr(sampler, "walkers", None)
         beta = None if walkers is None else walkers.get("beta")
         if beta is None or 1.0 - float(beta) >= 1e-4:
             raise ValueError("FlowPrior.from_sampler: the sampler has not run to beta = 1"
                              + ("" if beta is None else f" (beta = {float(beta):.6g})"))
-        if getattr(sampler, "flow_untrained", True):
-            raise ValueError("FlowPrior.from_sampler: the sampler's flow has not been trained")
-        return cls(sampler.flow, sampler.scaler)
+
+    @classmethod
+    def from_sampler(cls, sampler, columns=None, flow="nsf6", train_config=None):
+        """The prior a finished ``Sampler`` run leaves.  ``columns=None``: ``sampler.flow`` and ``sampler.scaler`` themselves
+        (``flow`` and ``train_config`` are not used); ``ValueError`` unless the sampler is preconditioned, has run to beta = 1
+        and has trained its flow.  ``columns``: the run's density on those of its parameters, in that order -- a flow cannot
+        be marginalised, so a new one is fitted on those columns of ``sampler.posterior()`` with its weights, on those rows of
+        the sampler's bounds (``from_samples``; ``ValueError`` unless the sampler has run to beta = 1)."""
+        if columns is None:
+            if not getattr(sampler, "preconditioned", False):
+                raise ValueError("FlowPrior.from_sampler: the sampler is not preconditioned (precondition=False): it trains "
+                                 "no flow")
+            cls._finished(sampler)
+            if getattr(sampler, "flow_untrained", True):
+                raise ValueError("FlowPrior.from_sampler: the sampler's flow has not been trained")
+            return cls(sampler.flow, sampler.scaler)
+        cls._finished(sampler)
+        scaler = sampler.scaler
+        k = len(columns) if hasattr(columns, "__len__") else 1
+        cols, _ = JointPrior.layout(columns, k, scaler.ndim - k)         # (checks them: distinct integers in [0, ndim))
+        samples, weights = sampler.posterior()[:2]
+        bounds = np.stack([scaler.low, scaler.high], axis=1)[cols]
+        return cls.from_samples(np.asarray(samples)[:, cols], weights, bounds=bounds, flow=flow, transform=scaler.transform,
+                                train_config=train_config)
+
+    TRAIN_KEYS = ("validation_split", "epochs", "batch_size", "patience", "learning_rate", "annealing", "gaussian_scale",
+                  "laplace_scale", "noise", "shuffle", "clip_grad_norm", "verbose")
+
+    @classmethod
+    def from_samples(cls, x, weights=None, bounds=None, flow="nsf6", transform="probit", train_config=None):
+        """A flow prior fitted on weighted samples: ``x`` ``(n, D)`` rows strictly inside ``bounds`` (``(D, 2)``, +-inf or NaN:
+        unbounded on that side; None: unbounded), ``weights`` ``(n,)`` (None: uniform; normalised here).  A diagonal
+        ``Reparameterize`` on ``bounds`` whose ``mu`` / ``sigma`` are the weighted mean and the weighted standard deviation
+        (ddof 0) of the unscaled forward transform of ``x``; then ``Flow(D, flow)`` fitted on ``u = scaler.forward(x)`` with
+        those weights, under the Sampler's ``train_config`` defaults (``validation_split=0.5, epochs=5000,
+        batch_size=min(n // 2, 512), patience=D, learning_rate=1e-3, annealing=False, clip_grad_norm=1.0, shuffle=True``),
+        which ``train_config`` overrides.  The fit shuffles with torch's global CPU generator, as every ``Flow.fit``."""
+        import torch
+        from .flow import Flow
+        from .scaler import Reparameterize
+        try:
+            x = np.array(x, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("FlowPrior.from_samples: x must be an (n, D) array of floats") from None
+        if x.ndim != 2 or x.shape[0] < 2:
+            raise ValueError(f"FlowPrior.from_samples: x must have shape (n, D) with n >= 2, got {x.shape}")
+        n, D = x.shape
+        if D < 2:
+            raise ValueError(f"FlowPrior.from_samples: a flow needs at least 2 dimensions, got {D}")
+        if D > cls.MAX_DIM:
+            raise ValueError(f"FlowPrior.from_samples: n_dim = {D} is too large (n_dim <= {cls.MAX_DIM})")
+        if bounds is None:
+            b = np.stack([np.full(D, -np.inf), np.full(D, np.inf)], axis=1)
+        else:
+            b = np.array(bounds, dtype=np.float64)
+            if b.shape != (D, 2):
+                raise ValueError(f"FlowPrior.from_samples: bounds must have shape ({D}, 2), got {b.shape}")
+            b = np.stack([np.where(np.isnan(b[:, 0]), -np.inf, b[:, 0]), np.where(np.isnan(b[:, 1]), np.inf, b[:, 1])], axis=1)
+        with np.errstate(invalid="ignore"):
+            ok = np.isfinite(x) & (x > b[:, 0]) & (x < b[:, 1])
+        if not ok.all():
+            r, j = np.argwhere(~ok)[0]
+            raise ValueError(f"FlowPrior.from_samples: row {r} is outside the bounds (column {j}: {x[r, j]} is not strictly "
+                             f"inside ({b[j, 0]}, {b[j, 1]}))")
+        if weights is None:
+            w = np.full(n, 1.0 / n)
+        else:
+            w = np.array(weights, dtype=np.float64)
+            if w.shape != (n,):
+                raise ValueError(f"FlowPrior.from_samples: weights must have shape ({n},), got {w.shape}")
+            if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+                raise ValueError("FlowPrior.from_samples: weights must be finite, not negative and not all zero")
+            w = w / w.sum()
+        cfg = dict(validation_split=0.5, epochs=5000, batch_size=min(n // 2, 512), patience=D, learning_rate=1e-3,
+                   annealing=False, clip_grad_norm=1.0, shuffle=True)
+        for k, v in (train_config or {}).items():
+            if k not in cls.TRAIN_KEYS:
+                raise ValueError(f"FlowPrior.from_samples: train_config has no key {k!r} (keys: {', '.join(cls.TRAIN_KEYS)})")
+            cfg[k] = v
+        cfg["batch_size"] = int(min(n // 2, cfg["batch_size"]))
+        scaler = Reparameterize(D, bounds=b, transform=transform)
+        t = scaler._forward_device(x, scale=False)
+        mu = np.sum(w[:, None] * t, axis=0)
+        sigma = np.sqrt(np.sum(w[:, None] * (t - mu) ** 2, axis=0))
+        if not (np.isfinite(mu).all() and np.isfinite(sigma).all() and (sigma > 0).all()):
+            raise ValueError("FlowPrior.from_samples: a column's transformed samples have no finite, positive spread")
+        scaler.mu, scaler.sigma = mu, sigma
+        u = scaler.forward(x, check_input=False)
+        f = Flow(D, flow)
+        f.fit(torch.from_numpy(u.astype(np.float32)), weights=torch.from_numpy(w.astype(np.float32)), **cfg)
+        return cls(f, scaler)
 
     # ----------------------------------------------------------------- state
     @staticmethod
@@ -435,3 +526,184 @@ class FlowPrior:
     @property
     def dim(self):
         return self.scaler.ndim
+
+
+class JointPrior:
+    """A flow prior on some of the parameters and scipy factors on the others:
+
+        ``log p(x) = flow_prior.logpdf(x[:, columns]) + sum_m rest.dists[m].logpdf(x[:, rest_cols[m]])``.
+
+    The usual case of two experiments that share a block of parameters: run A's posterior on the shared block (a
+    ``FlowPrior``, see ``FlowPrior.from_sampler(a, columns=...)``) and ordinary priors on run B's own nuisance parameters.
+
+    ``flow_prior``  a ``FlowPrior``;
+    ``columns``     the positions in the joint ``x`` of the flow prior's dimensions: ``flow_prior.dim`` distinct integers, in
+                    any order (``x[:, columns[k]]`` is the flow prior's dimension k);
+    ``rest``        a ``Prior`` the device evaluates (``Prior(dists, device=True)``, or uniform / normal factors), with at
+                    least one factor; its factors fill the remaining positions in increasing order.
+
+    ``logpdf_device(x)``  the ``DevicePrior`` contract, in three launches on the current stream: ``pmc_joint_prior_pre`` (one
+                          pass over ``x``: the flow block's u as float32, its scaler's log-determinant, the table factors' sum,
+                          the support test), the flow's own forward call with ``log_prob``, ``pmc_joint_prior_post``.  No host
+                          synchronisation; no copy of ``x`` when it is C-contiguous or the MCMC step's column-major view.  -inf
+                          outside the support of either part, on a bound of the flow block, at a pole of a factor and for rows
+                          with a NaN or an inf; never NaN, never +inf.  A row's value does not depend on the layout, on ``n``
+                          or on its place in ``x``, and is ``flow_prior.logpdf_device`` of the gathered block plus
+                          ``pmc_prior_logpdf`` of the gathered rest, bit for bit.
+    ``logpdf(x)``         numpy in, numpy out, through the same function.
+    ``rvs(size)``         the flow columns from ``flow_prior.rvs``, the others from ``rest.rvs``.
+    ``bounds``, ``dim``   the two parts', merged by position.
+
+    The prior owns copies of both parts (the flow prior through its pickled state, the table as arrays): later changes to the
+    sources do not move it.  There is no ``device_descriptor``: the step calls the function.  Out of scope: more than one flow
+    block, non-diagonal scalers, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
+
+    MAX_DIM = FlowPrior.MAX_DIM
+    _WORKSPACES = FlowPrior._WORKSPACES
+
+    @staticmethod
+    def layout(columns, flow_dim, rest_dim):
+        """``(flow_cols, rest_cols)`` as int32 arrays: ``flow_cols`` is ``columns`` (``flow_dim`` distinct integers in
+        ``[0, flow_dim + rest_dim)``), ``rest_cols`` the ``rest_dim`` other positions in increasing order.  ``ValueError`` for
+        duplicates, for entries out of range or not integers and for a wrong count.  Pure numpy."""
+        flow_dim, rest_dim = int(flow_dim), int(rest_dim)
+        if flow_dim < 0 or rest_dim < 0:
+            raise ValueError(f"JointPrior.layout: negative dimension (flow_dim = {flow_dim}, rest_dim = {rest_dim})")
+        try:
+            cols = np.asarray(columns)
+        except (TypeError, ValueError):
+            cols = np.asarray(columns, dtype=object)
+        if cols.size == 0:
+            cols = cols.astype(np.int64)
+        if cols.ndim != 1 or cols.dtype == np.bool_ or not np.issubdtype(cols.dtype, np.integer):
+            raise ValueError(f"JointPrior.layout: columns must be a sequence of integers, got {columns!r}")
+        if len(cols) != flow_dim:
+            raise ValueError(f"JointPrior.layout: {len(cols)} columns for a flow prior of {flow_dim} dimensions")
+        D = flow_dim + rest_dim
+        if ((cols < 0) | (cols >= D)).any():
+            raise ValueError(f"JointPrior.layout: columns must lie in [0, {D}), got {cols.tolist()}")
+        if len(np.unique(cols)) != len(cols):
+            raise ValueError(f"JointPrior.layout: columns are not distinct: {cols.tolist()}")
+        rest_cols = np.setdiff1d(np.arange(D), cols)
+        return cols.astype(np.int32), rest_cols.astype(np.int32)
+
+    def __init__(self, flow_prior, columns, rest):
+        if not isinstance(flow_prior, FlowPrior):
+            raise ValueError(f"JointPrior: flow_prior must be a pocomc_amd.FlowPrior, got {type(flow_prior).__name__}")
+        if not isinstance(rest, Prior):
+            raise ValueError(f"JointPrior: rest must be a pocomc_amd.Prior, got {type(rest).__name__}")
+        if rest.dists is None or rest.dim < 1:
+            raise ValueError("JointPrior: rest needs at least one factor")
+        if rest.device_table() is None:
+            raise ValueError("JointPrior: the device must evaluate rest: build it as Prior(dists, device=True)")
+        if flow_prior.dim + rest.dim > self.MAX_DIM:
+            raise ValueError(f"JointPrior: n_dim = {flow_prior.dim} + {rest.dim} is too large (n_dim <= {self.MAX_DIM})")
+        flow_cols, _ = self.layout(columns, flow_prior.dim, rest.dim)
+        self._restore(flow_prior.__getstate__(), flow_cols.tolist(), rest, flow_prior.flow.device)
+
+    # ----------------------------------------------------------------- state
+    def _restore(self, flow_prior_state, columns, rest, device=None):
+        import copy
+        import torch
+        from . import _lib
+        self.flow_prior = FlowPrior.__new__(FlowPrior)
+        self.flow_prior._restore(flow_prior_state["flow"], flow_prior_state["scaler"], device)
+        self.rest = copy.deepcopy(rest)
+        self._flow_cols, self._rest_cols = self.layout(columns, self.flow_prior.dim, self.rest.dim)
+        tab = self.rest.device_table()
+        dev = self.flow_prior.flow.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        n_ext = int((tab["family"] > 2).sum())
+        # (the descriptor points into these tensors: they live as long as it does)
+        self._dev = dict(family=up(tab["family"]), loc=up(tab["loc"]), scale=up(tab["scale"]),
+                         par=up(tab["par"]) if n_ext else None, flow_cols=up(self._flow_cols), rest_cols=up(self._rest_cols))
+        self._rdesc = _lib.pmc_prior_t(family=self._dev["family"].data_ptr(), loc=self._dev["loc"].data_ptr(),
+                                       scale=self._dev["scale"].data_ptr(), D=len(tab["family"]), reserved=0,
+                                       par=self._dev["par"].data_ptr() if n_ext else None, n_extended=n_ext, reserved2=0)
+        self._ws = {}
+
+    def __getstate__(self):
+        return {"flow_prior": self.flow_prior.__getstate__(), "columns": self._flow_cols.tolist(), "rest": self.rest}
+
+    def __setstate__(self, st):
+        self._restore(st["flow_prior"], st["columns"], st["rest"])
+
+    # ----------------------------------------------------------------- density
+    def _workspace(self, n):
+        import torch
+        ws = self._ws.get(n)
+        if ws is None:
+            dev, Df = self.flow_prior.flow.device, self.flow_prior.dim
+            ws = (torch.empty(n, Df, dtype=torch.float32, device=dev),           # u32
+                  torch.empty(n, Df, dtype=torch.float32, device=dev),           # z (the flow writes it; not used)
+                  torch.empty(n, dtype=torch.float32, device=dev),               # the flow's log_prob
+                  torch.empty(n, dtype=torch.float64, device=dev),               # the scaler's log-determinant
+                  torch.empty(n, dtype=torch.float64, device=dev),               # the table factors' sum
+                  torch.empty(n, dtype=torch.int32, device=dev))                 # inside the support
+            while len(self._ws) >= self._WORKSPACES:
+                self._ws.pop(next(iter(self._ws)))
+            self._ws[n] = ws
+        return ws
+
+    def logpdf_device(self, x):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        D, flow = self.dim, self.flow_prior.flow
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"JointPrior.logpdf_device: expected an (n, {D}) float64 tensor, got {what}")
+        _on_device(x, flow.device, "JointPrior.logpdf_device")
+        n = x.shape[0]
+        out = torch.empty(n, dtype=torch.float64, device=flow.device)
+        if n == 0:
+            return out
+        # the two layouts the kernel reads with coalesced loads; everything else is copied once
+        if x.is_contiguous():
+            strides = (D, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (D, 1)
+        u32, z, lp32, ldj, rest_logp, inside = self._workspace(n)
+        lib = flow.lib
+        with torch.cuda.device(flow.device):
+            _lib.check(lib.pmc_joint_prior_pre(C.byref(self.flow_prior._sdesc), _lib.ptr(self._dev["flow_cols"]),
+                                               C.byref(self._rdesc), _lib.ptr(self._dev["rest_cols"]),
+                                               C.c_void_p(x.data_ptr()), strides[0], strides[1], n, _lib.ptr(u32),
+                                               _lib.ptr(ldj), _lib.ptr(rest_logp), _lib.ptr(inside), _lib.stream_handle()),
+                       "pmc_joint_prior_pre")
+            flow._forward_call(u32, z, None, lp32, n)
+            _lib.check(lib.pmc_joint_prior_post(_lib.ptr(lp32), _lib.ptr(ldj), _lib.ptr(rest_logp), _lib.ptr(inside),
+                                                _lib.ptr(out), n, _lib.stream_handle()), "pmc_joint_prior_post")
+        return out
+
+    def logpdf(self, x):
+        import torch
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"JointPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
+        return self.logpdf_device(torch.from_numpy(x).to(self.flow_prior.flow.device)).cpu().numpy()
+
+    # ----------------------------------------------------------------- draws
+    def rvs(self, size=1):
+        size = int(size)
+        x = np.empty((size, self.dim), dtype=np.float64)
+        x[:, self._flow_cols] = self.flow_prior.rvs(size)
+        # rest.rvs with numpy's global generator named: this prior's copy of the factors (a deep copy, or an unpickled one)
+        # carries a private copy of that generator's state, which np.random.seed -- the Sampler's random_state -- never reaches
+        glob = np.random.mtrand._rand
+        x[:, self._rest_cols] = np.transpose([d.rvs(size=size, random_state=glob) for d in self.rest.dists])
+        return x
+
+    @property
+    def bounds(self):
+        b = np.empty((self.dim, 2), dtype=np.float64)
+        b[self._flow_cols] = self.flow_prior.bounds
+        b[self._rest_cols] = self.rest.bounds
+        return b
+
+    @property
+    def dim(self):
+        return self.flow_prior.dim + self.rest.dim
