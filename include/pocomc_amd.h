@@ -563,6 +563,32 @@ int pmc_accept_armed(int kind, int preconditioned, pmc_state_t* cur, const pmc_p
                      double nu, const pmc_rng_t* rng, double* alpha_out, int32_t* accept_out, double* sums,
                      double* sums_copy, const pmc_done_t* done, void* workspace, int64_t n, int32_t D, void* stream);
 
+/* What the step needs to evaluate a flow prior (pocomc_amd.FlowPrior) or a joint prior (pocomc_amd.JointPrior) on its own
+ * stream (pmc_step_ext_t.prior_stage, pmc_step_prior_stage): the descriptors the prior's own calls take and the workspaces its
+ * Python class allocates for them, for the n rows of one pmc_step_t.  Everything is device memory except h_count; the
+ * caller keeps all of it alive and unchanged while a step that points here is in flight. */
+typedef struct pmc_prior_stage {
+    const pmc_scaler_t* scaler;   /* the flow block's scaler (scaler->D = the flow's features) */
+    const pmc_maf_t* maf;         /* the flow */
+    const uint16_t* image16;      /* precision="bf16" flows: the bf16 image of pmc_maf_forward_bf16; NULL: pmc_maf_forward */
+    int64_t image_per_transform;  /* ... and its per_t (0 without an image) */
+    const int32_t* flow_cols;     /* joint prior: int32 [Df], as for pmc_joint_prior_pre; a flow prior: NULL, ... */
+    const pmc_prior_t* rest;      /* ... NULL ... */
+    const int32_t* rest_cols;     /* ... and NULL */
+    float* u32;                   /* f32 [n][Df] */
+    float* z;                     /* f32 [n][Df] (the flow writes it; not used) */
+    float* lp32;                  /* f32 [n] the flow's log_prob */
+    double* ldj;                  /* f64 [n] the scaler's log-determinant */
+    double* rest_logp;            /* f64 [n] the table factors' sum (joint prior; a flow prior: NULL) */
+    int32_t* inside;              /* int32 [n] */
+    unsigned long long* count;    /* device u64 [2], zeroed once by the caller: [0] the count of the launch in flight (zero
+                                   * again behind every launch), [1] the stage's launches so far */
+    int64_t* h_count;             /* pinned, device-accessible host int64 [2]: word [k & 1] <- the rows of the stage's launch
+                                   * number k (from 0: k = count[1]) with p_fin != 0 whose logp' is not finite.  Two words,
+                                   * taken in turn: the pre-step of step k + 1 may run before the host has read the count of
+                                   * step k; the host reads them in turn as well, one per step */
+} pmc_prior_stage_t;
+
 /* All buffers of one step in one place, for the composite entry points below. */
 typedef struct pmc_step {
     int32_t kind;             /* PMC_KIND_TPCN | PMC_KIND_RWM */
@@ -630,7 +656,9 @@ typedef struct pmc_step {
      * operation order, so a host that applies the same update to the same sums holds the same sigma and mu. */
     double* adapt_state;      /* device f64 [2 + D] or NULL */
     int32_t adapt_mode;       /* PMC_ADAPT_* ; 0: the accept kernel leaves adapt_state alone */
-    int32_t adapt_pad;
+    int32_t ext;              /* 0, or PMC_STEP_EXT: this struct is the `step` member of a pmc_step_ext_t, whose fields behind it
+                               * every entry point below then reads as well (the word was reserved padding, zero in every caller
+                               * so far: no offset and no size changes) */
     double adapt_c_sigma;     /* 1/(i+1)^0.75 (tpCN kinds) or 1/(i+1) (RWM kinds) of the update that follows this step */
     double adapt_c_mu;        /* 1/(i+1) */
     double adapt_cap;         /* min(2.38/sqrt(D), 0.99) */
@@ -719,6 +747,26 @@ typedef struct pmc_step {
 
 #define PMC_BLOB_ROW_BYTES_MAX (1 << 20)
 
+/* pmc_step_t with fields behind it.  pmc_step_t keeps its size -- callers that allocate one pass it as ever --, so what a
+ * step gains from here on is appended to this struct instead: a caller that wants it allocates a pmc_step_ext_t, sets
+ * step.ext = PMC_STEP_EXT and passes &ext.step wherever a pmc_step_t* is taken (pmc_pipeline_create included).  With
+ * step.ext == 0 nothing behind the pmc_step_t is read.
+ *
+ * prior_stage: a flow prior or a joint prior inside the step of a HOST likelihood (NULL: none, and every call does what it
+ * did).  With prior_stage non-NULL and prior == NULL, prior_rows == 0, lik_x == NULL:
+ *   pmc_step_pre enqueues pmc_step_prior_stage behind its own launches and copies: the prior's three launches read p_x
+ *   and write p_logp on the step's stream while the host, which got x' and the finite mask exactly as for a host prior
+ *   (pmc_step_handover returns what it returns without the stage), evaluates the likelihood.  Nothing about logp' goes
+ *   to the host: it masks on the finite flags only.
+ *   pmc_step_post takes logp' from p_logp in every hand-over mode (no H2D copy of h_logp, no read of it over PCIe).
+ * A row with a finite x' whose logp' is -inf reaches the host likelihood all the same; its logl' is dropped, alpha = 0
+ * through logp' (mcmc.py:130-134).  pmc_prior_stage_t.h_count tells the host how many such rows a step had. */
+#define PMC_STEP_EXT 1
+typedef struct pmc_step_ext {
+    pmc_step_t step;
+    const pmc_prior_stage_t* prior_stage;
+} pmc_step_ext_t;
+
 /* dst[r] <- src[r] (rows of row_bytes bytes) for every r < n with accept[r] != 0; the other rows are neither read nor
  * written.  accept: device int32 [n] (pmc_step_t.accept); src: device-accessible memory, typically pinned host memory
  * (the loads cross PCIe: the kernel keeps several in flight per thread); dst: device.  row_bytes a multiple of 4 between 4
@@ -779,6 +827,24 @@ int pmc_step_lik_rows(const pmc_step_t* s, void* stream);
  * current x and added to clean_count, so that pmc_step_post's h_calls = n - clean_count stays "rows that reached the
  * likelihood".  One launch on `stream`: no copy, no wait. */
 int pmc_step_prior_rows(const pmc_step_t* s, const void* logp, int logp_is_f32, void* stream);
+/* Host likelihood with a flow prior or a joint prior on the step's stream (pmc_step_ext_t.prior_stage): three launches on
+ * `stream`, behind the pre-step that wrote p_x (C-contiguous [n][D]) and p_fin -- no copy, no wait:
+ *   1. pmc_flow_prior_pre (flow_cols == NULL) or pmc_joint_prior_pre on p_x;
+ *   2. the flow's forward call with log_prob on u32: pmc_maf_forward, or pmc_maf_forward_bf16 with image16;
+ *   3. a closing kernel:  p_logp[r] = what pmc_flow_prior_post / pmc_joint_prior_post give for the row, in the same
+ *      operations and order (bit for bit), where p_fin[r] != 0, and -inf where it is 0 (mcmc.py:105-107).  It counts the
+ *      rows with p_fin[r] != 0 whose logp' is not finite -- rows the host hands to the likelihood and the reference would
+ *      not (mcmc.py:108-109) -- with one atomic per block; the last block stores the count to the host word whose turn it is
+ *      (pmc_prior_stage_t.h_count) and zeroes the device word.  The launch completes, that store
+ *      included, before the accept that follows it on the stream starts: the count is in host memory in front of the
+ *      accept's completion word, and in front of the end of its copies.
+ * pmc_step_pre calls it at its end; pmc_step_pre_deferred does not: pmc_pipeline_start / pmc_pipeline_next enqueue every
+ * lane's stage behind the LAST lane's pre-step (no lane's x' waits behind another lane's log_prob), in front of the
+ * variates of the next step.
+ * Refused before anything is launched, each with a text of its own: a struct without prior_stage; with prior, prior_rows or
+ * lik_x set as well; NULL descriptors, workspaces or count words; n < 1; p_x, p_fin or p_logp missing; a width that
+ * pmc_flow_prior_pre / pmc_joint_prior_pre refuses (their checks, their texts) or that is not the step's D. */
+int pmc_step_prior_stage(const pmc_step_t* s, void* stream);
 /* The adaptation of pmc_step_t.adapt_state as a launch of its own, for walker sets whose sums come in parts
  * (row ranges stepped one after the other, mcmc.LanedEngine; ranks, after the all-reduce):
  *   total[j] = parts[0][j] + parts[1][j] + ...   (j < D + 4, n_parts <= 8, added in this order)

@@ -108,12 +108,28 @@ class pmc_step_t(C.Structure):
                 ("rng_normal", c_p * 2), ("rng_gamma", c_p * 2), ("rng_uniform", c_p * 2), ("rng_ready", c_p),
                 ("ev_pre_done", c_p), ("h_done", c_p), ("done_ticket", c_p),
                 ("no_fuse", C.c_int32), ("host_direct", C.c_int32),
-                ("adapt_state", C.c_void_p), ("adapt_mode", C.c_int32), ("adapt_pad", C.c_int32),
+                ("adapt_state", C.c_void_p), ("adapt_mode", C.c_int32), ("ext", C.c_int32),
                 ("adapt_c_sigma", C.c_double), ("adapt_c_mu", C.c_double), ("adapt_cap", C.c_double),
                 ("adapt_n_total", C.c_double), ("adapt_other", C.c_void_p * 7), ("adapt_n_other", C.c_int32),
                 ("blob_host", C.c_int32), ("h_clean", c_p), ("clean_count", c_p),
                 ("fill_rejected", C.c_int32), ("prior_rows", C.c_int32), ("lik_x", c_p), ("h_calls", c_p),
                 ("blob_cur", c_p), ("blob_prop", c_p), ("blob_row_bytes", C.c_int64)]
+
+
+PMC_STEP_EXT = 1
+
+
+class pmc_step_ext_t(pmc_step_t):
+    """``pmc_step_t`` with the fields behind it (include/pocomc_amd.h: the base struct keeps its size); pass it wherever a
+    ``pmc_step_t`` is taken, with ``ext = PMC_STEP_EXT``."""
+    _fields_ = [("prior_stage", c_p)]
+
+
+class pmc_prior_stage_t(C.Structure):
+    _fields_ = [("scaler", c_p), ("maf", c_p), ("image16", c_p), ("image_per_transform", C.c_int64),
+                ("flow_cols", c_p), ("rest", c_p), ("rest_cols", c_p),
+                ("u32", c_p), ("z", c_p), ("lp32", c_p), ("ldj", c_p), ("rest_logp", c_p), ("inside", c_p),
+                ("count", c_p), ("h_count", c_p)]
 
 
 # name -> (restype, argtypes); every symbol include/pocomc_amd.h declares
@@ -177,6 +193,7 @@ SIGNATURES = {
     "pmc_step_post": (C.c_int, [P(pmc_step_t), P(pmc_rng_t), f64, f64, C.c_int, C.c_int, c_p]),
     "pmc_step_lik_rows": (C.c_int, [P(pmc_step_t), c_p]),
     "pmc_step_prior_rows": (C.c_int, [P(pmc_step_t), c_p, C.c_int, c_p]),
+    "pmc_step_prior_stage": (C.c_int, [P(pmc_step_t), c_p]),
     "pmc_blob_rows_move": (C.c_int, [c_p, c_p, c_p, i64, i64, c_p]),
     "pmc_stream_synchronize": (C.c_int, [c_p]),
     "pmc_pipeline_create": (C.c_void_p, [C.POINTER(C.c_void_p), i32, C.c_uint64, C.POINTER(C.c_uint64), c_p, f64, c_p]),

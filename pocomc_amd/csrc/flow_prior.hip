@@ -82,8 +82,7 @@ __global__ __launch_bounds__(256) void flow_prior_post_kernel(const float* __res
                                                               int64_t n) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
-    const double v = (double)lp32[r] - ldj[r];
-    logp[r] = (inside[r] && isfinite(v)) ? v : -INFINITY;
+    logp[r] = flow_prior_join(lp32[r], ldj[r], inside[r]);
 }
 
 extern "C" int pmc_flow_prior_pre(const pmc_scaler_t* s, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,

@@ -48,4 +48,16 @@ __device__ __forceinline__ void flow_prior_feature(const ScalerFeat& f, const pm
     else flow_prior_elements<3, 0>(f, s.scale, T, U, rowin, r0, rpp, rows, jt, ju, DU, LD);
 }
 
+// The join of a row: the flow's float32 log-density with the scaler's log-determinant (and the table factors' sum), -inf
+// outside the support and for a value that is not finite.  One statement of it for the post kernels of flow_prior.hip /
+// joint_prior.hip and for the step's closing kernel (step.hip), which must give their bits.
+__device__ __forceinline__ double flow_prior_join(float lp32, double ldj, int inside) {
+    const double v = (double)lp32 - ldj;
+    return (inside && isfinite(v)) ? v : -INFINITY;
+}
+__device__ __forceinline__ double joint_prior_join(float lp32, double ldj, double rest_logp, int inside) {
+    const double v = ((double)lp32 - ldj) + rest_logp;
+    return (inside && isfinite(v)) ? v : -INFINITY;
+}
+
 #endif

@@ -123,8 +123,7 @@ __global__ __launch_bounds__(256) void joint_prior_post_kernel(const float* __re
                                                                int64_t n) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
-    const double v = ((double)lp32[r] - ldj[r]) + rest_logp[r];
-    logp[r] = (inside[r] && isfinite(v)) ? v : -INFINITY;
+    logp[r] = joint_prior_join(lp32[r], ldj[r], rest_logp[r], inside[r]);
 }
 
 extern "C" int pmc_joint_prior_pre(const pmc_scaler_t* s, const int32_t* flow_cols, const pmc_prior_t* rest,

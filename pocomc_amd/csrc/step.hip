@@ -3,6 +3,7 @@
 // host-side driver spends its time in the user's black boxes instead of in dispatch overhead.
 //
 //   pmc_step_pre :  [H2D mu] -> propose -> flow inverse (one launch for the affine flows) -> scaler inverse [+ prior] -> D2H x', finite
+//                   [-> the flow / joint prior's three launches on p_x, pmc_step_ext_t.prior_stage]
 //   pmc_step_post:  H2D logl', logp' -> accept + reductions -> D2H sums
 //
 // With a likelihood on the device (pmc_step_t.lik_x) x' goes to lik_x instead of the host, the caller's likelihood fills
@@ -18,10 +19,12 @@
 #include "pmc_internal.h"
 #include "propose_body.h"
 #include "blob_move.h"
+#include "flow_prior_body.h"
 
 #ifdef PMC_DEBUG_HOOKS                               // measurement builds only (make DEBUG_HOOKS=1): not in the product library
 static long long* g_epilogue_stamps = nullptr;       // pmc_debug_set_epilogue_stamps
 static int64_t g_epilogue_stamps_n = 0;
+static bool g_stage_per_lane = false;                // pmc_debug_set_stage_per_lane
 #endif
 
 // the variates of step rng->step + 1 into the other parity's buffers (throughput mode, see pmc_step_t.rng_normal)
@@ -41,6 +44,18 @@ extern "C" int pmc_step_fill_next(const pmc_step_t* s, const pmc_rng_t* rng, dou
     if (rcf) return rcf;
     *s->rng_ready = (int64_t)nx.step;
     return 0;
+}
+
+// the fields behind a pmc_step_t that is the head of a pmc_step_ext_t (step.ext says so; nothing behind it is read otherwise)
+static const pmc_prior_stage_t* step_stage(const pmc_step_t* s) {
+    return s->ext == PMC_STEP_EXT ? reinterpret_cast<const pmc_step_ext_t*>(s)->prior_stage : nullptr;
+}
+// a copy the caller may change: the head, and the fields behind it where there are any
+static pmc_step_ext_t step_copy(const pmc_step_t* s) {
+    pmc_step_ext_t c{};
+    c.step = *s;
+    c.prior_stage = step_stage(s);
+    return c;
 }
 
 // host_direct: the kernels read mu from / write x', finite, logp' to pinned host memory themselves
@@ -96,11 +111,114 @@ extern "C" int pmc_step_handover(const pmc_step_t* s, int64_t step, int32_t epil
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The flow / joint prior of a host likelihood on the step's stream (pmc_step_ext_t.prior_stage, pmc_step_prior_stage).
+//
+// The closing kernel: one thread per walker.  logp' as the priors' own post kernels join it (flow_prior_body.h), -inf
+// where x' is not finite (mcmc.py:105-107).  The rows with a finite x' and no finite logp' -- the host hands them to the
+// likelihood, the reference does not (mcmc.py:108-109) -- are counted: a ballot per wavefront, one atomic per block on
+// count[0], whose high half counts the blocks that have arrived and whose low half the rows.  The block that finds every
+// other one arrived stores the total to h_count[launch & 1] (count[1]: the launches so far) and leaves count[0] at zero
+// for the next launch; nothing else in the kernel depends on another block.  The launch ends, that store included,
+// before the next launch on the stream -- the accept -- starts.
+template <bool JOINT>
+__global__ __launch_bounds__(256) void prior_stage_close_kernel(const float* __restrict__ lp32, const double* __restrict__ ldj,
+                                                                const double* __restrict__ rest_logp,
+                                                                const int32_t* __restrict__ inside,
+                                                                const int32_t* __restrict__ fin, double* __restrict__ logp,
+                                                                unsigned long long* __restrict__ count,
+                                                                long long* __restrict__ h_count, int64_t n) {
+    __shared__ unsigned wave_bad[4];
+    const int tid = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+    bool bad = false;
+    if (r < n) {
+        double v = -INFINITY;
+        if (fin[r]) {
+            v = JOINT ? joint_prior_join(lp32[r], ldj[r], rest_logp[r], inside[r]) : flow_prior_join(lp32[r], ldj[r], inside[r]);
+            bad = !isfinite(v);
+        }
+        logp[r] = v;
+    }
+    const unsigned nb = (unsigned)__popcll(__ballot(bad));
+    if ((tid & 63) == 0) wave_bad[tid >> 6] = nb;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long mine = wave_bad[0] + wave_bad[1] + wave_bad[2] + wave_bad[3];
+        const unsigned long long old = __hip_atomic_fetch_add(count, (1ull << 32) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)(old >> 32) == gridDim.x - 1) {
+            const unsigned long long launch = count[1];
+            __hip_atomic_store(h_count + (launch & 1), (long long)((old & 0xffffffffull) + mine), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+            count[1] = launch + 1;
+            __hip_atomic_store(count, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// what pmc_step_prior_stage refuses, before any launch (host logic: follows s->prior_stage and its scaler / rest only)
+static int prior_stage_check(const pmc_step_t* s) {
+    if (!s) return pmc_fail("pmc_step_prior_stage: null argument");
+    const pmc_prior_stage_t* g = step_stage(s);
+    if (!g) return pmc_fail("pmc_step_prior_stage: the step has no prior_stage");
+    if (s->prior) return pmc_fail("pmc_step_prior_stage: the step has a device prior table as well (prior): one of the two");
+    if (s->prior_rows) return pmc_fail("pmc_step_prior_stage: the step has a prior that is a GPU callable as well (prior_rows): one of the two");
+    if (s->lik_x) return pmc_fail("pmc_step_prior_stage: the stage is for a host likelihood (lik_x is set: call the prior on lik_x instead)");
+    if (!g->scaler || !g->maf) return pmc_fail("pmc_step_prior_stage: needs the flow block's scaler and the flow");
+    if (!g->u32 || !g->z || !g->lp32 || !g->ldj || !g->inside) return pmc_fail("pmc_step_prior_stage: null workspace (u32, z, lp32, ldj, inside)");
+    if (!g->count || !g->h_count) return pmc_fail("pmc_step_prior_stage: needs the device counter and the pinned host words");
+    const bool joint = g->flow_cols || g->rest || g->rest_cols;
+    if (joint && !(g->flow_cols && g->rest && g->rest_cols)) return pmc_fail("pmc_step_prior_stage: a joint prior needs flow_cols, rest and rest_cols");
+    if (joint && !g->rest_logp) return pmc_fail("pmc_step_prior_stage: null workspace (rest_logp)");
+    if (g->image16 && g->image_per_transform < 1) return pmc_fail("pmc_step_prior_stage: a bf16 image needs image_per_transform");
+    if (s->n < 1) return pmc_fail("pmc_step_prior_stage: n < 1");
+    if (s->n > 0x7fffffffLL) return pmc_fail("pmc_step_prior_stage: too many rows for one count");
+    if (!s->p_x || !s->p_fin || !s->p_logp) return pmc_fail("pmc_step_prior_stage: needs p_x, p_fin and p_logp");
+    // the widths the two *_pre entries refuse, in their words
+    const int64_t Df = g->scaler->D, Dr = joint ? g->rest->D : 0;
+    if (!joint && Df < 1) return pmc_fail("pmc_flow_prior_pre: bad descriptor");
+    if (!joint && Df > FP_MAX_D) return pmc_fail("pmc_flow_prior_pre: n_dim too large (D <= 157)");
+    if (joint && Df < 2) return pmc_fail("pmc_joint_prior_pre: the flow block needs at least 2 columns (Df >= 2)");
+    if (joint && Dr < 1) return pmc_fail("pmc_joint_prior_pre: the rest needs at least 1 factor (Dr >= 1)");
+    if (joint && Df + Dr > FP_MAX_D) return pmc_fail("pmc_joint_prior_pre: n_dim too large (Df + Dr <= 157)");
+    if (Df + Dr != s->D) return pmc_fail("pmc_step_prior_stage: the prior's width is not the step's D");
+    if (g->maf->D != Df) return pmc_fail("pmc_step_prior_stage: the flow's width is not the scaler's");
+    return 0;
+}
+
+// the three launches (the struct has passed prior_stage_check)
+static int prior_stage_enqueue(const pmc_step_t* s, void* stream) {
+    const pmc_prior_stage_t* g = step_stage(s);
+    const int64_t n = s->n;
+    const bool joint = g->flow_cols != nullptr;
+    int rc = joint ? pmc_joint_prior_pre(g->scaler, g->flow_cols, g->rest, g->rest_cols, s->p_x, s->D, 1, n, g->u32, g->ldj,
+                                         g->rest_logp, g->inside, stream)
+                   : pmc_flow_prior_pre(g->scaler, s->p_x, s->D, 1, n, g->u32, g->ldj, g->inside, stream);
+    if (rc) return rc;
+    rc = g->image16 ? pmc_maf_forward_bf16(g->maf, g->image16, g->image_per_transform, g->u32, g->z, nullptr, g->lp32, n, nullptr, stream)
+                    : pmc_maf_forward(g->maf, g->u32, g->z, nullptr, g->lp32, n, stream);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (joint)
+        hipLaunchKernelGGL(prior_stage_close_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g->lp32, g->ldj, g->rest_logp,
+                           g->inside, s->p_fin, s->p_logp, g->count, (long long*)g->h_count, n);
+    else
+        hipLaunchKernelGGL(prior_stage_close_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, g->lp32, g->ldj,
+                           (const double*)nullptr, g->inside, s->p_fin, s->p_logp, g->count, (long long*)g->h_count, n);
+    return pmc_check_launch("prior_stage_close_kernel");
+}
+
+extern "C" int pmc_step_prior_stage(const pmc_step_t* s, void* stream) {
+    if (int e = prior_stage_check(s)) return e;
+    return prior_stage_enqueue(s, stream);
+}
+
 // fill_next = false: the caller enqueues pmc_step_fill_next itself, behind whatever the host waits for first (the pipeline:
 // behind the last lane's pre-step)
 static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream,
                     bool fill_next) {
     if (!s || !rng) return pmc_fail("pmc_step_pre: null argument");
+    if (step_stage(s)) { if (int e = prior_stage_check(s)) return e; }      // (before the pre-step's own launches)
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = s->n;
     const int32_t D = s->D;
@@ -123,6 +241,10 @@ static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double
     // what follows the last kernel whose results the host waits for
     auto finish = [&]() -> int {
         if (s->ev_pre_done) (void)hipEventRecord((hipEvent_t)s->ev_pre_done, st);
+        // the flow / joint prior of a host likelihood: behind everything the host waits for, while it evaluates the
+        // likelihood; in front of the next step's variates, which nothing of this step needs (fill_next = false: the
+        // caller places the stage as it places the fill)
+        if (step_stage(s) && fill_next) { if (int e = prior_stage_enqueue(s, stream)) return e; }
         if (prefill && fill_next) return pmc_step_fill_next(s, rng_in, nu, stream);
         return 0;
     };
@@ -350,10 +472,12 @@ static int step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, dou
         if (!s->blob_cur || !s->blob_prop || !s->accept) return pmc_fail("pmc_step_post: blob_host needs blob_cur, blob_prop and the accept mask");
         if (int e = blob_buffers_check("pmc_step_post", s->blob_prop, s->blob_cur, s->blob_row_bytes)) return e;
     }
+    // logp' is in p_logp: the device prior's table, or the flow / joint prior's stage behind the pre-step
+    const bool dev_logp = s->prior || step_stage(s);
     if (mode == PMC_HANDOVER_COPIES) {
         if (hipMemcpyAsync(s->p_logl, s->h_logl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_post: H2D");
-        if (!s->prior &&     // with a device prior logp' never left the device
+        if (!dev_logp &&     // with a device prior logp' never left the device
             hipMemcpyAsync(s->p_logp, s->h_logp, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_post: H2D");
     }
@@ -363,7 +487,7 @@ static int step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, dou
     prop.u = s->p_u; prop.x = s->p_x; prop.logdetj = s->p_logdetj;
     // host_direct: the accept kernel reads logl' (and a host-evaluated logp') from the pinned host buffers
     prop.logl = mode == PMC_HANDOVER_DIRECT ? s->h_logl : s->p_logl;
-    prop.logp = (mode == PMC_HANDOVER_DIRECT && !s->prior) ? s->h_logp : s->p_logp;
+    prop.logp = (mode == PMC_HANDOVER_DIRECT && !dev_logp) ? s->h_logp : s->p_logp;
     prop.logdetj_flow = s->preconditioned ? s->p_ldjf : nullptr;
     prop.quad = s->quad; prop.quad_prop = s->p_quad;
     int rc;
@@ -413,6 +537,9 @@ extern "C" int pmc_step_post(const pmc_step_t* s, const pmc_rng_t* rng, double b
 // measurement only (bench.py, PMC_BENCH_EPI_STAMPS, a library built with `make DEBUG_HOOKS=1`): device int64 [blocks][8] that
 // the epilogue of the fused launches over n_rows rows stamps, or NULL
 extern "C" void pmc_debug_set_epilogue_stamps(long long* dev, int64_t n_rows) { g_epilogue_stamps = dev; g_epilogue_stamps_n = n_rows; }
+// measurement only (scripts/time_flow_prior.py --host): the C pipeline enqueues every lane's prior stage right behind that
+// lane's pre-step instead of all of them behind the last lane's
+extern "C" void pmc_debug_set_stage_per_lane(int on) { g_stage_per_lane = on != 0; }
 #endif
 
 extern "C" int pmc_stream_synchronize(void* stream) {
@@ -533,14 +660,28 @@ extern "C" int pmc_pipeline_set_comm(void* pp, void* comm) {
 }
 
 static int pipeline_enqueue_pre(pmc_pipeline* p, int64_t step, double nu) {
+#ifdef PMC_DEBUG_HOOKS
+    const bool stage_per_lane = g_stage_per_lane;     // (measurement: every lane's stage right behind its own pre-step)
+#else
+    const bool stage_per_lane = false;
+#endif
     for (int k = 0; k < p->n_lanes; ++k) {
-        pmc_step_t s = *p->lanes[k];
+        pmc_step_ext_t sx = step_copy(p->lanes[k]);
+        pmc_step_t& s = sx.step;
         s.adapt_mode = 1;                                   // (pre: any non-zero mode = read sigma, cn_a, mu from adapt_state)
         p->rng[k].step = (uint64_t)step;
         const int rc = step_pre(&s, &p->rng[k], nu, 0.0, 0.0, p->stream, false);
         if (rc) return rc;
+        if (sx.prior_stage && stage_per_lane) { if (int e = prior_stage_enqueue(&s, p->stream)) return e; }
         if (p->prefetcher)                                  // helper threads read x' once as soon as its completion word shows up
             (void)pmc_prefetcher_submit(p->prefetcher, s.h_done, step + 1, s.h_x, (int64_t)s.n * s.D * 8, p->timeout > 0 ? p->timeout : 1.0);
+    }
+    // the lanes' flow / joint prior (pmc_step_ext_t.prior_stage) behind the LAST lane's pre-step: no lane's x' waits behind
+    // another lane's log_prob (profiles/step_prior.txt has both orders)
+    for (int k = 0; k < p->n_lanes; ++k) {
+        if (!step_stage(p->lanes[k]) || stage_per_lane) continue;
+        const int rc = prior_stage_enqueue(p->lanes[k], p->stream);
+        if (rc) return rc;
     }
     // the variates of step + 1 behind the LAST lane's pre-step: they write the other parity's buffers, nothing reads them
     // before the next step, and no lane's x' waits behind another lane's fill
@@ -565,7 +706,8 @@ extern "C" int pmc_pipeline_next(void* pp, int32_t lane_done, double beta, doubl
     const int last = p->n_lanes - 1;
     double t0 = now_s();
     if (lane_done >= 0) {
-        pmc_step_t s = *p->lanes[lane_done];
+        pmc_step_ext_t sx = step_copy(p->lanes[lane_done]);
+        pmc_step_t& s = sx.step;
         s.adapt_n_other = 0;
         s.adapt_mode = 0;
         if (lane_done == last && !p->comm) {

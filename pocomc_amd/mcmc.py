@@ -14,6 +14,9 @@ stay in HBM as well and move with the accepted walkers in the accept launch.  A 
 pinned host buffer and a launch behind each accept moves the accepted rows, in whichever mode the call takes without blobs.
 ``option_dict["device_logprior"]`` makes the
 prior a GPU callable of the same kind, for priors that are no product of the scipy factors the device has a table for.
+``option_dict["step_prior"]`` (a HOST likelihood, ``function_dict["logprior"]`` the bound ``logpdf`` of a ``FlowPrior`` /
+``JointPrior``): the step evaluates the prior itself, on its own stream and its device copy of x', while the host evaluates
+the likelihood; the host masks on the finite flags only and ``prior.logpdf`` is not called.
 
 
 ``StepEngine`` is the reusable object (bench.py drives it directly); the four
@@ -508,7 +511,9 @@ class StepEngine:
             logdetj=self.p_logdetj.data_ptr(), logl=self.p_logl.data_ptr(), logp=self.p_logp.data_ptr(),
             logdetj_flow=self.p_ldjf.data_ptr() if self.pre else None,
             quad=self.quad.data_ptr() if self.tpcn else None, quad_prop=self.p_quad.data_ptr() if self.tpcn else None)
-        self._step = _lib.pmc_step_t(
+        # (the extended struct: pmc_step_t and, behind it, the prior stage of set_step_prior -- NULL until then)
+        self._step = _lib.pmc_step_ext_t(
+            ext=_lib.PMC_STEP_EXT,
             kind=PMC_KIND_TPCN if self.tpcn else PMC_KIND_RWM, preconditioned=int(self.pre), n=n, D=D,
             inverse_algo=flow.inverse_algo if self.pre else 0,
             maf=C.cast(C.pointer(flow._desc), C.c_void_p) if self.pre else None,
@@ -590,6 +595,10 @@ class StepEngine:
         self._np_blobs = None
         # prior on the device as the caller's GPU callable (set_device_logprior): its values go through pmc_step_prior_rows
         self.device_logprior = False
+        # a flow / joint prior evaluated by the step itself, next to a HOST likelihood (set_step_prior): its pmc_prior_stage_t,
+        # and how many of its per-step counts have been read (they alternate between the two pinned words)
+        self._stage = None
+        self._stage_read = 0
         self._sums_part = None   # (exchange_enqueue: this rank's sums as the exchange's single part)
 
     def __del__(self):
@@ -660,6 +669,39 @@ class StepEngine:
         self._step.prior = C.cast(C.pointer(desc), C.c_void_p)
         self._step.h_logp_out = self.h_logp.data_ptr()
         return True
+
+    def set_step_prior(self, prior):
+        """Evaluate a ``FlowPrior`` / ``JointPrior`` inside the step of a HOST likelihood (``pmc_step_ext_t.prior_stage``): behind
+        the hand-over of x' the pre-step enqueues the prior's three launches on its own stream -- they read ``p_x`` and write
+        ``p_logp`` while the host evaluates the likelihood -- and the accept takes logp' from the device.  The host gets x'
+        and the finite mask as for a host prior and masks on the finite flags only (:meth:`evaluate` with ``log_prior=None``);
+        the rows the prior rules out come back as a count per step (:meth:`stage_ruled_out`).  Not with a device prior
+        table, a device likelihood or the one-launch-per-stage event pass."""
+        assert self.prior_desc is None and not self.device_likelihood
+        with torch.cuda.device(self.device):
+            stage = prior.step_stage(self.n, self.device)
+        self._prior_obj = prior                      # (the descriptor keeps its tensors alive; the engine keeps both)
+        self._stage = stage
+        self._stage_read = 0
+        self._np_stage = stage.counts.numpy()
+        self._pins.append(stage.counts)
+        self._step.prior_stage = C.cast(C.pointer(stage), C.c_void_p)
+
+    def stage_enqueue(self):
+        """The stage behind a pre-step enqueued with ``defer_fill`` (``pmc_step_pre_deferred`` leaves it to the caller, who
+        places it behind the last lane's pre-step like the fill); nothing without :meth:`set_step_prior`."""
+        if self._stage is not None:
+            _lib.check(self.lib.pmc_step_prior_stage(C.byref(self._step), self._stream), "pmc_step_prior_stage")
+
+    def stage_ruled_out(self):
+        """Rows of the step whose sums were just waited for that the host handed to the likelihood although the stage's
+        logp' is not finite (finite x', logp' = -inf): the host's count minus this is the reference's ``n_calls`` increment
+        (``mcmc.py:108-121``).  0 without :meth:`set_step_prior`.  Call once per step, behind the wait for its sums."""
+        if self._stage is None:
+            return 0
+        k = self._stage_read
+        self._stage_read = k + 1
+        return int(self._np_stage[k & 1])
 
     def set_device_likelihood(self):
         """Evaluate the likelihood on the device (:meth:`evaluate_device`): the pre-step writes x' into ``p_xl`` -- the rows
@@ -799,6 +841,7 @@ class StepEngine:
         """:meth:`propose` as one launch per stage, HIP events between them (``_cur_ev``), then the copies of x', the finite
         mask and logp' to the host."""
         lib, n, D = self.lib, self.n, self.D
+        assert self._stage is None, "the event pass has no prior stage (set_step_prior)"
         self._np_clean[0] = -1        # (these launches count no rows: a word left by a composite pre-step is stale)
         self._rng_cur = self._rng(replay)
         st = _lib.stream_handle()
@@ -871,8 +914,8 @@ class StepEngine:
         t0 = time.perf_counter() if tm is not None else 0.0
         if not waited:
             self._wait_pre_step()
-        if self.prior_desc is not None:
-            log_prior = None                          # logp' came back from the device with x'
+        if self.prior_desc is not None or self._stage is not None:
+            log_prior = None                          # logp' came back from the device with x', or stays there (set_step_prior)
         if tm is not None:
             tm["wait_device"] += time.perf_counter() - t0
             log_prior = None if log_prior is None else _timed(log_prior, tm, "prior")
@@ -906,7 +949,11 @@ class StepEngine:
             else:
                 logp_prime[fin] = log_prior(x_prime[fin])
                 logp_prime[~fin] = -np.inf
-        mask = np.isfinite(logp_prime) if all_fin else fin & np.isfinite(logp_prime)
+        if self._stage is not None:
+            # logp' is the step's own (set_step_prior): the finite flags are the host's only mask
+            mask = np.ones(n, dtype=bool) if all_fin else fin
+        else:
+            mask = np.isfinite(logp_prime) if all_fin else fin & np.isfinite(logp_prime)
         whole = bool(mask.all())
         # mcmc.py:117-121 on x'[mask].  Or on the block as it is: with fill_rejected the host rows outside the mask hold the
         # walkers' current x, and a few wasted evaluations cost less than the gather -- those rows' values are dropped, the
@@ -941,9 +988,9 @@ class StepEngine:
             xs = x_prime[lo:hi]
             if log_prior is not None:
                 logp_prime[lo:hi] = log_prior(xs)
-            lp = logp_prime[lo:hi]
-            ok = np.isfinite(lp)
-            keep = self._np_blobs is not None           # (host blobs: the chunks' rows of the pinned buffer are disjoint)
+            # (set_step_prior: logp' is the step's own, every row of an all-finite x' goes to the likelihood)
+            ok = np.ones(hi - lo, dtype=bool) if self._stage is not None else np.isfinite(logp_prime[lo:hi])
+            keep = self._np_blobs is not None          # (host blobs: the chunks' rows of the pinned buffer are disjoint)
             if ok.all():
                 out = log_like(xs)
                 logl_prime[lo:hi] = self._keep_blobs(out, slice(lo, hi), hi - lo) if keep else out[0]
@@ -1244,6 +1291,8 @@ class LanedEngine:
             e.host_timers = self.host_timers
             e.propose(None, nu, step=e.step_idx + ahead, defer_fill=True)
         for e in self.lanes:
+            e.stage_enqueue()
+        for e in self.lanes:
             e.fill_next(nu)
 
     def resume_pipeline(self, nu):
@@ -1351,6 +1400,13 @@ class LanedEngine:
 
     def set_device_prior(self, prior):
         return all(self._each(lambda e: e.set_device_prior(prior)))
+
+    def set_step_prior(self, prior):
+        """``StepEngine.set_step_prior`` for every lane: each gets a stage and a workspace set of its own."""
+        self._each(lambda e: e.set_step_prior(prior))
+
+    def stage_ruled_out(self):
+        return sum(e.stage_ruled_out() for e in self.lanes)
 
     def set_mu(self, mu):
         for e in self.lanes:
@@ -1469,6 +1525,25 @@ def _counted(fn, rows):
     return call
 
 
+def _step_prior_owner(option_dict, log_prior):
+    """The prior whose stage the step evaluates itself (``option_dict["step_prior"]``): the object ``log_prior`` is the bound
+    ``logpdf`` of, where it has a ``step_stage`` method (``FlowPrior``, ``JointPrior``); None without the option.  An option
+    that cannot be served raises ValueError here, before any device call -- the route is never taken or left silently."""
+    if not option_dict.get("step_prior", False):
+        return None
+    if option_dict.get("device_likelihood", False):
+        raise ValueError("step_prior: the stage is for a host likelihood; with device_likelihood the prior is called on the "
+                         "device through device_prior=True (option device_logprior)")
+    if option_dict.get("group") is not None or _sharded(None):
+        raise ValueError("step_prior: sharded walkers (a process group) are not served: run it on one process")
+    owner = getattr(log_prior, "__self__", None)
+    if owner is None or not callable(getattr(owner, "step_stage", None)):
+        what = type(owner).__name__ if owner is not None else getattr(log_prior, "__name__", type(log_prior).__name__)
+        raise ValueError(f"step_prior: function_dict['logprior'] must be the bound logpdf of a prior with a step_stage "
+                         f"method (pocomc_amd.FlowPrior, JointPrior), got {what}")
+    return owner
+
+
 def _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior, whole_set, device_like,
                  device_logprior=False):
     """The engine of one kernel call, configured from ``option_dict``; ``whole_set``: blobs / traces / replayed variates
@@ -1503,6 +1578,8 @@ def _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_pr
     owner = getattr(log_prior, "__self__", None)
     if owner is not None and option_dict.get("device_prior", True) and hasattr(owner, "device_descriptor"):
         eng.set_device_prior(owner)                 # Prior.logpdf on the device when the Prior gives a descriptor
+    if _step_prior_owner(option_dict, log_prior) is not None:
+        eng.set_step_prior(owner)                   # a flow / joint prior on the step's own stream (_run drops log_prior)
     if device_like:
         eng.set_device_likelihood()
         if device_logprior and eng.prior_desc is None:      # (a Prior with a device descriptor keeps precedence)
@@ -1537,12 +1614,15 @@ def _step_device_likelihood_sharded(eng, ad, comm, beta, nu, n_total, log_prior,
     return eng.calls_reached(), sums
 
 
+# (stage_ruled_out: with a prior stage the host's rows minus the rows the stage ruled out, read behind the wait for the sums)
 def _step_pipelined(eng, ad, beta, nu, n_total, log_prior, log_like, more):       # lanes on one stream, sigma / mu on the device
-    return eng.step_pipelined(beta, nu, ad.coefficients(), n_total, log_prior, log_like, more=more)
+    calls, sums = eng.step_pipelined(beta, nu, ad.coefficients(), n_total, log_prior, log_like, more=more)
+    return calls - eng.stage_ruled_out(), sums
 
 
 def _step_laned(eng, ad, beta, nu, log_prior, log_like, more):                     # lanes on their streams, sigma / mu from the host
-    return eng.step(ad.sigma, nu, beta, log_prior, log_like)
+    calls, sums = eng.step(ad.sigma, nu, beta, log_prior, log_like)
+    return calls - eng.stage_ruled_out(), sums
 
 
 def _step_plain(eng, ad, beta, nu, log_prior, log_like, replay, blobs, want_mask, more):
@@ -1558,7 +1638,7 @@ def _step_plain(eng, ad, beta, nu, log_prior, log_like, replay, blobs, want_mask
     if blobs is not None:
         mask = eng.h_accept.numpy().astype(bool)
         blobs[mask] = blobs_prime[mask]
-    return calls, sums
+    return calls - eng.stage_ruled_out(), sums
 
 
 def _trace_record(eng, ad):
@@ -1623,9 +1703,15 @@ def _run(kind, state_dict, function_dict, option_dict, replay=None, trace=None):
     tensor_blobs = have_blobs and not device_like and isinstance(blobs, torch.Tensor)
     if tensor_blobs and (replay is not None or trace is not None):
         raise ValueError("blobs as a device tensor do not combine with replayed variates or traces: pass them as a numpy array")
+    # a flow / joint prior evaluated by the step itself (pmc_step_ext_t.prior_stage); checked before the device is touched
+    step_prior = _step_prior_owner(option_dict, log_prior) is not None
+    if step_prior and (replay is not None or trace is not None):
+        raise ValueError("step_prior: replayed variates and traces keep the prior on the host (leave step_prior out)")
     eng, pipelined = _make_engine(kind, n_walkers, n_dim, flow, scaler, seed, option_dict, log_prior,
                                   whole_set=(have_blobs and not tensor_blobs) or trace is not None or replay is not None,
                                   device_like=device_like, device_logprior=device_logprior)
+    if step_prior:
+        log_prior = None                           # (the engine evaluates it: the host masks on the finite flags only)
     laned = isinstance(eng, LanedEngine)
     lanes = eng.lanes if laned else [eng]
     eng.load_state(u, x, logdetj, logl, logp)

@@ -15,7 +15,10 @@ MCMC step calls on the device like a device likelihood (``Sampler(device_likelih
 prior's box, evaluated by two launches around the flow's own forward kernel (``csrc/flow_prior.hip``).
 
 ``JointPrior`` puts such a flow prior on some columns of ``x`` and a table of scipy factors on the others, in the same number
-of launches (``csrc/joint_prior.hip``)."""
+of launches (``csrc/joint_prior.hip``).
+
+Next to a HOST likelihood both can be evaluated by the MCMC step itself (``step_stage``, kernel option ``step_prior``): the same
+three launches on the step's stream, on the device's copy of x', while the host evaluates the likelihood."""
 from __future__ import annotations
 
 import numpy as np
@@ -260,6 +263,49 @@ class DevicePrior:
         return len(self._bounds)
 
 
+def _step_stage(owner, flow_prior, n, device, joint=None):
+    """``pmc_prior_stage_t`` of ``owner`` (a ``FlowPrior``, or a ``JointPrior`` with ``joint = (flow_cols, rdesc, rest_cols)``)
+    for the ``n`` rows of one step engine, with one workspace set of its own.  The descriptor keeps what it points into alive
+    (``_keep``): the engine that holds it holds the tensors, the prior's descriptors and the prior."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .mcmc import _on_device, _pinned_take
+    flow, n = flow_prior.flow, int(n)
+    if n < 1:
+        raise ValueError(f"{type(owner).__name__}.step_stage: n must be at least 1, got {n}")
+    dev = torch.device(flow.device)
+    if device is not None:
+        _on_device(torch.empty(0, device=dev), device, f"{type(owner).__name__}.step_stage")
+    Df = flow_prior.dim
+    with torch.cuda.device(dev):
+        ws = dict(u32=torch.empty(n, Df, dtype=torch.float32, device=dev),
+                  z=torch.empty(n, Df, dtype=torch.float32, device=dev),
+                  lp32=torch.empty(n, dtype=torch.float32, device=dev),
+                  ldj=torch.empty(n, dtype=torch.float64, device=dev),
+                  rest_logp=torch.empty(n, dtype=torch.float64, device=dev) if joint is not None else None,
+                  inside=torch.empty(n, dtype=torch.int32, device=dev),
+                  count=torch.zeros(2, dtype=torch.int64, device=dev))
+        image, per_t = None, 0
+        if flow.precision == "bf16":
+            _, image, per_t = flow._bf16_image()
+    h_count = _pinned_take((2,), torch.int64)
+    h_count.zero_()
+    flow_cols, rdesc, rest_cols = joint if joint is not None else (None, None, None)
+    desc = _lib.pmc_prior_stage_t(
+        scaler=C.cast(C.pointer(flow_prior._sdesc), C.c_void_p), maf=C.cast(C.pointer(flow._desc), C.c_void_p),
+        image16=image.data_ptr() if image is not None else None, image_per_transform=int(per_t),
+        flow_cols=flow_cols.data_ptr() if joint is not None else None,
+        rest=C.cast(C.pointer(rdesc), C.c_void_p) if joint is not None else None,
+        rest_cols=rest_cols.data_ptr() if joint is not None else None,
+        u32=ws["u32"].data_ptr(), z=ws["z"].data_ptr(), lp32=ws["lp32"].data_ptr(), ldj=ws["ldj"].data_ptr(),
+        rest_logp=ws["rest_logp"].data_ptr() if joint is not None else None, inside=ws["inside"].data_ptr(),
+        count=ws["count"].data_ptr(), h_count=h_count.data_ptr())
+    desc._keep = (owner, ws, image, joint)
+    desc.counts = h_count             # (the pinned words: the engine reads them, and recycles the tensor with its own)
+    return desc
+
+
 class FlowPrior:
     """The density a finished run leaves behind, as a prior: a trained ``Flow`` and a fitted diagonal ``Reparameterize``,
 
@@ -495,6 +541,13 @@ class FlowPrior:
             raise ValueError(f"FlowPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
         return self.logpdf_device(torch.from_numpy(x).to(self.flow.device)).cpu().numpy()
 
+    def step_stage(self, n, device=None):
+        """``pmc_prior_stage_t`` for a step engine of ``n`` rows on ``device`` (None: the flow's): the MCMC step of a HOST
+        likelihood then evaluates this prior itself, on its own stream, from its device copy of x' (kernel option
+        ``step_prior``, ``StepEngine.set_step_prior``) -- the three launches of ``logpdf_device``, the same bits.  One
+        workspace set per call; the descriptor keeps it and this prior alive."""
+        return _step_stage(self, self, n, device)
+
     # ----------------------------------------------------------------- draws
     def _inside(self, x):
         lo = np.where(np.isfinite(self.scaler.low), self.scaler.low, -np.inf)
@@ -685,6 +738,11 @@ class JointPrior:
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"JointPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
         return self.logpdf_device(torch.from_numpy(x).to(self.flow_prior.flow.device)).cpu().numpy()
+
+    def step_stage(self, n, device=None):
+        """``FlowPrior.step_stage`` for the joint prior: the descriptor carries the column maps and the table as well."""
+        return _step_stage(self, self.flow_prior, n, device,
+                           joint=(self._dev["flow_cols"], self._rdesc, self._dev["rest_cols"]))
 
     # ----------------------------------------------------------------- draws
     def rvs(self, size=1):

@@ -145,7 +145,8 @@ class Sampler:
                  train_frequency=None, precondition=True, dynamic=True, metric="ess", n_prior=None,
                  sample="tpcn", n_steps=None, n_max_steps=None, resample="mult", output_dir=None,
                  output_label=None, random_state=None, n_ess=None, group=None, mcmc_options=None,
-                 device_likelihood=False, device_blobs=False, device_prior=False, student_fit="reference"):
+                 device_likelihood=False, device_blobs=False, device_prior=False, student_fit="reference",
+                 step_prior=False):
         """Arguments and defaults of ``pocomc/sampler.py:154-185``, plus
 
         ``flow``          a name (``"nsf6"``, ``"maf3"`` ...) or a ready ``Flow``, taken as it is with everything it was built
@@ -187,6 +188,13 @@ class Sampler:
                           scipy factors (``Prior(dists)``, which the device evaluates from a table by itself).  The MCMC
                           steps then never hand x' to the host; warm-up and evidence call the same function on uploaded
                           rows.  Sharded: called on every rank with that rank's rows, the same function on every rank.
+        ``step_prior``    (a HOST likelihood, a ``FlowPrior`` or ``JointPrior``, one process) the MCMC steps evaluate the prior
+                          themselves: its three launches run on the step's stream, on the device's copy of x', while the
+                          host evaluates the likelihood (kernel option ``step_prior``, ``pmc_step_ext_t.prior_stage``) -- no
+                          upload of x', no download of logp', no wait for the prior in front of the likelihood.  The same
+                          trajectory as without it, bit for bit; a row the prior rules out (-inf) still reaches the
+                          likelihood, and its value is dropped: the likelihood must be row-wise and free of side effects.
+                          Warm-up and evidence call ``prior.logpdf`` as ever.  With a device likelihood use ``device_prior``;
         ``student_fit``   how the Student-t geometry of the MCMC step is fitted (``pocomc_amd/geometry.py``):
                           ``"reference"`` (default) as the reference does, which always ends at ``nu = 1e6`` -- a Gaussian
                           pCN step; ``"em"`` by EM on the device (``pmc_student_em``, ``n_dim <= 128``), which gives
@@ -249,6 +257,14 @@ class Sampler:
         if self.device_prior and not callable(getattr(prior, "logpdf_device", None)):
             raise ValueError(f"device_prior=True needs a prior with a logpdf_device method (pocomc_amd.DevicePrior), "
                              f"got {type(prior).__name__}")
+        self.step_prior = bool(step_prior)
+        if self.step_prior and self.device_likelihood:
+            raise ValueError("step_prior=True is for a host likelihood: with device_likelihood=True use device_prior=True")
+        if self.step_prior and not callable(getattr(prior, "step_stage", None)):
+            raise ValueError(f"step_prior=True needs a prior with a step_stage method (pocomc_amd.FlowPrior, JointPrior), "
+                             f"got {type(prior).__name__}")
+        if self.step_prior and self.ranks.world > 1:
+            raise ValueError("step_prior=True does not run on sharded walkers (a process group)")
         # (blob_shape, dtype name) of the device blobs, or blob_shape of a vectorised host likelihood's: fixed by the first call
         self._blob_spec = None
         # blobs of a vectorised HOST likelihood: it returns (logl, blobs) numpy on whole blocks; the walkers' and the pool's
@@ -517,6 +533,8 @@ class Sampler:
         if self.device_prior:
             funcs["logprior"] = self.prior.logpdf_device
             opts["device_logprior"] = True
+        if self.step_prior:
+            opts["step_prior"] = True
         if self.world > 1:
             opts.update(group=self.group, shard_offset=sl.start)
         res = _KERNELS[(bool(self.preconditioned), self.sample)](state, funcs, opts)

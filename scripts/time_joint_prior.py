@@ -3,6 +3,7 @@ dimensions, a flow prior on 24 of them and scipy factors on the other 8, maf3 an
 
     python scripts/time_joint_prior.py [--walkers 10000] [--dim 32] [--flow-dim 24] [--steps 200] [--repeats 3] [--calls 200]
                                        [--out FILE]
+    python scripts/time_joint_prior.py --host [--walkers 10000] [--dim 32] [--flow-dim 24] [--steps 200] [--repeats 3]
 
 The two priors compute the same density:
   * ``joint``:     ``JointPrior.logpdf_device`` -- three launches, one pass over x;
@@ -16,7 +17,11 @@ Per flow:
     (``device_likelihood=True``) and the prior inside the step (``device_logprior``): host clock around the call, the two
     priors alternate, one warm-up call each, median of --repeats.
 The flows carry their initial parameters: the kernels' time does not depend on the values.  One JSON line; --out writes a
-readable table as well."""
+readable table as well.
+
+--host: the joint prior next to a HOST likelihood -- the modes and the settings of ``scripts/time_flow_prior.py --host``
+(``uniform_table``, ``host_route``, ``step_prior`` and, with the measurement library, ``step_prior_per_lane``), one JSON
+line per process."""
 import argparse
 import json
 import math
@@ -75,6 +80,31 @@ def event_us(fn, calls, repeats):
     return float(np.median(out)), out
 
 
+def host_main(args):
+    from scipy.stats import uniform
+    import pocomc_amd as pc
+    from pocomc_amd import _lib
+    from time_flow_prior import host_step_rates
+    N, D, Df = args.walkers, args.dim, args.flow_dim
+    columns = np.random.default_rng(0).permutation(D)[:Df]
+    flow_cols, _ = pc.JointPrior.layout(columns, Df, D - Df)
+    rest = pc.Prior(rest_factors(D - Df)[0], device=True)
+    table = pc.Prior([uniform(-10, 20)] * D)
+    rng = np.random.default_rng(0)
+    x = rng.uniform(-2.0, 2.0, size=(N, D))
+    xs = rng.uniform(-2.0, 2.0, size=(4 * N, D))
+    out = dict(mode="host likelihood", walkers=N, dim=D, flow_dim=Df, steps=args.steps, repeats=args.repeats,
+               kind="preconditioned_pcn", library=os.path.basename(_lib.LIB_PATH), gpu=torch.cuda.get_device_name(0), flows={})
+    for name in args.flows.split(","):
+        block_scaler = pc.Reparameterize(Df, bounds=np.array([[-10.0, 10.0]] * Df))
+        block_scaler.fit(xs[:, flow_cols])
+        joint = pc.JointPrior(pc.FlowPrior(pc.Flow(Df, name, seed=0), block_scaler), flow_cols.tolist(), rest)
+        priors = dict(host_route=(joint, {}, False), step_prior=(joint, dict(step_prior=True), False),
+                      step_prior_per_lane=(joint, dict(step_prior=True), True))
+        out["flows"][name] = host_step_rates(name, priors, table, x, xs, args)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--walkers", type=int, default=10000)
@@ -85,7 +115,10 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--flows", default="maf3,nsf6")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--host", action="store_true", help="the joint prior next to a host likelihood (see the module's text)")
     args = ap.parse_args()
+    if args.host:
+        return host_main(args)
     import pocomc_amd as pc
     from pocomc_amd import mcmc as pmcmc
     from pocomc_amd.geometry import Geometry
