@@ -843,7 +843,10 @@ int pmc_step_prior_rows(const pmc_step_t* s, const void* logp, int logp_is_f32, 
  * variates of the next step.
  * Refused before anything is launched, each with a text of its own: a struct without prior_stage; with prior, prior_rows or
  * lik_x set as well; NULL descriptors, workspaces or count words; n < 1; p_x, p_fin or p_logp missing; a width that
- * pmc_flow_prior_pre / pmc_joint_prior_pre refuses (their checks, their texts) or that is not the step's D. */
+ * pmc_flow_prior_pre / pmc_joint_prior_pre refuses (their checks, their texts) or that is not the step's D.
+ * A struct announced as pmc_step_ext2_t (below, ext = PMC_STEP_EXT2) with blocks_stage set: the same place on the stream
+ * and the same count protocol for the blocks form of the joint prior -- pmc_joint_blocks_pre on p_x, the blocks' forward
+ * calls in block order, a closing kernel with pmc_joint_blocks_post's join; see pmc_step_ext2_t for its refusals. */
 int pmc_step_prior_stage(const pmc_step_t* s, void* stream);
 /* The adaptation of pmc_step_t.adapt_state as a launch of its own, for walker sets whose sums come in parts
  * (row ranges stepped one after the other, mcmc.LanedEngine; ranks, after the all-reduce):
@@ -1110,6 +1113,91 @@ int pmc_joint_prior_pre(const pmc_scaler_t* s, const int32_t* flow_cols, const p
  * flow's log_prob of u32), ldj, rest_logp f64 [n], inside int32 [n], logp f64 [n]. */
 int pmc_joint_prior_post(const float* lp32, const double* ldj, const double* rest_logp, const int32_t* inside, double* logp,
                          int64_t n, void* stream);
+
+/* ----------------------------------------------------------------- joint prior, several flow blocks */
+
+/* B flow priors on disjoint blocks of columns and an optional table on the others (pocomc_amd.JointPrior, the blocks form),
+ * D = sum_b Df_b + Dr:
+ *   log p(x) = sum_b [flow_b.log_prob(u_b(x_{F_b})) - log|dx_{F_b}/du_b|] + sum_m dist_m.logpdf(x[rest_cols[m]]),
+ * as B + 2 launches and one pass over x: pmc_joint_blocks_pre, every block's own forward call on its piece of u32 (in block
+ * order), pmc_joint_blocks_post.  Appended within ABI 9: new entries and a new struct only.
+ *
+ * scaler[b]: block b's scaler, a host struct that points to device arrays (scaler[b]->D = Df_b >= 2; bc is not read); the
+ * blocks may differ in transform (logit) and in the affine part (scale).  cols[b]: int32 [Df_b], device memory: the column of
+ * x that is block b's feature k.  rest / rest_cols: the table and its columns (int32 [Dr], device memory) as for
+ * pmc_joint_prior_pre, or both NULL: no table, Dr = 0.  All maps together are a permutation of 0 .. D - 1 (the caller's to
+ * check: JointPrior.layout_blocks); an entry outside [0, D) is not followed, every row of the call's blocks then gets
+ * inside = 0.  Entries b >= n_blocks are not read. */
+#define PMC_JOINT_BLOCKS_MAX 8
+typedef struct pmc_joint_blocks {
+    int32_t n_blocks;             /* 1 .. PMC_JOINT_BLOCKS_MAX */
+    int32_t reserved;
+    const pmc_scaler_t* scaler[PMC_JOINT_BLOCKS_MAX];
+    const int32_t* cols[PMC_JOINT_BLOCKS_MAX];
+    const pmc_prior_t* rest;      /* or NULL */
+    const int32_t* rest_cols;     /* or NULL (with rest) */
+} pmc_joint_blocks_t;
+
+/* One launch with pmc_joint_prior_pre's shape and stride contract (64 rows of all D columns through LDS, the two coalesced
+ * layouts (D, 1) and (1, n), one thread per slot, one lane per row for the sums).  The slots: block 0's features, block
+ * 1's, ..., then the rest factors.
+ * u32 f32: block b's [n][Df_b] array starts n * (Df_0 + ... + Df_{b-1}) floats into u32 (sum_b n * Df_b floats in all).
+ * ldj f64 [B][n].  rest_logp f64 [n]: not written, and may be NULL, without a table.  inside int32 [n]: ONE flag per row:
+ * every x_j finite, every block's columns pass pmc_flow_prior_pre's test, no rest term NaN.
+ * On every row with inside == 1, block b's piece of u32 and ldj[b] are what pmc_flow_prior_pre writes for the gathered
+ * C-contiguous block, and rest_logp what pmc_prior_logpdf gives on the gathered rest, bit for bit.  A row with inside == 0
+ * is zeros in every block's u32 and -inf in rest_logp.  A row's bits depend on its values alone.
+ * Refused before anything is launched or written, each with a text of its own: a NULL descriptor or NULL fields; n_blocks
+ * outside 1 .. 8; a block with Df_b < 2; sum Df_b + Dr > 157 ("n_dim too large"; LDS as for pmc_joint_prior_pre with Df the
+ * blocks' sum); rest->n_extended > 0 without rest->par; a scaler with scale and no mu / sigma; a NULL array, a negative
+ * count or stride; more than 2^31 - 1 blocks of 64 rows.  n == 0 returns 0 and reads no array. */
+int pmc_joint_blocks_pre(const pmc_joint_blocks_t* j, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
+                         float* u32, double* ldj, double* rest_logp, int32_t* inside, void* stream);
+
+/* v = (double)lp32[0][r] - ldj[0][r]; v = v + ((double)lp32[b][r] - ldj[b][r]) for b = 1 .. n_blocks - 1; with rest_logp
+ * non-NULL v = v + rest_logp[r]; logp[r] = v where inside[r] and v is finite, -inf everywhere else: never NaN, never +inf.
+ * lp32 f32 [n_blocks][n] (block b's log_prob of its piece of u32), ldj f64 [n_blocks][n], rest_logp f64 [n] or NULL.  One
+ * block: pmc_joint_prior_post's bits with a table, pmc_flow_prior_post's without. */
+int pmc_joint_blocks_post(int32_t n_blocks, const float* lp32, const double* ldj, const double* rest_logp,
+                          const int32_t* inside, double* logp, int64_t n, void* stream);
+
+/* The blocks form inside the step of a HOST likelihood: what pmc_prior_stage_t is for one flow block, for several.  The
+ * descriptor of pmc_joint_blocks_pre by value, every block's flow (maf[b]; precision="bf16": its image and per_t, else NULL
+ * and 0) and the workspaces for the n rows of one pmc_step_t: u32 and ldj laid out as pmc_joint_blocks_pre writes them,
+ * lp32 f32 [n_blocks][n], ONE z of n * max_b Df_b floats (the flows run one after another on the stream and nobody reads
+ * z), rest_logp f64 [n] (NULL without a table), inside int32 [n]; count / h_count: pmc_prior_stage_t's count protocol,
+ * unchanged.  Entries b >= blocks.n_blocks are not read. */
+typedef struct pmc_prior_blocks_stage {
+    pmc_joint_blocks_t blocks;
+    const pmc_maf_t* maf[PMC_JOINT_BLOCKS_MAX];
+    const uint16_t* image16[PMC_JOINT_BLOCKS_MAX];
+    int64_t image_per_transform[PMC_JOINT_BLOCKS_MAX];
+    float* u32;
+    float* z;
+    float* lp32;
+    double* ldj;
+    double* rest_logp;
+    int32_t* inside;
+    unsigned long long* count;
+    int64_t* h_count;
+} pmc_prior_blocks_stage_t;
+
+/* pmc_step_ext_t with one more field behind it, announced by step.ext = PMC_STEP_EXT2 (callers with ext = 0 or
+ * ext = PMC_STEP_EXT read exactly what they read before: nothing behind the struct they allocated).  At most one of the
+ * two pointers is non-NULL; with both set every call that would place the stage refuses it.  blocks_stage stands where
+ * prior_stage stands: pmc_step_prior_stage, pmc_step_pre and the pipeline enqueue it behind the hand-over (the pipeline:
+ * behind the LAST lane's pre-step, in front of the fills) as pmc_joint_blocks_pre on p_x, the blocks' forward calls in
+ * block order and a closing kernel that writes p_logp -- pmc_joint_blocks_post's join where p_fin != 0, -inf elsewhere --
+ * and counts the rows with p_fin != 0 and no finite logp' into h_count[launch & 1]; pmc_step_post takes logp' from p_logp.
+ * The stage check refuses, before any launch: NULL workspaces, a block without its scaler or flow, a width that is not
+ * the step's D, a flow whose width is not its scaler's, both pointers set, and what pmc_joint_blocks_pre refuses, in its
+ * words. */
+#define PMC_STEP_EXT2 2
+typedef struct pmc_step_ext2 {
+    pmc_step_t step;
+    const pmc_prior_stage_t* prior_stage;
+    const pmc_prior_blocks_stage_t* blocks_stage;
+} pmc_step_ext2_t;
 
 #ifdef __cplusplus
 }

@@ -125,9 +125,32 @@ class pmc_step_ext_t(pmc_step_t):
     _fields_ = [("prior_stage", c_p)]
 
 
+PMC_STEP_EXT2 = 2
+
+
+class pmc_step_ext2_t(pmc_step_ext_t):
+    """``pmc_step_ext_t`` with the blocks form's stage behind it, announced by ``ext = PMC_STEP_EXT2``."""
+    _fields_ = [("blocks_stage", c_p)]
+
+
 class pmc_prior_stage_t(C.Structure):
     _fields_ = [("scaler", c_p), ("maf", c_p), ("image16", c_p), ("image_per_transform", C.c_int64),
                 ("flow_cols", c_p), ("rest", c_p), ("rest_cols", c_p),
+                ("u32", c_p), ("z", c_p), ("lp32", c_p), ("ldj", c_p), ("rest_logp", c_p), ("inside", c_p),
+                ("count", c_p), ("h_count", c_p)]
+
+
+PMC_JOINT_BLOCKS_MAX = 8
+
+
+class pmc_joint_blocks_t(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("reserved", C.c_int32), ("scaler", c_p * PMC_JOINT_BLOCKS_MAX),
+                ("cols", c_p * PMC_JOINT_BLOCKS_MAX), ("rest", c_p), ("rest_cols", c_p)]
+
+
+class pmc_prior_blocks_stage_t(C.Structure):
+    _fields_ = [("blocks", pmc_joint_blocks_t), ("maf", c_p * PMC_JOINT_BLOCKS_MAX),
+                ("image16", c_p * PMC_JOINT_BLOCKS_MAX), ("image_per_transform", C.c_int64 * PMC_JOINT_BLOCKS_MAX),
                 ("u32", c_p), ("z", c_p), ("lp32", c_p), ("ldj", c_p), ("rest_logp", c_p), ("inside", c_p),
                 ("count", c_p), ("h_count", c_p)]
 
@@ -248,6 +271,8 @@ SIGNATURES = {
     "pmc_flow_prior_post": (C.c_int, [c_p, c_p, c_p, c_p, i64, c_p]),
     "pmc_joint_prior_pre": (C.c_int, [P(pmc_scaler_t), c_p, P(pmc_prior_t), c_p, c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p]),
     "pmc_joint_prior_post": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, c_p]),
+    "pmc_joint_blocks_pre": (C.c_int, [P(pmc_joint_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p]),
+    "pmc_joint_blocks_post": (C.c_int, [i32, c_p, c_p, c_p, c_p, c_p, i64, c_p]),
 }
 
 _lib = None

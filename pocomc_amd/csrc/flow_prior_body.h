@@ -59,5 +59,15 @@ __device__ __forceinline__ double joint_prior_join(float lp32, double ldj, doubl
     const double v = ((double)lp32 - ldj) + rest_logp;
     return (inside && isfinite(v)) ? v : -INFINITY;
 }
+// Several flow blocks (lp32 / ldj: [n_blocks][n], block b's row r at [b * n + r]) and an optional table (rest_logp NULL:
+// none): the blocks' terms added left to right, then the table's.  One block: joint_prior_join with a table,
+// flow_prior_join without one.
+__device__ __forceinline__ double joint_blocks_join(int n_blocks, const float* lp32, const double* ldj,
+                                                    const double* rest_logp, int inside, int64_t n, int64_t r) {
+    double v = (double)lp32[r] - ldj[r];
+    for (int b = 1; b < n_blocks; ++b) v = v + ((double)lp32[(int64_t)b * n + r] - ldj[(int64_t)b * n + r]);
+    if (rest_logp) v = v + rest_logp[r];
+    return (inside && isfinite(v)) ? v : -INFINITY;
+}
 
 #endif

@@ -99,5 +99,8 @@ int pmc_accept_adapt(int kind, int preconditioned, pmc_state_t* cur, const pmc_p
                      const pmc_done_t* done, void* workspace, int64_t n, int32_t D, void* stream,
                      const pmc_adapt_args* adapt, const pmc_gate_args* gate = nullptr,
                      const pmc_blob_args* blob = nullptr);
+// what pmc_joint_blocks_pre refuses of its descriptor (joint_prior.hip), for the step's stage check as well: 0 with the
+// blocks' total width in *DF and the table's in *Dr (either may be NULL), or pmc_fail's code with that entry's text
+int pmc_joint_blocks_check(const pmc_joint_blocks_t* j, int* DF, int* Dr);
 
 #endif

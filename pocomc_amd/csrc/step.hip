@@ -3,7 +3,8 @@
 // host-side driver spends its time in the user's black boxes instead of in dispatch overhead.
 //
 //   pmc_step_pre :  [H2D mu] -> propose -> flow inverse (one launch for the affine flows) -> scaler inverse [+ prior] -> D2H x', finite
-//                   [-> the flow / joint prior's three launches on p_x, pmc_step_ext_t.prior_stage]
+//                   [-> the flow / joint prior's three launches on p_x, pmc_step_ext_t.prior_stage; the blocks form's B + 2,
+//                       pmc_step_ext2_t.blocks_stage]
 //   pmc_step_post:  H2D logl', logp' -> accept + reductions -> D2H sums
 //
 // With a likelihood on the device (pmc_step_t.lik_x) x' goes to lik_x instead of the host, the caller's likelihood fills
@@ -47,14 +48,21 @@ extern "C" int pmc_step_fill_next(const pmc_step_t* s, const pmc_rng_t* rng, dou
 }
 
 // the fields behind a pmc_step_t that is the head of a pmc_step_ext_t (step.ext says so; nothing behind it is read otherwise)
+// (pmc_step_ext2_t begins as pmc_step_ext_t does: prior_stage sits at one offset in both)
 static const pmc_prior_stage_t* step_stage(const pmc_step_t* s) {
-    return s->ext == PMC_STEP_EXT ? reinterpret_cast<const pmc_step_ext_t*>(s)->prior_stage : nullptr;
+    return (s->ext == PMC_STEP_EXT || s->ext == PMC_STEP_EXT2) ? reinterpret_cast<const pmc_step_ext_t*>(s)->prior_stage : nullptr;
 }
+static const pmc_prior_blocks_stage_t* step_blocks_stage(const pmc_step_t* s) {
+    return s->ext == PMC_STEP_EXT2 ? reinterpret_cast<const pmc_step_ext2_t*>(s)->blocks_stage : nullptr;
+}
+// a stage of either kind (pmc_step_ext_t.prior_stage, pmc_step_ext2_t.blocks_stage)
+static bool step_has_stage(const pmc_step_t* s) { return step_stage(s) || step_blocks_stage(s); }
 // a copy the caller may change: the head, and the fields behind it where there are any
-static pmc_step_ext_t step_copy(const pmc_step_t* s) {
-    pmc_step_ext_t c{};
+static pmc_step_ext2_t step_copy(const pmc_step_t* s) {
+    pmc_step_ext2_t c{};
     c.step = *s;
     c.prior_stage = step_stage(s);
+    c.blocks_stage = step_blocks_stage(s);
     return c;
 }
 
@@ -156,10 +164,104 @@ __global__ __launch_bounds__(256) void prior_stage_close_kernel(const float* __r
     }
 }
 
+// The blocks form of the joint prior (pmc_step_ext2_t.blocks_stage): the closing kernel of the stage above with the join
+// over several blocks (joint_blocks_join: lp32 / ldj [n_blocks][n], rest_logp NULL without a table) -- the same count
+// protocol, word for word.
+__global__ __launch_bounds__(256) void prior_blocks_stage_close_kernel(int n_blocks, const float* __restrict__ lp32,
+                                                                       const double* __restrict__ ldj,
+                                                                       const double* __restrict__ rest_logp,
+                                                                       const int32_t* __restrict__ inside,
+                                                                       const int32_t* __restrict__ fin, double* __restrict__ logp,
+                                                                       unsigned long long* __restrict__ count,
+                                                                       long long* __restrict__ h_count, int64_t n) {
+    __shared__ unsigned wave_bad[4];
+    const int tid = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+    bool bad = false;
+    if (r < n) {
+        double v = -INFINITY;
+        if (fin[r]) {
+            v = joint_blocks_join(n_blocks, lp32, ldj, rest_logp, inside[r], n, r);
+            bad = !isfinite(v);
+        }
+        logp[r] = v;
+    }
+    const unsigned nb = (unsigned)__popcll(__ballot(bad));
+    if ((tid & 63) == 0) wave_bad[tid >> 6] = nb;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long mine = wave_bad[0] + wave_bad[1] + wave_bad[2] + wave_bad[3];
+        const unsigned long long old = __hip_atomic_fetch_add(count, (1ull << 32) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)(old >> 32) == gridDim.x - 1) {
+            const unsigned long long launch = count[1];
+            __hip_atomic_store(h_count + (launch & 1), (long long)((old & 0xffffffffull) + mine), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+            count[1] = launch + 1;
+            __hip_atomic_store(count, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// what the step refuses of a stage of either kind (the texts of prior_stage_check below)
+static int stage_step_check(const pmc_step_t* s) {
+    if (s->prior) return pmc_fail("pmc_step_prior_stage: the step has a device prior table as well (prior): one of the two");
+    if (s->prior_rows) return pmc_fail("pmc_step_prior_stage: the step has a prior that is a GPU callable as well (prior_rows): one of the two");
+    if (s->lik_x) return pmc_fail("pmc_step_prior_stage: the stage is for a host likelihood (lik_x is set: call the prior on lik_x instead)");
+    return 0;
+}
+
+// the blocks branch of prior_stage_check: the same order -- the step, the stage's pointers, the rows, the widths
+static int blocks_stage_check(const pmc_step_t* s, const pmc_prior_blocks_stage_t* g) {
+    if (int e = stage_step_check(s)) return e;
+    const int B = g->blocks.n_blocks;
+    if (B < 1 || B > PMC_JOINT_BLOCKS_MAX) return pmc_fail("pmc_joint_blocks_pre: n_blocks must lie in 1 .. 8");
+    for (int b = 0; b < B; ++b)
+        if (!g->blocks.scaler[b] || !g->maf[b]) return pmc_fail("pmc_step_prior_stage: every block needs its scaler and its flow");
+    if (!g->u32 || !g->z || !g->lp32 || !g->ldj || !g->inside) return pmc_fail("pmc_step_prior_stage: null workspace (u32, z, lp32, ldj, inside)");
+    if (!g->count || !g->h_count) return pmc_fail("pmc_step_prior_stage: needs the device counter and the pinned host words");
+    if (g->blocks.rest && !g->rest_logp) return pmc_fail("pmc_step_prior_stage: null workspace (rest_logp)");
+    for (int b = 0; b < B; ++b)
+        if (g->image16[b] && g->image_per_transform[b] < 1) return pmc_fail("pmc_step_prior_stage: a bf16 image needs image_per_transform");
+    if (s->n < 1) return pmc_fail("pmc_step_prior_stage: n < 1");
+    if (s->n > 0x7fffffffLL) return pmc_fail("pmc_step_prior_stage: too many rows for one count");
+    if (!s->p_x || !s->p_fin || !s->p_logp) return pmc_fail("pmc_step_prior_stage: needs p_x, p_fin and p_logp");
+    int DF = 0, Dr = 0;
+    if (int e = pmc_joint_blocks_check(&g->blocks, &DF, &Dr)) return e;     // (what pmc_joint_blocks_pre refuses, in its words)
+    if (DF + Dr != s->D) return pmc_fail("pmc_step_prior_stage: the prior's width is not the step's D");
+    for (int b = 0; b < B; ++b)
+        if (g->maf[b]->D != g->blocks.scaler[b]->D) return pmc_fail("pmc_step_prior_stage: the flow's width is not the scaler's");
+    return 0;
+}
+
+// the B + 2 launches (the struct has passed blocks_stage_check)
+static int blocks_stage_enqueue(const pmc_step_t* s, const pmc_prior_blocks_stage_t* g, void* stream) {
+    const int64_t n = s->n;
+    const int B = g->blocks.n_blocks;
+    int rc = pmc_joint_blocks_pre(&g->blocks, s->p_x, s->D, 1, n, g->u32, g->ldj, g->rest_logp, g->inside, stream);
+    if (rc) return rc;
+    int64_t off = 0;
+    for (int b = 0; b < B; ++b) {                   // block b's piece of u32 and its row of lp32; one z for all: nobody reads it
+        float* u = g->u32 + n * off;
+        float* lp = g->lp32 + (int64_t)b * n;
+        rc = g->image16[b] ? pmc_maf_forward_bf16(g->maf[b], g->image16[b], g->image_per_transform[b], u, g->z, nullptr, lp, n, nullptr, stream)
+                           : pmc_maf_forward(g->maf[b], u, g->z, nullptr, lp, n, stream);
+        if (rc) return rc;
+        off += g->blocks.scaler[b]->D;
+    }
+    hipLaunchKernelGGL(prior_blocks_stage_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B,
+                       g->lp32, g->ldj, g->blocks.rest ? g->rest_logp : (const double*)nullptr, g->inside, s->p_fin, s->p_logp,
+                       g->count, (long long*)g->h_count, n);
+    return pmc_check_launch("prior_blocks_stage_close_kernel");
+}
+
 // what pmc_step_prior_stage refuses, before any launch (host logic: follows s->prior_stage and its scaler / rest only)
 static int prior_stage_check(const pmc_step_t* s) {
     if (!s) return pmc_fail("pmc_step_prior_stage: null argument");
     const pmc_prior_stage_t* g = step_stage(s);
+    if (const pmc_prior_blocks_stage_t* gb = step_blocks_stage(s)) {
+        if (g) return pmc_fail("pmc_step_prior_stage: prior_stage and blocks_stage are both set: one of the two");
+        return blocks_stage_check(s, gb);
+    }
     if (!g) return pmc_fail("pmc_step_prior_stage: the step has no prior_stage");
     if (s->prior) return pmc_fail("pmc_step_prior_stage: the step has a device prior table as well (prior): one of the two");
     if (s->prior_rows) return pmc_fail("pmc_step_prior_stage: the step has a prior that is a GPU callable as well (prior_rows): one of the two");
@@ -188,6 +290,7 @@ static int prior_stage_check(const pmc_step_t* s) {
 
 // the three launches (the struct has passed prior_stage_check)
 static int prior_stage_enqueue(const pmc_step_t* s, void* stream) {
+    if (const pmc_prior_blocks_stage_t* gb = step_blocks_stage(s)) return blocks_stage_enqueue(s, gb, stream);
     const pmc_prior_stage_t* g = step_stage(s);
     const int64_t n = s->n;
     const bool joint = g->flow_cols != nullptr;
@@ -218,7 +321,7 @@ extern "C" int pmc_step_prior_stage(const pmc_step_t* s, void* stream) {
 static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double sigma, double cn_a, void* stream,
                     bool fill_next) {
     if (!s || !rng) return pmc_fail("pmc_step_pre: null argument");
-    if (step_stage(s)) { if (int e = prior_stage_check(s)) return e; }      // (before the pre-step's own launches)
+    if (step_has_stage(s)) { if (int e = prior_stage_check(s)) return e; }      // (before the pre-step's own launches)
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = s->n;
     const int32_t D = s->D;
@@ -244,7 +347,7 @@ static int step_pre(const pmc_step_t* s, const pmc_rng_t* rng, double nu, double
         // the flow / joint prior of a host likelihood: behind everything the host waits for, while it evaluates the
         // likelihood; in front of the next step's variates, which nothing of this step needs (fill_next = false: the
         // caller places the stage as it places the fill)
-        if (step_stage(s) && fill_next) { if (int e = prior_stage_enqueue(s, stream)) return e; }
+        if (step_has_stage(s) && fill_next) { if (int e = prior_stage_enqueue(s, stream)) return e; }
         if (prefill && fill_next) return pmc_step_fill_next(s, rng_in, nu, stream);
         return 0;
     };
@@ -473,7 +576,7 @@ static int step_post(const pmc_step_t* s, const pmc_rng_t* rng, double beta, dou
         if (int e = blob_buffers_check("pmc_step_post", s->blob_prop, s->blob_cur, s->blob_row_bytes)) return e;
     }
     // logp' is in p_logp: the device prior's table, or the flow / joint prior's stage behind the pre-step
-    const bool dev_logp = s->prior || step_stage(s);
+    const bool dev_logp = s->prior || step_has_stage(s);
     if (mode == PMC_HANDOVER_COPIES) {
         if (hipMemcpyAsync(s->p_logl, s->h_logl, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
             return pmc_fail("pmc_step_post: H2D");
@@ -666,20 +769,20 @@ static int pipeline_enqueue_pre(pmc_pipeline* p, int64_t step, double nu) {
     const bool stage_per_lane = false;
 #endif
     for (int k = 0; k < p->n_lanes; ++k) {
-        pmc_step_ext_t sx = step_copy(p->lanes[k]);
+        pmc_step_ext2_t sx = step_copy(p->lanes[k]);
         pmc_step_t& s = sx.step;
         s.adapt_mode = 1;                                   // (pre: any non-zero mode = read sigma, cn_a, mu from adapt_state)
         p->rng[k].step = (uint64_t)step;
         const int rc = step_pre(&s, &p->rng[k], nu, 0.0, 0.0, p->stream, false);
         if (rc) return rc;
-        if (sx.prior_stage && stage_per_lane) { if (int e = prior_stage_enqueue(&s, p->stream)) return e; }
+        if (step_has_stage(&s) && stage_per_lane) { if (int e = prior_stage_enqueue(&s, p->stream)) return e; }
         if (p->prefetcher)                                  // helper threads read x' once as soon as its completion word shows up
             (void)pmc_prefetcher_submit(p->prefetcher, s.h_done, step + 1, s.h_x, (int64_t)s.n * s.D * 8, p->timeout > 0 ? p->timeout : 1.0);
     }
     // the lanes' flow / joint prior (pmc_step_ext_t.prior_stage) behind the LAST lane's pre-step: no lane's x' waits behind
     // another lane's log_prob (profiles/step_prior.txt has both orders)
     for (int k = 0; k < p->n_lanes; ++k) {
-        if (!step_stage(p->lanes[k]) || stage_per_lane) continue;
+        if (!step_has_stage(p->lanes[k]) || stage_per_lane) continue;
         const int rc = prior_stage_enqueue(p->lanes[k], p->stream);
         if (rc) return rc;
     }
@@ -706,7 +809,7 @@ extern "C" int pmc_pipeline_next(void* pp, int32_t lane_done, double beta, doubl
     const int last = p->n_lanes - 1;
     double t0 = now_s();
     if (lane_done >= 0) {
-        pmc_step_ext_t sx = step_copy(p->lanes[lane_done]);
+        pmc_step_ext2_t sx = step_copy(p->lanes[lane_done]);
         pmc_step_t& s = sx.step;
         s.adapt_n_other = 0;
         s.adapt_mode = 0;

@@ -511,9 +511,9 @@ class StepEngine:
             logdetj=self.p_logdetj.data_ptr(), logl=self.p_logl.data_ptr(), logp=self.p_logp.data_ptr(),
             logdetj_flow=self.p_ldjf.data_ptr() if self.pre else None,
             quad=self.quad.data_ptr() if self.tpcn else None, quad_prop=self.p_quad.data_ptr() if self.tpcn else None)
-        # (the extended struct: pmc_step_t and, behind it, the prior stage of set_step_prior -- NULL until then)
-        self._step = _lib.pmc_step_ext_t(
-            ext=_lib.PMC_STEP_EXT,
+        # (the extended struct: pmc_step_t and, behind it, the two prior stages of set_step_prior -- NULL until then)
+        self._step = _lib.pmc_step_ext2_t(
+            ext=_lib.PMC_STEP_EXT2,
             kind=PMC_KIND_TPCN if self.tpcn else PMC_KIND_RWM, preconditioned=int(self.pre), n=n, D=D,
             inverse_algo=flow.inverse_algo if self.pre else 0,
             maf=C.cast(C.pointer(flow._desc), C.c_void_p) if self.pre else None,
@@ -671,7 +671,8 @@ class StepEngine:
         return True
 
     def set_step_prior(self, prior):
-        """Evaluate a ``FlowPrior`` / ``JointPrior`` inside the step of a HOST likelihood (``pmc_step_ext_t.prior_stage``): behind
+        """Evaluate a ``FlowPrior`` / ``JointPrior`` inside the step of a HOST likelihood (``pmc_step_ext_t.prior_stage``; the
+        blocks form of a ``JointPrior``: ``pmc_step_ext2_t.blocks_stage``, B + 2 launches): behind
         the hand-over of x' the pre-step enqueues the prior's three launches on its own stream -- they read ``p_x`` and write
         ``p_logp`` while the host evaluates the likelihood -- and the accept takes logp' from the device.  The host gets x'
         and the finite mask as for a host prior and masks on the finite flags only (:meth:`evaluate` with ``log_prior=None``);
@@ -685,7 +686,11 @@ class StepEngine:
         self._stage_read = 0
         self._np_stage = stage.counts.numpy()
         self._pins.append(stage.counts)
-        self._step.prior_stage = C.cast(C.pointer(stage), C.c_void_p)
+        # (the field that matches the descriptor: pmc_prior_blocks_stage_t is the blocks form of a JointPrior)
+        if isinstance(stage, _lib.pmc_prior_blocks_stage_t):
+            self._step.blocks_stage = C.cast(C.pointer(stage), C.c_void_p)
+        else:
+            self._step.prior_stage = C.cast(C.pointer(stage), C.c_void_p)
 
     def stage_enqueue(self):
         """The stage behind a pre-step enqueued with ``defer_fill`` (``pmc_step_pre_deferred`` leaves it to the caller, who

@@ -15,7 +15,8 @@ MCMC step calls on the device like a device likelihood (``Sampler(device_likelih
 prior's box, evaluated by two launches around the flow's own forward kernel (``csrc/flow_prior.hip``).
 
 ``JointPrior`` puts such a flow prior on some columns of ``x`` and a table of scipy factors on the others, in the same number
-of launches (``csrc/joint_prior.hip``).
+of launches (``csrc/joint_prior.hip``); its blocks form takes several flow priors on disjoint blocks of columns, in B + 2
+launches and still one pass over ``x``.
 
 Next to a HOST likelihood both can be evaluated by the MCMC step itself (``step_stage``, kernel option ``step_prior``): the same
 three launches on the step's stream, on the device's copy of x', while the host evaluates the likelihood."""
@@ -608,10 +609,28 @@ class JointPrior:
     ``bounds``, ``dim``   the two parts', merged by position.
 
     The prior owns copies of both parts (the flow prior through its pickled state, the table as arrays): later changes to the
-    sources do not move it.  There is no ``device_descriptor``: the step calls the function.  Out of scope: more than one flow
-    block, non-diagonal scalers, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
+    sources do not move it.  There is no ``device_descriptor``: the step calls the function.
+
+    The blocks form: ``JointPrior([fp_0, fp_1, ...], [columns_0, columns_1, ...], rest=None)`` -- a list or tuple of
+    1 <= B <= 8 ``FlowPrior`` s (on one device) and as many column lists; ``rest`` a ``Prior`` as above, or None when the blocks
+    cover every column:
+
+        ``log p(x) = sum_b flow_priors[b].logpdf(x[:, columns_b]) + sum_m rest.dists[m].logpdf(x[:, rest_cols[m]])``.
+
+    ``flow_priors`` is the tuple of owned copies, ``blocks`` its length (0 in the single form, whose ``flow_prior`` the blocks
+    form does not have).  ``logpdf_device`` is B + 2 launches and one pass over ``x``: ``pmc_joint_blocks_pre`` (every block's
+    u as float32 -- each block with its own scaler, transform included --, the scalers' log-determinants, the table's sum, one
+    support flag per row), every block's forward call with ``log_prob`` in block order (a ``precision="bf16"`` block keeps
+    its matrix-core kernel), ``pmc_joint_blocks_post``; the value is the left-to-right float64 sum of the blocks'
+    ``FlowPrior.logpdf_device`` on their gathered columns and ``pmc_prior_logpdf`` of the gathered rest, bit for bit, with
+    the single form's contract otherwise.  ``rvs`` draws block 0, block 1, ... with each block's ``rvs`` (torch's global
+    generator), then the rest with numpy's global generator.  ``step_stage`` gives the step a ``pmc_prior_blocks_stage_t``.
+
+    Out of scope: more than 8 blocks, non-diagonal scalers, the stage on sharded walkers, and -- as for every
+    ``DevicePrior`` -- lanes and graph capture."""
 
     MAX_DIM = FlowPrior.MAX_DIM
+    MAX_BLOCKS = 8           # PMC_JOINT_BLOCKS_MAX
     _WORKSPACES = FlowPrior._WORKSPACES
 
     @staticmethod
@@ -640,7 +659,52 @@ class JointPrior:
         rest_cols = np.setdiff1d(np.arange(D), cols)
         return cols.astype(np.int32), rest_cols.astype(np.int32)
 
-    def __init__(self, flow_prior, columns, rest):
+    @staticmethod
+    def layout_blocks(columns, flow_dims, rest_dim):
+        """``(block_cols, rest_cols)``: ``block_cols[b]`` is ``columns[b]`` as an int32 array (``flow_dims[b]`` integers in
+        ``[0, sum(flow_dims) + rest_dim)``, distinct within the block and across blocks), ``rest_cols`` the ``rest_dim``
+        other positions in increasing order.  ``ValueError`` for a number of column lists that is not the number of blocks,
+        a wrong count in a block, entries out of range or not integers, duplicates within a block and an overlap between two
+        blocks (both are named).  Pure numpy."""
+        flow_dims = [int(d) for d in flow_dims]
+        rest_dim = int(rest_dim)
+        if rest_dim < 0 or any(d < 0 for d in flow_dims):
+            raise ValueError(f"JointPrior.layout_blocks: negative dimension (flow_dims = {flow_dims}, rest_dim = {rest_dim})")
+        try:
+            lists = list(columns)
+        except TypeError:
+            raise ValueError(f"JointPrior.layout_blocks: columns must be a sequence of column lists, got {columns!r}") from None
+        if len(lists) != len(flow_dims):
+            raise ValueError(f"JointPrior.layout_blocks: {len(lists)} column lists for {len(flow_dims)} blocks")
+        D = sum(flow_dims) + rest_dim
+        maps, owner = [], {}
+        for b, (cols_in, Df) in enumerate(zip(lists, flow_dims)):
+            try:
+                cols = np.asarray(cols_in)
+            except (TypeError, ValueError):
+                cols = np.asarray(cols_in, dtype=object)
+            if cols.size == 0:
+                cols = cols.astype(np.int64)
+            if cols.ndim != 1 or cols.dtype == np.bool_ or not np.issubdtype(cols.dtype, np.integer):
+                raise ValueError(f"JointPrior.layout_blocks: block {b}: columns must be a sequence of integers, got {cols_in!r}")
+            if len(cols) != Df:
+                raise ValueError(f"JointPrior.layout_blocks: block {b}: {len(cols)} columns for a flow prior of {Df} dimensions")
+            if ((cols < 0) | (cols >= D)).any():
+                raise ValueError(f"JointPrior.layout_blocks: block {b}: columns must lie in [0, {D}), got {cols.tolist()}")
+            if len(np.unique(cols)) != len(cols):
+                raise ValueError(f"JointPrior.layout_blocks: block {b}: columns are not distinct: {cols.tolist()}")
+            for c in cols.tolist():
+                if c in owner:
+                    raise ValueError(f"JointPrior.layout_blocks: blocks {owner[c]} and {b} overlap (column {c})")
+                owner[c] = b
+            maps.append(cols.astype(np.int32))
+        rest_cols = np.setdiff1d(np.arange(D), np.fromiter(owner, dtype=np.int64, count=len(owner)))
+        return maps, rest_cols.astype(np.int32)
+
+    def __init__(self, flow_prior, columns, rest=None):
+        if isinstance(flow_prior, (list, tuple)):
+            self._init_blocks(flow_prior, columns, rest)
+            return
         if not isinstance(flow_prior, FlowPrior):
             raise ValueError(f"JointPrior: flow_prior must be a pocomc_amd.FlowPrior, got {type(flow_prior).__name__}")
         if not isinstance(rest, Prior):
@@ -676,10 +740,186 @@ class JointPrior:
         self._ws = {}
 
     def __getstate__(self):
+        if self.blocks:
+            return {"flow_priors": [fp.__getstate__() for fp in self.flow_priors],
+                    "columns": [c.tolist() for c in self._block_cols], "rest": self.rest}
         return {"flow_prior": self.flow_prior.__getstate__(), "columns": self._flow_cols.tolist(), "rest": self.rest}
 
     def __setstate__(self, st):
-        self._restore(st["flow_prior"], st["columns"], st["rest"])
+        if "flow_priors" in st:
+            self._restore_blocks(st["flow_priors"], st["columns"], st["rest"])
+        else:
+            self._restore(st["flow_prior"], st["columns"], st["rest"])
+
+    # ----------------------------------------------------------------- the blocks form
+    blocks = 0                    # the number of flow blocks in the blocks form; 0: the single form (``flow_prior``)
+
+    def _init_blocks(self, flow_priors, columns, rest):
+        B = len(flow_priors)
+        for b, fp in enumerate(flow_priors):
+            if not isinstance(fp, FlowPrior):
+                raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior, got {type(fp).__name__}")
+        if not 1 <= B <= self.MAX_BLOCKS:
+            raise ValueError(f"JointPrior: {B} flow blocks (1 <= blocks <= {self.MAX_BLOCKS})")
+        import torch
+        devs = [torch.device(fp.flow.device) for fp in flow_priors]
+        for b in range(1, B):
+            if devs[b] != devs[0]:
+                raise ValueError(f"JointPrior: blocks 0 and {b} are on different devices ({devs[0]}, {devs[b]})")
+        if rest is not None:
+            if not isinstance(rest, Prior):
+                raise ValueError(f"JointPrior: rest must be a pocomc_amd.Prior or None, got {type(rest).__name__}")
+            if rest.dists is None or rest.dim < 1:
+                raise ValueError("JointPrior: rest needs at least one factor (rest=None: the blocks cover every column)")
+            if rest.device_table() is None:
+                raise ValueError("JointPrior: the device must evaluate rest: build it as Prior(dists, device=True)")
+        dims, Dr = [fp.dim for fp in flow_priors], 0 if rest is None else rest.dim
+        if sum(dims) + Dr > self.MAX_DIM:
+            raise ValueError(f"JointPrior: n_dim = {' + '.join(str(d) for d in dims + [Dr])} is too large "
+                             f"(n_dim <= {self.MAX_DIM})")
+        maps, _ = self.layout_blocks(columns, dims, Dr)
+        self._restore_blocks([fp.__getstate__() for fp in flow_priors], [m.tolist() for m in maps], rest, devs[0])
+
+    def _restore_blocks(self, states, columns, rest, device=None):
+        import copy
+        import ctypes as C
+        import torch
+        from . import _lib
+        fps = []
+        for st in states:
+            fp = FlowPrior.__new__(FlowPrior)
+            fp._restore(st["flow"], st["scaler"], device)
+            device = fp.flow.device                                # (an unpickled prior: every block where the first one went)
+            fps.append(fp)
+        self.flow_priors = tuple(fps)
+        self.blocks = len(fps)
+        self.rest = copy.deepcopy(rest)
+        Dr = 0 if self.rest is None else self.rest.dim
+        self._block_cols, self._rest_cols = self.layout_blocks(columns, [fp.dim for fp in fps], Dr)
+        dev = fps[0].flow.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        # (the descriptors point into these tensors: they live as long as the descriptors do)
+        self._dev = dict(cols=[up(c) for c in self._block_cols], rest_cols=up(self._rest_cols) if Dr else None)
+        self._rdesc = None
+        if Dr:
+            tab = self.rest.device_table()
+            n_ext = int((tab["family"] > 2).sum())
+            self._dev.update(family=up(tab["family"]), loc=up(tab["loc"]), scale=up(tab["scale"]),
+                             par=up(tab["par"]) if n_ext else None)
+            self._rdesc = _lib.pmc_prior_t(family=self._dev["family"].data_ptr(), loc=self._dev["loc"].data_ptr(),
+                                           scale=self._dev["scale"].data_ptr(), D=Dr, reserved=0,
+                                           par=self._dev["par"].data_ptr() if n_ext else None, n_extended=n_ext, reserved2=0)
+        j = _lib.pmc_joint_blocks_t(n_blocks=self.blocks, reserved=0,
+                                    rest=C.cast(C.pointer(self._rdesc), C.c_void_p) if Dr else None,
+                                    rest_cols=self._dev["rest_cols"].data_ptr() if Dr else None)
+        for b, fp in enumerate(fps):
+            j.scaler[b] = C.cast(C.pointer(fp._sdesc), C.c_void_p)
+            j.cols[b] = self._dev["cols"][b].data_ptr()
+        self._jdesc = j
+        self._offsets = np.concatenate([[0], np.cumsum([fp.dim for fp in fps])]).astype(np.int64)
+        self._ws = {}
+
+    def _workspace_blocks(self, n):
+        import torch
+        ws = self._ws.get(n)
+        if ws is None:
+            dev, off = self.flow_priors[0].flow.device, self._offsets
+            u32 = torch.empty(n * int(off[-1]), dtype=torch.float32, device=dev)
+            z = torch.empty(n * max(fp.dim for fp in self.flow_priors), dtype=torch.float32, device=dev)
+            ws = (u32,
+                  # block b's [n][Df_b] piece of u32, and the one z every flow writes in turn (not used)
+                  [u32[n * int(off[b]):n * int(off[b + 1])].view(n, fp.dim) for b, fp in enumerate(self.flow_priors)],
+                  [z[:n * fp.dim].view(n, fp.dim) for fp in self.flow_priors],
+                  torch.empty(self.blocks, n, dtype=torch.float32, device=dev),      # the flows' log_prob
+                  torch.empty(self.blocks, n, dtype=torch.float64, device=dev),      # the scalers' log-determinants
+                  torch.empty(n, dtype=torch.float64, device=dev) if self._rdesc is not None else None,
+                  torch.empty(n, dtype=torch.int32, device=dev))                     # inside the support (one flag per row)
+            while len(self._ws) >= self._WORKSPACES:
+                self._ws.pop(next(iter(self._ws)))
+            self._ws[n] = ws
+        return ws
+
+    def _logpdf_device_blocks(self, x):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        D, flow0 = self.dim, self.flow_priors[0].flow
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"JointPrior.logpdf_device: expected an (n, {D}) float64 tensor, got {what}")
+        _on_device(x, flow0.device, "JointPrior.logpdf_device")
+        n = x.shape[0]
+        out = torch.empty(n, dtype=torch.float64, device=flow0.device)
+        if n == 0:
+            return out
+        # the two layouts the kernel reads with coalesced loads; everything else is copied once
+        if x.is_contiguous():
+            strides = (D, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (D, 1)
+        u32, u32_b, z_b, lp32, ldj, rest_logp, inside = self._workspace_blocks(n)
+        lib = flow0.lib
+        with torch.cuda.device(flow0.device):
+            _lib.check(lib.pmc_joint_blocks_pre(C.byref(self._jdesc), C.c_void_p(x.data_ptr()), strides[0], strides[1], n,
+                                                _lib.ptr(u32), _lib.ptr(ldj), _lib.ptr(rest_logp), _lib.ptr(inside),
+                                                _lib.stream_handle()), "pmc_joint_blocks_pre")
+            for b, fp in enumerate(self.flow_priors):
+                fp.flow._forward_call(u32_b[b], z_b[b], None, lp32[b], n)
+            _lib.check(lib.pmc_joint_blocks_post(self.blocks, _lib.ptr(lp32), _lib.ptr(ldj), _lib.ptr(rest_logp),
+                                                 _lib.ptr(inside), _lib.ptr(out), n, _lib.stream_handle()),
+                       "pmc_joint_blocks_post")
+        return out
+
+    def _step_stage_blocks(self, n, device):
+        """``pmc_prior_blocks_stage_t`` for the ``n`` rows of one step engine: this prior's ``pmc_joint_blocks_t``, every
+        block's flow (a bf16 block: its image) and one workspace set of its own, laid out as ``logpdf_device``'s.  The
+        descriptor keeps what it points into alive, like ``pmc_prior_stage_t``'s."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device, _pinned_take
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"JointPrior.step_stage: n must be at least 1, got {n}")
+        dev = torch.device(self.flow_priors[0].flow.device)
+        if device is not None:
+            _on_device(torch.empty(0, device=dev), device, "JointPrior.step_stage")
+        with torch.cuda.device(dev):
+            ws = dict(u32=torch.empty(n * int(self._offsets[-1]), dtype=torch.float32, device=dev),
+                      z=torch.empty(n * max(fp.dim for fp in self.flow_priors), dtype=torch.float32, device=dev),
+                      lp32=torch.empty(self.blocks, n, dtype=torch.float32, device=dev),
+                      ldj=torch.empty(self.blocks, n, dtype=torch.float64, device=dev),
+                      rest_logp=torch.empty(n, dtype=torch.float64, device=dev) if self._rdesc is not None else None,
+                      inside=torch.empty(n, dtype=torch.int32, device=dev),
+                      count=torch.zeros(2, dtype=torch.int64, device=dev))
+            images = [fp.flow._bf16_image()[1:] if fp.flow.precision == "bf16" else None for fp in self.flow_priors]
+        h_count = _pinned_take((2,), torch.int64)
+        h_count.zero_()
+        desc = _lib.pmc_prior_blocks_stage_t(
+            u32=ws["u32"].data_ptr(), z=ws["z"].data_ptr(), lp32=ws["lp32"].data_ptr(), ldj=ws["ldj"].data_ptr(),
+            rest_logp=ws["rest_logp"].data_ptr() if ws["rest_logp"] is not None else None, inside=ws["inside"].data_ptr(),
+            count=ws["count"].data_ptr(), h_count=h_count.data_ptr())
+        C.memmove(C.byref(desc.blocks), C.byref(self._jdesc), C.sizeof(_lib.pmc_joint_blocks_t))
+        for b, fp in enumerate(self.flow_priors):
+            desc.maf[b] = C.cast(C.pointer(fp.flow._desc), C.c_void_p)
+            if images[b] is not None:
+                desc.image16[b] = images[b][0].data_ptr()
+                desc.image_per_transform[b] = int(images[b][1])
+        desc._keep = (self, ws, images)
+        desc.counts = h_count             # (the pinned words: the engine reads them, and recycles the tensor with its own)
+        return desc
+
+    def _rvs_blocks(self, size):
+        x = np.empty((size, self.dim), dtype=np.float64)
+        for cols, fp in zip(self._block_cols, self.flow_priors):          # block 0, block 1, ..., then the rest
+            x[:, cols] = fp.rvs(size)
+        if self.rest is not None:
+            glob = np.random.mtrand._rand                                 # (numpy's global generator, named: see rvs)
+            x[:, self._rest_cols] = np.transpose([d.rvs(size=size, random_state=glob) for d in self.rest.dists])
+        return x
 
     # ----------------------------------------------------------------- density
     def _workspace(self, n):
@@ -699,6 +939,8 @@ class JointPrior:
         return ws
 
     def logpdf_device(self, x):
+        if self.blocks:
+            return self._logpdf_device_blocks(x)
         import ctypes as C
         import torch
         from . import _lib
@@ -737,16 +979,21 @@ class JointPrior:
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"JointPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
-        return self.logpdf_device(torch.from_numpy(x).to(self.flow_prior.flow.device)).cpu().numpy()
+        dev = self.flow_priors[0].flow.device if self.blocks else self.flow_prior.flow.device
+        return self.logpdf_device(torch.from_numpy(x).to(dev)).cpu().numpy()
 
     def step_stage(self, n, device=None):
         """``FlowPrior.step_stage`` for the joint prior: the descriptor carries the column maps and the table as well."""
+        if self.blocks:
+            return self._step_stage_blocks(n, device)
         return _step_stage(self, self.flow_prior, n, device,
                            joint=(self._dev["flow_cols"], self._rdesc, self._dev["rest_cols"]))
 
     # ----------------------------------------------------------------- draws
     def rvs(self, size=1):
         size = int(size)
+        if self.blocks:
+            return self._rvs_blocks(size)
         x = np.empty((size, self.dim), dtype=np.float64)
         x[:, self._flow_cols] = self.flow_prior.rvs(size)
         # rest.rvs with numpy's global generator named: this prior's copy of the factors (a deep copy, or an unpickled one)
@@ -758,10 +1005,18 @@ class JointPrior:
     @property
     def bounds(self):
         b = np.empty((self.dim, 2), dtype=np.float64)
+        if self.blocks:
+            for cols, fp in zip(self._block_cols, self.flow_priors):
+                b[cols] = fp.bounds
+            if self.rest is not None:
+                b[self._rest_cols] = self.rest.bounds
+            return b
         b[self._flow_cols] = self.flow_prior.bounds
         b[self._rest_cols] = self.rest.bounds
         return b
 
     @property
     def dim(self):
+        if self.blocks:
+            return int(self._offsets[-1]) + (0 if self.rest is None else self.rest.dim)
         return self.flow_prior.dim + self.rest.dim
