@@ -1127,11 +1127,16 @@ int pmc_joint_prior_post(const float* lp32, const double* ldj, const double* res
  * x that is block b's feature k.  rest / rest_cols: the table and its columns (int32 [Dr], device memory) as for
  * pmc_joint_prior_pre, or both NULL: no table, Dr = 0.  All maps together are a permutation of 0 .. D - 1 (the caller's to
  * check: JointPrior.layout_blocks); an entry outside [0, D) is not followed, every row of the call's blocks then gets
- * inside = 0.  Entries b >= n_blocks are not read. */
+ * inside = 0.  Entries b >= n_blocks are not read.
+ * D: the columns of x where the maps do not cover them all (the other columns belong to correlated normal blocks, see
+ * pmc_gauss_blocks_t): sum_b Df_b + Dr <= D <= 157; the maps are then distinct entries of [0, D), the tile holds D columns
+ * and the bits of every output are those of the call on the gathered columns.  D = 0 is what every caller passed so far:
+ * the maps are a permutation.  The stage of a step (pmc_prior_blocks_stage_t) takes D = 0, or the step's D with maps that
+ * cover it. */
 #define PMC_JOINT_BLOCKS_MAX 8
 typedef struct pmc_joint_blocks {
     int32_t n_blocks;             /* 1 .. PMC_JOINT_BLOCKS_MAX */
-    int32_t reserved;
+    int32_t D;                    /* columns of x; 0 (the field was reserved): sum_b Df_b + Dr */
     const pmc_scaler_t* scaler[PMC_JOINT_BLOCKS_MAX];
     const int32_t* cols[PMC_JOINT_BLOCKS_MAX];
     const pmc_prior_t* rest;      /* or NULL */
@@ -1149,7 +1154,8 @@ typedef struct pmc_joint_blocks {
  * is zeros in every block's u32 and -inf in rest_logp.  A row's bits depend on its values alone.
  * Refused before anything is launched or written, each with a text of its own: a NULL descriptor or NULL fields; n_blocks
  * outside 1 .. 8; a block with Df_b < 2; sum Df_b + Dr > 157 ("n_dim too large"; LDS as for pmc_joint_prior_pre with Df the
- * blocks' sum); rest->n_extended > 0 without rest->par; a scaler with scale and no mu / sigma; a NULL array, a negative
+ * blocks' sum, 64 * (D | 1) * 8 for the tile with D set); D set and smaller than sum Df_b + Dr, or larger than 157;
+ * rest->n_extended > 0 without rest->par; a scaler with scale and no mu / sigma; a NULL array, a negative
  * count or stride; more than 2^31 - 1 blocks of 64 rows.  n == 0 returns 0 and reads no array. */
 int pmc_joint_blocks_pre(const pmc_joint_blocks_t* j, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
                          float* u32, double* ldj, double* rest_logp, int32_t* inside, void* stream);
@@ -1198,6 +1204,55 @@ typedef struct pmc_step_ext2 {
     const pmc_prior_stage_t* prior_stage;
     const pmc_prior_blocks_stage_t* blocks_stage;
 } pmc_step_ext2_t;
+
+/* ----------------------------------------------------------------- correlated normal blocks */
+
+/* B correlated normal blocks on disjoint blocks of columns of x (pocomc_amd.GaussianPrior; the Gaussian blocks of
+ * pocomc_amd.JointPrior), on top of a value that is already there (base), of a table of scipy factors (rest) or of nothing:
+ *   log p(x) = start + sum_b g_b,   g_b = -0.5 |Linv_b (x[cols_b] - mean_b)|^2 - logc_b,
+ * Linv_b the inverse of the lower Cholesky factor of block b's covariance and logc_b = sum log diag(L_b) + dim_b / 2
+ * log(2 pi), both from the host in float64.  ONE launch, float64, one pass over x.  Appended within ABI 9: a new entry and
+ * a new struct only.
+ *
+ * dim[b] >= 1 columns per block; cols[b] int32 [dim[b]], mean[b] f64 [dim[b]], linv[b] f64 [dim[b] (dim[b] + 1) / 2]: row i
+ * of Linv_b holds its i + 1 entries at i (i + 1) / 2; all device memory.  D: the columns of x (the blocks and the rest need
+ * not cover them all).  rest / rest_cols: a table and its columns (int32 [rest->D], device memory) as for
+ * pmc_joint_blocks_pre, or both NULL.  The maps are the caller's to check (JointPrior.layout_blocks): distinct entries of
+ * [0, D); an entry outside [0, D) is not followed, every row of its launch block of 64 rows then gets -inf.  Entries
+ * b >= n_blocks are not read.
+ *
+ * The arithmetic, every product and every sum rounded to float64 (no FMA), for a row and a block:
+ *   d_j = x[cols[j]] - mean[j]
+ *   y_i = (((0.0 + Linv[i,0] d_0) + Linv[i,1] d_1) + ...) + Linv[i,i] d_i
+ *   q   = ((0.0 + y_0 y_0) + y_1 y_1) + ...                   in i order
+ *   g   = -0.5 q - logc
+ * logp[r] = v = start + g_0 + g_1 + ..., left to right; start = base[r] with base (f64 [n]; may be logp itself: in place),
+ * else lp = 0.0; lp += term_m, m = 0 .. rest->D - 1 with rest (the bits of pmc_prior_logpdf on the gathered rest columns),
+ * else nothing: v = g_0 (+ g_1 ...).  -inf where an x_j of a block or rest column is not finite, a rest term is NaN or v is
+ * not finite (a NaN of the arithmetic, a pole of a table family): never NaN, never +inf.
+ * x: f64, element (r, j) at x[r * row_stride + j * col_stride], with the two coalesced layouts (D, 1) and (1, n) of
+ * pmc_flow_prior_pre; other strides are read correctly, slowly.  A row's bits depend on its values alone -- not on the
+ * layout, on n or on the row's place in the call.
+ * Refused before anything is launched or written, each with a text of its own: a NULL descriptor or NULL block arrays;
+ * n_blocks outside 1 .. 8; a block with dim < 1; D > 157 ("n_dim too large"; a launch block keeps 64 rows of x in LDS:
+ * 64 * (D | 1) * 8 + 256 bytes); more block and rest columns than D; rest without rest_cols or the reverse;
+ * rest->n_extended > 0 without rest->par; base and rest together; a NULL x or logp, a negative count or stride; more than
+ * 2^31 - 1 blocks of 64 rows.  n == 0 returns 0 and reads no array. */
+#define PMC_GAUSS_BLOCKS_MAX 8
+typedef struct pmc_gauss_blocks {
+    int32_t n_blocks;             /* 1 .. PMC_GAUSS_BLOCKS_MAX */
+    int32_t D;                    /* columns of x */
+    int32_t dim[PMC_GAUSS_BLOCKS_MAX];
+    const int32_t* cols[PMC_GAUSS_BLOCKS_MAX];
+    const double* mean[PMC_GAUSS_BLOCKS_MAX];
+    const double* linv[PMC_GAUSS_BLOCKS_MAX];
+    double logc[PMC_GAUSS_BLOCKS_MAX];
+    const pmc_prior_t* rest;      /* or NULL */
+    const int32_t* rest_cols;     /* or NULL (with rest) */
+} pmc_gauss_blocks_t;
+
+int pmc_gauss_blocks_logpdf(const pmc_gauss_blocks_t* g, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
+                            const double* base, double* logp, void* stream);
 
 #ifdef __cplusplus
 }

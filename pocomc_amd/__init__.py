@@ -6,7 +6,7 @@ gfx950 kernels behind the C ABI of ``include/pocomc_amd.h``.
 """
 from .maf_spec import MAFSpec  # noqa: F401
 
-__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "JointPrior", "mcmc", "tools"]
+__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "GaussianPrior", "JointPrior", "mcmc", "tools"]
 
 
 def __getattr__(name):
@@ -32,6 +32,9 @@ def __getattr__(name):
     if name == "FlowPrior":
         from .prior import FlowPrior
         return FlowPrior
+    if name == "GaussianPrior":
+        from .prior import GaussianPrior
+        return GaussianPrior
     if name == "JointPrior":
         from .prior import JointPrior
         return JointPrior

@@ -144,7 +144,7 @@ PMC_JOINT_BLOCKS_MAX = 8
 
 
 class pmc_joint_blocks_t(C.Structure):
-    _fields_ = [("n_blocks", C.c_int32), ("reserved", C.c_int32), ("scaler", c_p * PMC_JOINT_BLOCKS_MAX),
+    _fields_ = [("n_blocks", C.c_int32), ("D", C.c_int32), ("scaler", c_p * PMC_JOINT_BLOCKS_MAX),
                 ("cols", c_p * PMC_JOINT_BLOCKS_MAX), ("rest", c_p), ("rest_cols", c_p)]
 
 
@@ -153,6 +153,16 @@ class pmc_prior_blocks_stage_t(C.Structure):
                 ("image16", c_p * PMC_JOINT_BLOCKS_MAX), ("image_per_transform", C.c_int64 * PMC_JOINT_BLOCKS_MAX),
                 ("u32", c_p), ("z", c_p), ("lp32", c_p), ("ldj", c_p), ("rest_logp", c_p), ("inside", c_p),
                 ("count", c_p), ("h_count", c_p)]
+
+
+PMC_GAUSS_BLOCKS_MAX = 8
+
+
+class pmc_gauss_blocks_t(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("D", C.c_int32), ("dim", C.c_int32 * PMC_GAUSS_BLOCKS_MAX),
+                ("cols", c_p * PMC_GAUSS_BLOCKS_MAX), ("mean", c_p * PMC_GAUSS_BLOCKS_MAX),
+                ("linv", c_p * PMC_GAUSS_BLOCKS_MAX), ("logc", C.c_double * PMC_GAUSS_BLOCKS_MAX),
+                ("rest", c_p), ("rest_cols", c_p)]
 
 
 # name -> (restype, argtypes); every symbol include/pocomc_amd.h declares
@@ -273,6 +283,7 @@ SIGNATURES = {
     "pmc_joint_prior_post": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, c_p]),
     "pmc_joint_blocks_pre": (C.c_int, [P(pmc_joint_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p]),
     "pmc_joint_blocks_post": (C.c_int, [i32, c_p, c_p, c_p, c_p, c_p, i64, c_p]),
+    "pmc_gauss_blocks_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
 }
 
 _lib = None

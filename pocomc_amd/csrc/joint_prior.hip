@@ -177,11 +177,16 @@ struct JointBlocksArgs {
     const int32_t* cols[PMC_JOINT_BLOCKS_MAX];
     int32_t off[PMC_JOINT_BLOCKS_MAX + 1];
     int32_t n_blocks;
+    int32_t D;                                     // the columns of x (>= the slots: the blocks' features and the factors)
     pmc_prior_t rest;
     const int32_t* rest_cols;
 };
 
-static inline size_t joint_blocks_lds_bytes(int DF, int Dr) { return joint_prior_lds_bytes(DF, Dr); }
+// joint_prior_lds_bytes with the tile as wide as x: the same bytes where the slots cover every column
+static inline size_t joint_blocks_lds_bytes(int DF, int Dr, int D) {
+    return (size_t)FP_ROWS * (D | 1) * sizeof(double) + (size_t)FP_ROWS * DF * sizeof(float) + FP_ROWS * sizeof(int) +
+           (size_t)(DF + Dr) * sizeof(int);
+}
 
 // joint_prior_pre_kernel's shape and stride contract with the flow slots of several blocks: slot c in [off[b], off[b + 1])
 // is feature c - off[b] of block b in tile column cols[b][c - off[b]], the slots behind off[B] are the rest factors.  A
@@ -189,23 +194,24 @@ static inline size_t joint_blocks_lds_bytes(int DF, int Dr) { return joint_prior
 // read with a constant index; a lane keeps the pointers and flags of the block its slot lies in), then does what
 // joint_prior_pre_kernel's thread does with that block's constants -- its own transform, its own affine part.  U holds
 // block b's [FP_ROWS][Df_b] piece at FP_ROWS * off[b]: the piece leaves as one contiguous run of the block's array, which
-// starts n * off[b] floats into u32.  One lane per row forms block after block's log-determinant, k in slot order as
+// starts n * off[b] floats into u32.  x may have columns that are nobody's slot (a.D > S, the slots' number: columns of a
+// Gaussian block, gauss_prior.hip): they go through the tile and are not read.  One lane per row forms block after block's log-determinant, k in slot order as
 // flow_prior_pre_kernel adds them, and then the rest's sum: no atomics, a row's bits depend on its values alone.
 __global__ __launch_bounds__(FP_THREADS) void joint_blocks_pre_kernel(
     JointBlocksArgs a, const double* __restrict__ x, int64_t row_stride, int64_t col_stride, int64_t n,
     float* __restrict__ u32, double* __restrict__ ldj, double* __restrict__ rest_logp, int32_t* __restrict__ inside) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int B = a.n_blocks, DF = a.off[B], Dr = a.rest.D, D = DF + Dr, LD = D | 1;
+    const int B = a.n_blocks, DF = a.off[B], Dr = a.rest.D, S = DF + Dr, D = a.D, LD = D | 1;
     double* T = sm;                                                       // [FP_ROWS][LD]: x, then J / the factor's term
     float* U = reinterpret_cast<float*>(sm + (size_t)FP_ROWS * LD);       // [FP_ROWS * DF]: block after block
     int* rowin = reinterpret_cast<int*>(U + (size_t)FP_ROWS * DF);        // [FP_ROWS]
-    int* cmap = rowin + FP_ROWS;                                          // [D]: tile column of every slot
+    int* cmap = rowin + FP_ROWS;                                          // [S]: tile column of every slot
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * FP_ROWS;
     const int rows = (int)min((int64_t)FP_ROWS, n - row0);
     if (tid < FP_ROWS) rowin[tid] = 1;
-    const int rpp = FP_THREADS / D;                                       // (D <= 157 < FP_THREADS)
-    const int r0 = tid / D, c = tid - r0 * D;
+    const int rpp = FP_THREADS / S;                                       // (S <= D <= 157 < FP_THREADS)
+    const int r0 = tid / S, c = tid - r0 * S;
     const bool act = r0 < rpp, is_flow = c < DF;
     // the slot's block: its scaler as this lane's own descriptor, its map, its first slot
     pmc_scaler_t s = a.s[0];
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(FP_THREADS) void joint_blocks_pre_kernel(
         if (is_flow) scaler_feat_request(f, s, (const pmc_prior_un_t*)nullptr, cb);
     }
     const bool col_ok = (unsigned)col < (unsigned)D;
-    if (tid < D) cmap[tid] = col_ok ? col : 0;                            // (tid < D: r0 == 0, c == tid)
+    if (tid < S) cmap[tid] = col_ok ? col : 0;                            // (tid < S: r0 == 0, c == tid)
     if (col_stride == 1) {
         int r = tid / D, cc = tid - r * D;                                // element e = r * D + cc, stepped without a division
         const int dr = FP_THREADS / D, dc = FP_THREADS - dr * D;
@@ -325,6 +331,8 @@ int pmc_joint_blocks_check(const pmc_joint_blocks_t* j, int* DF_out, int* Dr_out
         return pmc_fail("pmc_joint_blocks_pre: bad prior descriptor");
     const int64_t Dr = rest ? rest->D : 0;
     if (DF + Dr > FP_MAX_D) return pmc_fail("pmc_joint_blocks_pre: n_dim too large (sum Df + Dr <= 157)");
+    if (j->D != 0 && j->D < DF + Dr) return pmc_fail("pmc_joint_blocks_pre: D is smaller than the blocks and the rest together");
+    if (j->D > FP_MAX_D) return pmc_fail("pmc_joint_blocks_pre: n_dim too large (D <= 157)");
     if (rest && rest->n_extended > 0 && !rest->par)
         return pmc_fail("pmc_joint_blocks_pre: factors other than uniform / normal need the parameter table (par)");
     if (DF_out) *DF_out = (int)DF;
@@ -350,7 +358,8 @@ extern "C" int pmc_joint_blocks_pre(const pmc_joint_blocks_t* j, const double* x
     for (int b = j->n_blocks; b < PMC_JOINT_BLOCKS_MAX; ++b) a.off[b + 1] = a.off[b];
     if (j->rest) a.rest = *j->rest;
     a.rest_cols = j->rest_cols;
-    const size_t lds = joint_blocks_lds_bytes(DF, Dr);
+    a.D = j->D ? j->D : DF + Dr;
+    const size_t lds = joint_blocks_lds_bytes(DF, Dr, a.D);
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(joint_blocks_pre_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -227,7 +227,8 @@ static int blocks_stage_check(const pmc_step_t* s, const pmc_prior_blocks_stage_
     if (!s->p_x || !s->p_fin || !s->p_logp) return pmc_fail("pmc_step_prior_stage: needs p_x, p_fin and p_logp");
     int DF = 0, Dr = 0;
     if (int e = pmc_joint_blocks_check(&g->blocks, &DF, &Dr)) return e;     // (what pmc_joint_blocks_pre refuses, in its words)
-    if (DF + Dr != s->D) return pmc_fail("pmc_step_prior_stage: the prior's width is not the step's D");
+    if (DF + Dr != s->D || (g->blocks.D != 0 && g->blocks.D != s->D))
+        return pmc_fail("pmc_step_prior_stage: the prior's width is not the step's D");
     for (int b = 0; b < B; ++b)
         if (g->maf[b]->D != g->blocks.scaler[b]->D) return pmc_fail("pmc_step_prior_stage: the flow's width is not the scaler's");
     return 0;

@@ -18,7 +18,11 @@ prior's box, evaluated by two launches around the flow's own forward kernel (``c
 of launches (``csrc/joint_prior.hip``); its blocks form takes several flow priors on disjoint blocks of columns, in B + 2
 launches and still one pass over ``x``.
 
-Next to a HOST likelihood both can be evaluated by the MCMC step itself (``step_stage``, kernel option ``step_prior``): the same
+``GaussianPrior`` is a correlated normal, ``N(mean, cov)``: one float64 launch (``csrc/gauss_prior.hip``), alone or as a block of
+a ``JointPrior`` next to flow blocks and a table.
+
+Next to a HOST likelihood ``FlowPrior`` and ``JointPrior`` (without Gaussian blocks) can be evaluated by the MCMC step
+itself (``step_stage``, kernel option ``step_prior``): the same
 three launches on the step's stream, on the device's copy of x', while the host evaluates the likelihood."""
 from __future__ import annotations
 
@@ -582,6 +586,160 @@ class FlowPrior:
         return self.scaler.ndim
 
 
+class GaussianPrior:
+    """A correlated normal prior, ``x ~ N(mean, cov)`` in ``1 <= k <= 157`` dimensions: what an earlier result leaves where it
+    is a mean and a covariance matrix -- a published constraint, a Fisher forecast, a Laplace approximation -- and no flow.
+
+    ``mean``  ``(k,)`` finite floats; ``cov``  ``(k, k)`` finite, exactly symmetric (``np.array_equal(cov, cov.T)``: the user
+    symmetrises) and positive definite (``np.linalg.cholesky`` succeeds).  ``ValueError`` names what is wrong.  The constructor
+    is numpy alone: ``L = cholesky(cov)``, ``Linv = solve_triangular(L, I, lower=True)`` packed by rows (row i: i + 1 entries)
+    and ``logc = sum(log(diag(L))) + 0.5 k log(2 pi)``, all float64 (``device_block()``); the device's copies are made at the
+    first device call and dropped on pickling.
+
+    ``logpdf_device(x)``  the ``DevicePrior`` contract: an ``(n, k)`` float64 tensor on the device in, an ``(n,)`` float64 tensor
+                          out, on the current stream, in ONE launch (``pmc_gauss_blocks_logpdf``, ``csrc/gauss_prior.hip``) and
+                          no host synchronisation; no copy of ``x`` when it is C-contiguous or the MCMC step's column-major
+                          view (any other layout is made contiguous first).  The value is
+                          ``-0.5 |Linv (x - mean)|^2 - logc`` with every product and every sum rounded, in the order
+                          ``include/pocomc_amd.h`` fixes: the bits of ``tests/gauss_prior_model.py``, whatever the layout,
+                          ``n`` or the row's place in ``x``.  -inf for a row with a NaN or an inf and for a row whose arithmetic
+                          gives NaN; never NaN, never +inf.
+    ``logpdf(x)``         numpy in, numpy out, through the same function.
+    ``rvs(size)``         ``mean + z @ L.T``, ``z`` standard normal from numpy's global generator (``Sampler(random_state=...)``
+                          reaches it).
+    ``bounds``, ``dim``   ``(k, 2)`` of -inf / +inf, and k.
+
+    There is no ``device_descriptor`` and no ``step_stage``: the step calls the function (``Sampler(device_likelihood=True,
+    device_prior=True)``).  ``JointPrior`` takes it as a block next to flow priors and a table.  Out of scope: truncation (a box
+    around a correlated normal has no closed-form normalisation) and singular covariances."""
+
+    MAX_DIM = FlowPrior.MAX_DIM
+
+    def __init__(self, mean, cov):
+        try:
+            m = np.array(mean, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("GaussianPrior: mean must be a (k,) array of floats") from None
+        try:
+            c = np.array(cov, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("GaussianPrior: cov must be a (k, k) array of floats") from None
+        if m.ndim != 1:
+            raise ValueError(f"GaussianPrior: mean must have shape (k,), got {m.shape}")
+        k = len(m)
+        if not 1 <= k <= self.MAX_DIM:
+            raise ValueError(f"GaussianPrior: mean has {k} dimensions (1 <= k <= {self.MAX_DIM})")
+        if c.shape != (k, k):
+            raise ValueError(f"GaussianPrior: cov must have shape ({k}, {k}), got {c.shape}")
+        if not np.isfinite(m).all():
+            raise ValueError(f"GaussianPrior: mean[{int(np.argmin(np.isfinite(m)))}] is not finite")
+        if not np.isfinite(c).all():
+            i, j = np.argwhere(~np.isfinite(c))[0]
+            raise ValueError(f"GaussianPrior: cov[{i}, {j}] is not finite")
+        if not np.array_equal(c, c.T):
+            i, j = np.argwhere(c != c.T)[0]
+            raise ValueError(f"GaussianPrior: cov is not symmetric (cov[{i}, {j}] = {c[i, j]!r}, cov[{j}, {i}] = {c[j, i]!r}); "
+                             "symmetrise it, 0.5 * (cov + cov.T)")
+        try:
+            L = np.linalg.cholesky(c)
+        except np.linalg.LinAlgError:
+            raise ValueError("GaussianPrior: cov is not positive definite (np.linalg.cholesky fails)") from None
+        from scipy.linalg import solve_triangular
+        Linv = solve_triangular(L, np.eye(k), lower=True)
+        logc = float(np.sum(np.log(np.diag(L))) + 0.5 * k * np.log(2 * np.pi))
+        if not (np.isfinite(Linv).all() and np.isfinite(logc)):
+            raise ValueError("GaussianPrior: cov is too close to singular: the inverse of its Cholesky factor is not finite")
+        self.__setstate__(dict(mean=m, cov=c, L=L, linv_packed=np.ascontiguousarray(Linv[np.tril_indices(k)]), logc=logc))
+
+    # ----------------------------------------------------------------- state
+    def __getstate__(self):
+        return dict(mean=self.mean.copy(), cov=self.cov.copy(), L=self.L.copy(), linv_packed=self.linv_packed.copy(),
+                    logc=self.logc)
+
+    def __setstate__(self, st):
+        self.mean = np.array(st["mean"], dtype=np.float64)
+        self.cov = np.array(st["cov"], dtype=np.float64)
+        self.L = np.array(st["L"], dtype=np.float64)
+        self.linv_packed = np.array(st["linv_packed"], dtype=np.float64)
+        self.logc = float(st["logc"])
+        self._dev = None
+
+    def device_block(self):
+        """The device's constants as numpy arrays: ``mean`` (k,), ``linv_packed`` (k (k + 1) / 2,): row i of the inverse of
+        the Cholesky factor at ``i (i + 1) / 2``, and ``logc`` (a 0-d array).  No torch, no GPU."""
+        return dict(mean=self.mean.copy(), linv_packed=self.linv_packed.copy(), logc=np.array(self.logc, dtype=np.float64))
+
+    def _device(self, device):
+        """The device's copies and the one-block descriptor, made once, on ``device``."""
+        if self._dev is None:
+            import torch
+            from . import _lib
+            k = self.dim
+            dev = torch.device(device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d = dict(device=dev, mean=up(self.mean), linv=up(self.linv_packed), cols=up(np.arange(k, dtype=np.int32)))
+            g = _lib.pmc_gauss_blocks_t(n_blocks=1, D=k, rest=None, rest_cols=None)
+            g.dim[0], g.logc[0] = k, self.logc
+            g.cols[0], g.mean[0], g.linv[0] = d["cols"].data_ptr(), d["mean"].data_ptr(), d["linv"].data_ptr()
+            d["desc"] = g                                   # (it points into the tensors next to it)
+            self._dev = d
+        return self._dev
+
+    # ----------------------------------------------------------------- density
+    def logpdf_device(self, x):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        k = self.dim
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != k:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"GaussianPrior.logpdf_device: expected an (n, {k}) float64 tensor, got {what}")
+        if not x.is_cuda:
+            raise ValueError(f"GaussianPrior.logpdf_device: expected a tensor on the GPU, got one on {x.device}")
+        d = self._device(x.device)
+        _on_device(x, d["device"], "GaussianPrior.logpdf_device")
+        n = x.shape[0]
+        out = torch.empty(n, dtype=torch.float64, device=x.device)
+        if n == 0:
+            return out
+        # the two layouts the kernel reads with coalesced loads; everything else is copied once
+        if x.is_contiguous():
+            strides = (k, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (k, 1)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().pmc_gauss_blocks_logpdf(C.byref(d["desc"]), C.c_void_p(x.data_ptr()), strides[0],
+                                                           strides[1], n, None, _lib.ptr(out), _lib.stream_handle()),
+                       "pmc_gauss_blocks_logpdf")
+        return out
+
+    def logpdf(self, x):
+        import torch
+        from . import _lib
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"GaussianPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
+        dev = self._dev["device"] if self._dev is not None else _lib.require_gpu()
+        return self.logpdf_device(torch.from_numpy(x).to(dev)).cpu().numpy()
+
+    # ----------------------------------------------------------------- draws
+    def rvs(self, size=1):
+        size = int(size)
+        z = np.random.mtrand._rand.standard_normal((size, self.dim))     # (numpy's global generator, named: JointPrior.rvs)
+        return self.mean + z @ self.L.T
+
+    @property
+    def bounds(self):
+        return np.stack([np.full(self.dim, -np.inf), np.full(self.dim, np.inf)], axis=1)
+
+    @property
+    def dim(self):
+        return len(self.mean)
+
+
 class JointPrior:
     """A flow prior on some of the parameters and scipy factors on the others:
 
@@ -626,8 +784,20 @@ class JointPrior:
     the single form's contract otherwise.  ``rvs`` draws block 0, block 1, ... with each block's ``rvs`` (torch's global
     generator), then the rest with numpy's global generator.  ``step_stage`` gives the step a ``pmc_prior_blocks_stage_t``.
 
-    Out of scope: more than 8 blocks, non-diagonal scalers, the stage on sharded walkers, and -- as for every
-    ``DevicePrior`` -- lanes and graph capture."""
+    Gaussian blocks: the list takes a ``GaussianPrior`` wherever it takes a ``FlowPrior`` (of one column too), at most 8 blocks
+    of both kinds together, with or without a flow block: ``JointPrior([shared_a, planck], [[4, 0, 2], [1, 5, 6]], own)``,
+    ``JointPrior([planck], [[1, 5, 6]], own)``.  ``blocks`` counts the blocks of both kinds, ``flow_priors`` and
+    ``gaussian_priors`` are the owned copies of each kind in list order (a Gaussian block is copied through its state).  The
+    value is the flow blocks' and the table's value as above, then ``+ g`` for every Gaussian block in list order -- the
+    Gaussian blocks are added AFTER the flow blocks and the table, whatever their place in the list -- and equals the parts
+    evaluated on their gathered columns and added in that order, bit for bit; -inf outside any part's support, never NaN.
+    With a flow block the launches above run over the flow blocks and the table and one ``pmc_gauss_blocks_logpdf`` launch adds
+    the Gaussian blocks in place (B_flow + 3 launches); without one that launch evaluates the table as well (one launch, one
+    pass over ``x``).  ``rvs`` and ``bounds`` go by list order.  ``step_stage`` raises ``ValueError``: a prior with a Gaussian
+    block is for ``logpdf`` and for ``device_prior=True``, not for the step of a host likelihood.
+
+    Out of scope: more than 8 blocks, non-diagonal scalers, the stage on sharded walkers, truncated or singular Gaussian
+    blocks, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
 
     MAX_DIM = FlowPrior.MAX_DIM
     MAX_BLOCKS = 8           # PMC_JOINT_BLOCKS_MAX
@@ -741,13 +911,16 @@ class JointPrior:
 
     def __getstate__(self):
         if self.blocks:
-            return {"flow_priors": [fp.__getstate__() for fp in self.flow_priors],
-                    "columns": [c.tolist() for c in self._block_cols], "rest": self.rest}
+            st = {"flow_priors": [p.__getstate__() for p in self._parts],
+                  "columns": [c.tolist() for c in self._block_cols], "rest": self.rest}
+            if self.gaussian_priors:
+                st["kinds"] = list(self._kinds)               # (the blocks in list order: a flow's state or a Gaussian's)
+            return st
         return {"flow_prior": self.flow_prior.__getstate__(), "columns": self._flow_cols.tolist(), "rest": self.rest}
 
     def __setstate__(self, st):
         if "flow_priors" in st:
-            self._restore_blocks(st["flow_priors"], st["columns"], st["rest"])
+            self._restore_blocks(st["flow_priors"], st["columns"], st["rest"], kinds=st.get("kinds"))
         else:
             self._restore(st["flow_prior"], st["columns"], st["rest"])
 
@@ -757,15 +930,21 @@ class JointPrior:
     def _init_blocks(self, flow_priors, columns, rest):
         B = len(flow_priors)
         for b, fp in enumerate(flow_priors):
-            if not isinstance(fp, FlowPrior):
-                raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior, got {type(fp).__name__}")
+            if not isinstance(fp, (FlowPrior, GaussianPrior)):
+                raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior or GaussianPrior, got "
+                                 f"{type(fp).__name__}")
+        kinds = ["flow" if isinstance(fp, FlowPrior) else "gauss" for fp in flow_priors]
         if not 1 <= B <= self.MAX_BLOCKS:
-            raise ValueError(f"JointPrior: {B} flow blocks (1 <= blocks <= {self.MAX_BLOCKS})")
+            raise ValueError(f"JointPrior: {B} blocks ({kinds.count('flow')} flow blocks, {kinds.count('gauss')} Gaussian "
+                             f"blocks; 1 <= blocks <= {self.MAX_BLOCKS})")
         import torch
-        devs = [torch.device(fp.flow.device) for fp in flow_priors]
-        for b in range(1, B):
-            if devs[b] != devs[0]:
-                raise ValueError(f"JointPrior: blocks 0 and {b} are on different devices ({devs[0]}, {devs[b]})")
+        # (a Gaussian block that has not been on a device yet goes where the others are)
+        devs = [torch.device(fp.flow.device) if k == "flow" else None if fp._dev is None else fp._dev["device"]
+                for k, fp in zip(kinds, flow_priors)]
+        known = [b for b in range(B) if devs[b] is not None]
+        for b in known[1:]:
+            if devs[b] != devs[known[0]]:
+                raise ValueError(f"JointPrior: blocks {known[0]} and {b} are on different devices ({devs[known[0]]}, {devs[b]})")
         if rest is not None:
             if not isinstance(rest, Prior):
                 raise ValueError(f"JointPrior: rest must be a pocomc_amd.Prior or None, got {type(rest).__name__}")
@@ -773,33 +952,48 @@ class JointPrior:
                 raise ValueError("JointPrior: rest needs at least one factor (rest=None: the blocks cover every column)")
             if rest.device_table() is None:
                 raise ValueError("JointPrior: the device must evaluate rest: build it as Prior(dists, device=True)")
-        dims, Dr = [fp.dim for fp in flow_priors], 0 if rest is None else rest.dim
+        dims, Dr = [fp.dim for fp in flow_priors], 0 if rest is None else rest.dim      # (blocks of both kinds)
         if sum(dims) + Dr > self.MAX_DIM:
             raise ValueError(f"JointPrior: n_dim = {' + '.join(str(d) for d in dims + [Dr])} is too large "
                              f"(n_dim <= {self.MAX_DIM})")
         maps, _ = self.layout_blocks(columns, dims, Dr)
-        self._restore_blocks([fp.__getstate__() for fp in flow_priors], [m.tolist() for m in maps], rest, devs[0])
+        self._restore_blocks([fp.__getstate__() for fp in flow_priors], [m.tolist() for m in maps], rest,
+                             devs[known[0]] if known else None, kinds)
 
-    def _restore_blocks(self, states, columns, rest, device=None):
+    def _restore_blocks(self, states, columns, rest, device=None, kinds=None):
+        """``states``, ``columns``, ``kinds`` (``"flow"`` / ``"gauss"``; None: every block a flow): the blocks in list order."""
         import copy
         import ctypes as C
         import torch
         from . import _lib
-        fps = []
-        for st in states:
-            fp = FlowPrior.__new__(FlowPrior)
-            fp._restore(st["flow"], st["scaler"], device)
-            device = fp.flow.device                                # (an unpickled prior: every block where the first one went)
-            fps.append(fp)
-        self.flow_priors = tuple(fps)
-        self.blocks = len(fps)
+        kinds = ["flow"] * len(states) if kinds is None else list(kinds)
+        parts = []
+        for kind, st in zip(kinds, states):
+            if kind == "flow":
+                fp = FlowPrior.__new__(FlowPrior)
+                fp._restore(st["flow"], st["scaler"], device)
+                device = fp.flow.device                            # (an unpickled prior: every block where the first one went)
+            else:
+                fp = GaussianPrior.__new__(GaussianPrior)
+                fp.__setstate__(copy.deepcopy(st))
+            parts.append(fp)
+        fps = [p for k, p in zip(kinds, parts) if k == "flow"]
+        gps = [p for k, p in zip(kinds, parts) if k == "gauss"]
+        self._kinds, self._parts = tuple(kinds), tuple(parts)
+        self.flow_priors, self.gaussian_priors = tuple(fps), tuple(gps)
+        self.blocks = len(parts)
         self.rest = copy.deepcopy(rest)
         Dr = 0 if self.rest is None else self.rest.dim
-        self._block_cols, self._rest_cols = self.layout_blocks(columns, [fp.dim for fp in fps], Dr)
-        dev = fps[0].flow.device
+        self._block_cols, self._rest_cols = self.layout_blocks(columns, [p.dim for p in parts], Dr)
+        self._dim = sum(p.dim for p in parts) + Dr
+        dev = torch.device(fps[0].flow.device if fps else device if device is not None else _lib.require_gpu())
+        self._device = dev
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        flow_cols = [c for k, c in zip(kinds, self._block_cols) if k == "flow"]
+        gauss_cols = [c for k, c in zip(kinds, self._block_cols) if k == "gauss"]
         # (the descriptors point into these tensors: they live as long as the descriptors do)
-        self._dev = dict(cols=[up(c) for c in self._block_cols], rest_cols=up(self._rest_cols) if Dr else None)
+        self._dev = dict(cols=[up(c) for c in flow_cols], gauss_cols=[up(c) for c in gauss_cols],
+                         rest_cols=up(self._rest_cols) if Dr else None)
         self._rdesc = None
         if Dr:
             tab = self.rest.device_table()
@@ -809,13 +1003,27 @@ class JointPrior:
             self._rdesc = _lib.pmc_prior_t(family=self._dev["family"].data_ptr(), loc=self._dev["loc"].data_ptr(),
                                            scale=self._dev["scale"].data_ptr(), D=Dr, reserved=0,
                                            par=self._dev["par"].data_ptr() if n_ext else None, n_extended=n_ext, reserved2=0)
-        j = _lib.pmc_joint_blocks_t(n_blocks=self.blocks, reserved=0,
-                                    rest=C.cast(C.pointer(self._rdesc), C.c_void_p) if Dr else None,
-                                    rest_cols=self._dev["rest_cols"].data_ptr() if Dr else None)
-        for b, fp in enumerate(fps):
-            j.scaler[b] = C.cast(C.pointer(fp._sdesc), C.c_void_p)
-            j.cols[b] = self._dev["cols"][b].data_ptr()
-        self._jdesc = j
+        rest_ptr = C.cast(C.pointer(self._rdesc), C.c_void_p) if Dr else None
+        rest_cols_ptr = self._dev["rest_cols"].data_ptr() if Dr else None
+        self._jdesc = None
+        if fps:
+            # (D: x has the Gaussian blocks' columns as well; 0 where the flow blocks and the table cover every column)
+            j = _lib.pmc_joint_blocks_t(n_blocks=len(fps), D=self._dim if gps else 0, rest=rest_ptr, rest_cols=rest_cols_ptr)
+            for b, fp in enumerate(fps):
+                j.scaler[b] = C.cast(C.pointer(fp._sdesc), C.c_void_p)
+                j.cols[b] = self._dev["cols"][b].data_ptr()
+            self._jdesc = j
+        self._gdesc = None
+        if gps:
+            # (the table goes through this launch only where no flow launch has taken it)
+            g = _lib.pmc_gauss_blocks_t(n_blocks=len(gps), D=self._dim, rest=None if fps else rest_ptr,
+                                        rest_cols=None if fps else rest_cols_ptr)
+            for b, gp in enumerate(gps):
+                d = gp._device(dev)
+                g.dim[b], g.logc[b] = gp.dim, gp.logc
+                g.cols[b] = self._dev["gauss_cols"][b].data_ptr()
+                g.mean[b], g.linv[b] = d["mean"].data_ptr(), d["linv"].data_ptr()
+            self._gdesc = g
         self._offsets = np.concatenate([[0], np.cumsum([fp.dim for fp in fps])]).astype(np.int64)
         self._ws = {}
 
@@ -830,8 +1038,8 @@ class JointPrior:
                   # block b's [n][Df_b] piece of u32, and the one z every flow writes in turn (not used)
                   [u32[n * int(off[b]):n * int(off[b + 1])].view(n, fp.dim) for b, fp in enumerate(self.flow_priors)],
                   [z[:n * fp.dim].view(n, fp.dim) for fp in self.flow_priors],
-                  torch.empty(self.blocks, n, dtype=torch.float32, device=dev),      # the flows' log_prob
-                  torch.empty(self.blocks, n, dtype=torch.float64, device=dev),      # the scalers' log-determinants
+                  torch.empty(len(self.flow_priors), n, dtype=torch.float32, device=dev),      # the flows' log_prob
+                  torch.empty(len(self.flow_priors), n, dtype=torch.float64, device=dev),      # the scalers' log-determinants
                   torch.empty(n, dtype=torch.float64, device=dev) if self._rdesc is not None else None,
                   torch.empty(n, dtype=torch.int32, device=dev))                     # inside the support (one flag per row)
             while len(self._ws) >= self._WORKSPACES:
@@ -868,7 +1076,7 @@ class JointPrior:
                                                 _lib.stream_handle()), "pmc_joint_blocks_pre")
             for b, fp in enumerate(self.flow_priors):
                 fp.flow._forward_call(u32_b[b], z_b[b], None, lp32[b], n)
-            _lib.check(lib.pmc_joint_blocks_post(self.blocks, _lib.ptr(lp32), _lib.ptr(ldj), _lib.ptr(rest_logp),
+            _lib.check(lib.pmc_joint_blocks_post(len(self.flow_priors), _lib.ptr(lp32), _lib.ptr(ldj), _lib.ptr(rest_logp),
                                                  _lib.ptr(inside), _lib.ptr(out), n, _lib.stream_handle()),
                        "pmc_joint_blocks_post")
         return out
@@ -890,8 +1098,8 @@ class JointPrior:
         with torch.cuda.device(dev):
             ws = dict(u32=torch.empty(n * int(self._offsets[-1]), dtype=torch.float32, device=dev),
                       z=torch.empty(n * max(fp.dim for fp in self.flow_priors), dtype=torch.float32, device=dev),
-                      lp32=torch.empty(self.blocks, n, dtype=torch.float32, device=dev),
-                      ldj=torch.empty(self.blocks, n, dtype=torch.float64, device=dev),
+                      lp32=torch.empty(len(self.flow_priors), n, dtype=torch.float32, device=dev),
+                      ldj=torch.empty(len(self.flow_priors), n, dtype=torch.float64, device=dev),
                       rest_logp=torch.empty(n, dtype=torch.float64, device=dev) if self._rdesc is not None else None,
                       inside=torch.empty(n, dtype=torch.int32, device=dev),
                       count=torch.zeros(2, dtype=torch.int64, device=dev))
@@ -914,7 +1122,7 @@ class JointPrior:
 
     def _rvs_blocks(self, size):
         x = np.empty((size, self.dim), dtype=np.float64)
-        for cols, fp in zip(self._block_cols, self.flow_priors):          # block 0, block 1, ..., then the rest
+        for cols, fp in zip(self._block_cols, self._parts):               # block 0, block 1, ..., then the rest
             x[:, cols] = fp.rvs(size)
         if self.rest is not None:
             glob = np.random.mtrand._rand                                 # (numpy's global generator, named: see rvs)
@@ -938,7 +1146,41 @@ class JointPrior:
             self._ws[n] = ws
         return ws
 
+    def _logpdf_device_gauss(self, x):
+        """The blocks form with Gaussian blocks: the flow blocks' launches with the table as ``_logpdf_device_blocks`` makes
+        them, then one ``pmc_gauss_blocks_logpdf`` launch that adds the Gaussian blocks in place; without a flow block that one
+        launch alone, the table in it."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        D, dev = self.dim, self._device
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"JointPrior.logpdf_device: expected an (n, {D}) float64 tensor, got {what}")
+        _on_device(x, dev, "JointPrior.logpdf_device")
+        n = x.shape[0]
+        if n == 0:
+            return torch.empty(0, dtype=torch.float64, device=dev)
+        # the two layouts the kernels read with coalesced loads; everything else is copied once, for both
+        if x.is_contiguous():
+            strides = (D, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (D, 1)
+        out = self._logpdf_device_blocks(x) if self.flow_priors else torch.empty(n, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().pmc_gauss_blocks_logpdf(C.byref(self._gdesc), C.c_void_p(x.data_ptr()), strides[0],
+                                                           strides[1], n, _lib.ptr(out) if self.flow_priors else None,
+                                                           _lib.ptr(out), _lib.stream_handle()), "pmc_gauss_blocks_logpdf")
+        return out
+
+    gaussian_priors = ()          # the owned copies of the Gaussian blocks, in list order (the blocks form)
+
     def logpdf_device(self, x):
+        if self.gaussian_priors:
+            return self._logpdf_device_gauss(x)
         if self.blocks:
             return self._logpdf_device_blocks(x)
         import ctypes as C
@@ -979,11 +1221,14 @@ class JointPrior:
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"JointPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
-        dev = self.flow_priors[0].flow.device if self.blocks else self.flow_prior.flow.device
+        dev = self._device if self.blocks else self.flow_prior.flow.device
         return self.logpdf_device(torch.from_numpy(x).to(dev)).cpu().numpy()
 
     def step_stage(self, n, device=None):
         """``FlowPrior.step_stage`` for the joint prior: the descriptor carries the column maps and the table as well."""
+        if self.gaussian_priors:
+            raise ValueError("JointPrior.step_stage: a prior with a Gaussian block is not evaluated inside the step of a host "
+                             "likelihood (step_prior); use logpdf, or device_prior=True with a device likelihood")
         if self.blocks:
             return self._step_stage_blocks(n, device)
         return _step_stage(self, self.flow_prior, n, device,
@@ -1006,7 +1251,7 @@ class JointPrior:
     def bounds(self):
         b = np.empty((self.dim, 2), dtype=np.float64)
         if self.blocks:
-            for cols, fp in zip(self._block_cols, self.flow_priors):
+            for cols, fp in zip(self._block_cols, self._parts):
                 b[cols] = fp.bounds
             if self.rest is not None:
                 b[self._rest_cols] = self.rest.bounds
@@ -1018,5 +1263,5 @@ class JointPrior:
     @property
     def dim(self):
         if self.blocks:
-            return int(self._offsets[-1]) + (0 if self.rest is None else self.rest.dim)
+            return self._dim
         return self.flow_prior.dim + self.rest.dim
