@@ -1254,6 +1254,23 @@ typedef struct pmc_gauss_blocks {
 int pmc_gauss_blocks_logpdf(const pmc_gauss_blocks_t* g, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
                             const double* base, double* logp, void* stream);
 
+/* The same blocks, some of them restricted to a closed box (pocomc_amd.TruncatedGaussianPrior, alone or as a block of
+ * pocomc_amd.JointPrior): pmc_gauss_blocks_logpdf's contract plus one rule -- a row with any x[cols_b[j]] that is not in
+ * [lo_b[j], hi_b[j]] gets -inf.  The test is !(x >= lo && x <= hi): the value on a bound is finite, the first float beyond
+ * it is -inf, and a NaN fails it.  Every other row has exactly the bits pmc_gauss_blocks_logpdf gives for the same
+ * descriptor; the caller puts logc + log_mass, the log of the box's mass under the block's normal, into g->logc[b].
+ * Appended within ABI 9: a new entry and a new struct only; the kernel is a second instance of the same template, the
+ * entry above launches the instance without the test.
+ * Refused before anything is launched or written: everything pmc_gauss_blocks_logpdf refuses, with the same texts under
+ * this entry's name; a NULL box; a block with one of lo / hi set and the other NULL.  Entries b >= n_blocks are not read.
+ * n == 0 returns 0 and reads no array. */
+typedef struct pmc_gauss_box {            /* per block of the pmc_gauss_blocks_t it goes with */
+    const double* lo[PMC_GAUSS_BLOCKS_MAX];   /* f64 [dim[b]], device memory, -inf allowed; NULL with hi[b]: block b has no box */
+    const double* hi[PMC_GAUSS_BLOCKS_MAX];
+} pmc_gauss_box_t;
+int pmc_gauss_box_logpdf(const pmc_gauss_blocks_t* g, const pmc_gauss_box_t* box, const double* x, int64_t row_stride,
+                         int64_t col_stride, int64_t n, const double* base, double* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ gfx950 kernels behind the C ABI of ``include/pocomc_amd.h``.
 """
 from .maf_spec import MAFSpec  # noqa: F401
 
-__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "GaussianPrior", "JointPrior", "mcmc", "tools"]
+__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "GaussianPrior", "TruncatedGaussianPrior", "JointPrior", "mcmc", "tools"]
 
 
 def __getattr__(name):
@@ -35,6 +35,9 @@ def __getattr__(name):
     if name == "GaussianPrior":
         from .prior import GaussianPrior
         return GaussianPrior
+    if name == "TruncatedGaussianPrior":
+        from .prior import TruncatedGaussianPrior
+        return TruncatedGaussianPrior
     if name == "JointPrior":
         from .prior import JointPrior
         return JointPrior

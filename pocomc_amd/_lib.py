@@ -165,6 +165,10 @@ class pmc_gauss_blocks_t(C.Structure):
                 ("rest", c_p), ("rest_cols", c_p)]
 
 
+class pmc_gauss_box_t(C.Structure):
+    _fields_ = [("lo", c_p * PMC_GAUSS_BLOCKS_MAX), ("hi", c_p * PMC_GAUSS_BLOCKS_MAX)]
+
+
 # name -> (restype, argtypes); every symbol include/pocomc_amd.h declares
 i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
 P = C.POINTER
@@ -284,6 +288,7 @@ SIGNATURES = {
     "pmc_joint_blocks_pre": (C.c_int, [P(pmc_joint_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p, c_p, c_p]),
     "pmc_joint_blocks_post": (C.c_int, [i32, c_p, c_p, c_p, c_p, c_p, i64, c_p]),
     "pmc_gauss_blocks_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
+    "pmc_gauss_box_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), P(pmc_gauss_box_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
 }
 
 _lib = None

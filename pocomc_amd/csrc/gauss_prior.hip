@@ -4,6 +4,8 @@
 // Linv_b the inverse of the lower Cholesky factor of block b's covariance, packed by rows.  One launch, float64 VALU, one
 // pass over x.  The order of every addition is fixed (include/pocomc_amd.h, tests/gauss_prior_model.py) and nothing is
 // contracted into an FMA: a row's bits are those of the numpy model.
+// With a box (TruncatedGaussianPrior, pmc_gauss_box_logpdf) a block's columns are also held to lo_j <= x_j <= hi_j: a row
+// outside gets -inf, every other row keeps its bits (the caller has put the box's log mass into logc).
 #include "pmc_internal.h"
 #include "flow_prior_body.h"
 #include "prior_body.h"
@@ -26,6 +28,11 @@ struct GaussBlocksArgs {
     pmc_prior_t rest;
     const int32_t* rest_cols;
 };
+// The boxes of pmc_gauss_box_t, by value as well; a block without a box has a NULL pair.
+struct GaussBoxArgs {
+    const double* lo[PMC_GAUSS_BLOCKS_MAX];
+    const double* hi[PMC_GAUSS_BLOCKS_MAX];
+};
 
 static inline size_t gauss_blocks_lds_bytes(int D) {
     return (size_t)FP_ROWS * (D | 1) * sizeof(double) + FP_ROWS * sizeof(int);
@@ -46,6 +53,21 @@ struct GaussBlock {
     double logc;
     int k;
 };
+struct GaussBox {
+    gp_f64 lo;
+    gp_f64 hi;
+};
+__device__ __forceinline__ GaussBox gauss_box(const GaussBoxArgs& a, int bb) {
+    GaussBox g = {(gp_f64)a.lo[0], (gp_f64)a.hi[0]};
+#pragma unroll
+    for (int b = 1; b < PMC_GAUSS_BLOCKS_MAX; ++b) {
+        if (b == bb) {
+            g.lo = (gp_f64)a.lo[b];
+            g.hi = (gp_f64)a.hi[b];
+        }
+    }
+    return g;
+}
 __device__ __forceinline__ GaussBlock gauss_block(const GaussBlocksArgs& a, int bb) {
     GaussBlock g = {(gp_i32)a.cols[0], (gp_f64)a.mean[0], (gp_f64)a.linv[0], a.logc[0], a.dim[0]};
 #pragma unroll
@@ -72,7 +94,9 @@ __device__ __forceinline__ int gauss_col(gp_i32 cols, int j, int D) {
 // so that every constant -- a column index, a mean, an entry of Linv, a table factor's family -- sits at an address the
 // whole wavefront shares, and the lanes of a wavefront walk the tile at an odd stride.
 //   1. every block column's x becomes d = x - mean in place, every table column's x its factor's term; a row with an x
-//      that is not finite or a table term that is NaN is marked in rowin.
+//      that is not finite or a table term that is NaN is marked in rowin.  BOX: so is a row with a block column's x outside
+//      [lo_j, hi_j] (a NaN fails the test as written); lo and hi are read like mean, with scalar loads, and a block with a
+//      NULL pair has no box.  The instance without BOX never looks at the box argument.
 //   2. block after block, i from k - 1 down in steps of 8 * GP_ACC: wavefront w forms y_i of i = top - GP_ACC w - u,
 //      u = 0 .. GP_ACC - 1, in ONE walk over d_0 .. d_i (each y_i = ((0.0 + Linv[i,0] d_0) + Linv[i,1] d_1) + ..., every
 //      product and every sum rounded).  The lane's rows are neighbours: their walks end within three entries of each
@@ -87,9 +111,10 @@ __device__ __forceinline__ int gauss_col(gp_i32 cols, int j, int D) {
 //      q = ((0.0 + y_0 y_0) + y_1 y_1) + ..., g = -0.5 q - logc, v = start + g_0 + g_1 + ... left to right.
 // The bits of a row depend on its values alone.  A column outside [0, D) is not followed: the rows of its tile are marked.
 // Every barrier is reached by every thread: the trip counts depend on the descriptor alone.
+template <bool BOX>
 __global__ __launch_bounds__(FP_THREADS) void gauss_blocks_kernel(GaussBlocksArgs a, const double* __restrict__ x,
                                                                   int64_t row_stride, int64_t col_stride, int64_t n,
-                                                                  const double* base, double* logp) {
+                                                                  const double* base, double* logp, GaussBoxArgs box) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int B = a.n_blocks, D = a.D, Dr = a.Dr, LD = D | 1;
     double* T = sm;                                                       // [FP_ROWS][LD]
@@ -123,6 +148,8 @@ __global__ __launch_bounds__(FP_THREADS) void gauss_blocks_kernel(GaussBlocksArg
     // 1. the elements
     for (int bb = 0; bb < B; ++bb) {
         const GaussBlock g = gauss_block(a, bb);
+        GaussBox bx = {nullptr, nullptr};
+        if (BOX) bx = gauss_box(box, bb);
         for (int j = w; j < g.k; j += GP_WAVES) {
             const int c = g.cols[j];
             const bool col_ok = (unsigned)c < (unsigned)D;
@@ -131,6 +158,9 @@ __global__ __launch_bounds__(FP_THREADS) void gauss_blocks_kernel(GaussBlocksArg
             const double xv = Tr[c];
             Tr[c] = xv - g.mean[j];
             if (!isfinite(xv)) rowin[r] = 0;
+            if (BOX && bx.lo) {
+                if (!(xv >= bx.lo[j] && xv <= bx.hi[j])) rowin[r] = 0;
+            }
         }
     }
     for (int m = w; m < Dr; m += GP_WAVES) {
@@ -206,32 +236,42 @@ __global__ __launch_bounds__(FP_THREADS) void gauss_blocks_kernel(GaussBlocksArg
     }
 }
 
-extern "C" int pmc_gauss_blocks_logpdf(const pmc_gauss_blocks_t* g, const double* x, int64_t row_stride, int64_t col_stride,
-                                       int64_t n, const double* base, double* logp, void* stream) {
-    if (!g) return pmc_fail("pmc_gauss_blocks_logpdf: bad descriptor");
-    if (g->n_blocks < 1 || g->n_blocks > PMC_GAUSS_BLOCKS_MAX)
-        return pmc_fail("pmc_gauss_blocks_logpdf: n_blocks must lie in 1 .. 8");
+// Both entries: the checks (the texts under the entry's name), the arguments by value, the launch of one instance.
+static int gauss_blocks_launch(const char* who, const pmc_gauss_blocks_t* g, const pmc_gauss_box_t* box, bool with_box,
+                               const double* x, int64_t row_stride, int64_t col_stride, int64_t n, const double* base,
+                               double* logp, void* stream) {
+    char msg[192];
+#define GP_FAIL(text) return (snprintf(msg, sizeof msg, "%s: " text, who), pmc_fail(msg))
+    if (!g) GP_FAIL("bad descriptor");
+    if (g->n_blocks < 1 || g->n_blocks > PMC_GAUSS_BLOCKS_MAX) GP_FAIL("n_blocks must lie in 1 .. 8");
     int64_t K = 0;
     for (int b = 0; b < g->n_blocks; ++b) {
-        if (!g->cols[b] || !g->mean[b] || !g->linv[b]) return pmc_fail("pmc_gauss_blocks_logpdf: bad block descriptor");
-        if (g->dim[b] < 1) return pmc_fail("pmc_gauss_blocks_logpdf: every block needs at least 1 column (dim >= 1)");
+        if (!g->cols[b] || !g->mean[b] || !g->linv[b]) GP_FAIL("bad block descriptor");
+        if (g->dim[b] < 1) GP_FAIL("every block needs at least 1 column (dim >= 1)");
         K += g->dim[b];
     }
-    if (g->D > FP_MAX_D) return pmc_fail("pmc_gauss_blocks_logpdf: n_dim too large (D <= 157)");
+    if (g->D > FP_MAX_D) GP_FAIL("n_dim too large (D <= 157)");
     const pmc_prior_t* rest = g->rest;
-    if ((rest == nullptr) != (g->rest_cols == nullptr))
-        return pmc_fail("pmc_gauss_blocks_logpdf: rest and rest_cols go together (both, or both NULL)");
+    if ((rest == nullptr) != (g->rest_cols == nullptr)) GP_FAIL("rest and rest_cols go together (both, or both NULL)");
     if (rest && (!rest->family || !rest->loc || !rest->scale || rest->n_extended < 0 || rest->D < 1))
-        return pmc_fail("pmc_gauss_blocks_logpdf: bad prior descriptor");
+        GP_FAIL("bad prior descriptor");
     const int64_t Dr = rest ? rest->D : 0;
-    if (K + Dr > g->D) return pmc_fail("pmc_gauss_blocks_logpdf: the blocks and the rest have more columns than x (D)");
+    if (K + Dr > g->D) GP_FAIL("the blocks and the rest have more columns than x (D)");
     if (rest && rest->n_extended > 0 && !rest->par)
-        return pmc_fail("pmc_gauss_blocks_logpdf: factors other than uniform / normal need the parameter table (par)");
-    if (base && rest) return pmc_fail("pmc_gauss_blocks_logpdf: base and rest exclude each other");
+        GP_FAIL("factors other than uniform / normal need the parameter table (par)");
+    if (base && rest) GP_FAIL("base and rest exclude each other");
+    if (with_box) {
+        if (!box) GP_FAIL("bad box descriptor (NULL)");
+        for (int b = 0; b < g->n_blocks; ++b)
+            if ((box->lo[b] == nullptr) != (box->hi[b] == nullptr))
+                GP_FAIL("lo and hi of a block go together (both, or both NULL: no box)");
+    }
     if (n == 0) return 0;
-    if (!x || !logp || n < 0 || row_stride < 0 || col_stride < 0) return pmc_fail("pmc_gauss_blocks_logpdf: bad argument");
-    if ((n + FP_ROWS - 1) / FP_ROWS > 0x7fffffffLL) return pmc_fail("pmc_gauss_blocks_logpdf: too many rows for one launch");
+    if (!x || !logp || n < 0 || row_stride < 0 || col_stride < 0) GP_FAIL("bad argument");
+    if ((n + FP_ROWS - 1) / FP_ROWS > 0x7fffffffLL) GP_FAIL("too many rows for one launch");
+#undef GP_FAIL
     GaussBlocksArgs a = {};
+    GaussBoxArgs bx = {};
     a.n_blocks = g->n_blocks;
     a.D = g->D;
     for (int b = 0; b < PMC_GAUSS_BLOCKS_MAX; ++b) {
@@ -241,17 +281,38 @@ extern "C" int pmc_gauss_blocks_logpdf(const pmc_gauss_blocks_t* g, const double
         a.linv[b] = g->linv[s];
         a.logc[b] = g->logc[s];
         a.dim[b] = g->dim[s];
+        if (with_box) {
+            bx.lo[b] = box->lo[s];
+            bx.hi[b] = box->hi[s];
+        }
     }
     a.Dr = (int32_t)Dr;
     if (rest) a.rest = *rest;
     a.rest_cols = g->rest_cols;
     const size_t lds = gauss_blocks_lds_bytes(g->D);
+    const void* kernel = with_box ? reinterpret_cast<const void*>(gauss_blocks_kernel<true>)
+                                  : reinterpret_cast<const void*>(gauss_blocks_kernel<false>);
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gauss_blocks_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return pmc_fail_hip(e, "hipFuncSetAttribute(gauss_blocks_kernel)");
     }
-    hipLaunchKernelGGL(gauss_blocks_kernel, dim3((unsigned)((n + FP_ROWS - 1) / FP_ROWS)), dim3(FP_THREADS), lds,
-                       (hipStream_t)stream, a, x, row_stride, col_stride, n, base, logp);
+    const dim3 grid((unsigned)((n + FP_ROWS - 1) / FP_ROWS)), block(FP_THREADS);
+    if (with_box)
+        hipLaunchKernelGGL(gauss_blocks_kernel<true>, grid, block, lds, (hipStream_t)stream, a, x, row_stride, col_stride, n,
+                           base, logp, bx);
+    else
+        hipLaunchKernelGGL(gauss_blocks_kernel<false>, grid, block, lds, (hipStream_t)stream, a, x, row_stride, col_stride, n,
+                           base, logp, bx);
     return pmc_check_launch("gauss_blocks_kernel");
+}
+
+extern "C" int pmc_gauss_blocks_logpdf(const pmc_gauss_blocks_t* g, const double* x, int64_t row_stride, int64_t col_stride,
+                                       int64_t n, const double* base, double* logp, void* stream) {
+    return gauss_blocks_launch("pmc_gauss_blocks_logpdf", g, nullptr, false, x, row_stride, col_stride, n, base, logp, stream);
+}
+
+extern "C" int pmc_gauss_box_logpdf(const pmc_gauss_blocks_t* g, const pmc_gauss_box_t* box, const double* x,
+                                    int64_t row_stride, int64_t col_stride, int64_t n, const double* base, double* logp,
+                                    void* stream) {
+    return gauss_blocks_launch("pmc_gauss_box_logpdf", g, box, true, x, row_stride, col_stride, n, base, logp, stream);
 }

@@ -21,6 +21,9 @@ launches and still one pass over ``x``.
 ``GaussianPrior`` is a correlated normal, ``N(mean, cov)``: one float64 launch (``csrc/gauss_prior.hip``), alone or as a block of
 a ``JointPrior`` next to flow blocks and a table.
 
+``TruncatedGaussianPrior`` is that normal restricted to a box and normalised: the box's mass is one number, computed once on
+the host, and the same launch tests the box (``pmc_gauss_box_logpdf``); alone or as a block of a ``JointPrior``.
+
 Next to a HOST likelihood ``FlowPrior`` and ``JointPrior`` (without Gaussian blocks) can be evaluated by the MCMC step
 itself (``step_stage``, kernel option ``step_prior``): the same
 three launches on the step's stream, on the device's copy of x', while the host evaluates the likelihood."""
@@ -610,12 +613,17 @@ class GaussianPrior:
     ``bounds``, ``dim``   ``(k, 2)`` of -inf / +inf, and k.
 
     There is no ``device_descriptor`` and no ``step_stage``: the step calls the function (``Sampler(device_likelihood=True,
-    device_prior=True)``).  ``JointPrior`` takes it as a block next to flow priors and a table.  Out of scope: truncation (a box
-    around a correlated normal has no closed-form normalisation) and singular covariances."""
+    device_prior=True)``).  ``JointPrior`` takes it as a block next to flow priors and a table.  Out of scope: singular
+    covariances.  A box around it: ``TruncatedGaussianPrior``."""
 
     MAX_DIM = FlowPrior.MAX_DIM
 
     def __init__(self, mean, cov):
+        self.__setstate__(self._constants(mean, cov))
+
+    @classmethod
+    def _constants(cls, mean, cov):
+        """The checks and the host-side constants: the state of a ``GaussianPrior(mean, cov)``."""
         try:
             m = np.array(mean, dtype=np.float64)
         except (TypeError, ValueError):
@@ -627,8 +635,8 @@ class GaussianPrior:
         if m.ndim != 1:
             raise ValueError(f"GaussianPrior: mean must have shape (k,), got {m.shape}")
         k = len(m)
-        if not 1 <= k <= self.MAX_DIM:
-            raise ValueError(f"GaussianPrior: mean has {k} dimensions (1 <= k <= {self.MAX_DIM})")
+        if not 1 <= k <= cls.MAX_DIM:
+            raise ValueError(f"GaussianPrior: mean has {k} dimensions (1 <= k <= {cls.MAX_DIM})")
         if c.shape != (k, k):
             raise ValueError(f"GaussianPrior: cov must have shape ({k}, {k}), got {c.shape}")
         if not np.isfinite(m).all():
@@ -649,7 +657,7 @@ class GaussianPrior:
         logc = float(np.sum(np.log(np.diag(L))) + 0.5 * k * np.log(2 * np.pi))
         if not (np.isfinite(Linv).all() and np.isfinite(logc)):
             raise ValueError("GaussianPrior: cov is too close to singular: the inverse of its Cholesky factor is not finite")
-        self.__setstate__(dict(mean=m, cov=c, L=L, linv_packed=np.ascontiguousarray(Linv[np.tril_indices(k)]), logc=logc))
+        return dict(mean=m, cov=c, L=L, linv_packed=np.ascontiguousarray(Linv[np.tril_indices(k)]), logc=logc)
 
     # ----------------------------------------------------------------- state
     def __getstate__(self):
@@ -679,7 +687,7 @@ class GaussianPrior:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             d = dict(device=dev, mean=up(self.mean), linv=up(self.linv_packed), cols=up(np.arange(k, dtype=np.int32)))
             g = _lib.pmc_gauss_blocks_t(n_blocks=1, D=k, rest=None, rest_cols=None)
-            g.dim[0], g.logc[0] = k, self.logc
+            g.dim[0], g.logc[0] = k, self._logc_device
             g.cols[0], g.mean[0], g.linv[0] = d["cols"].data_ptr(), d["mean"].data_ptr(), d["linv"].data_ptr()
             d["desc"] = g                                   # (it points into the tensors next to it)
             self._dev = d
@@ -691,14 +699,14 @@ class GaussianPrior:
         import torch
         from . import _lib
         from .mcmc import _on_device
-        k = self.dim
+        k, who = self.dim, type(self).__name__
         if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != k:
             what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
-            raise ValueError(f"GaussianPrior.logpdf_device: expected an (n, {k}) float64 tensor, got {what}")
+            raise ValueError(f"{who}.logpdf_device: expected an (n, {k}) float64 tensor, got {what}")
         if not x.is_cuda:
-            raise ValueError(f"GaussianPrior.logpdf_device: expected a tensor on the GPU, got one on {x.device}")
+            raise ValueError(f"{who}.logpdf_device: expected a tensor on the GPU, got one on {x.device}")
         d = self._device(x.device)
-        _on_device(x, d["device"], "GaussianPrior.logpdf_device")
+        _on_device(x, d["device"], f"{who}.logpdf_device")
         n = x.shape[0]
         out = torch.empty(n, dtype=torch.float64, device=x.device)
         if n == 0:
@@ -711,17 +719,23 @@ class GaussianPrior:
         else:
             x, strides = x.contiguous(), (k, 1)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().pmc_gauss_blocks_logpdf(C.byref(d["desc"]), C.c_void_p(x.data_ptr()), strides[0],
-                                                           strides[1], n, None, _lib.ptr(out), _lib.stream_handle()),
-                       "pmc_gauss_blocks_logpdf")
+            self._launch(d, C.c_void_p(x.data_ptr()), strides, n, _lib.ptr(out))
         return out
+
+    _logc_device = property(lambda self: self.logc)      # the constant the device subtracts
+
+    def _launch(self, d, x_ptr, strides, n, out_ptr):
+        import ctypes as C
+        from . import _lib
+        _lib.check(_lib.load().pmc_gauss_blocks_logpdf(C.byref(d["desc"]), x_ptr, strides[0], strides[1], n, None, out_ptr,
+                                                       _lib.stream_handle()), "pmc_gauss_blocks_logpdf")
 
     def logpdf(self, x):
         import torch
         from . import _lib
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"GaussianPrior.logpdf: expected shape (n, {self.dim}), got {x.shape}")
+            raise ValueError(f"{type(self).__name__}.logpdf: expected shape (n, {self.dim}), got {x.shape}")
         dev = self._dev["device"] if self._dev is not None else _lib.require_gpu()
         return self.logpdf_device(torch.from_numpy(x).to(dev)).cpu().numpy()
 
@@ -738,6 +752,218 @@ class GaussianPrior:
     @property
     def dim(self):
         return len(self.mean)
+
+
+MAX_CORRELATED_BOUNDS = 12        # bounded columns with a non-diagonal covariance whose box mass the constructor integrates
+MAX_LOG_MASS_SPREAD = 1e-3        # |log mass (seed 0) - log mass (seed 1)| the constructor accepts: 30 times below the +-0.03
+                                  # of a run's log-evidence
+MASS_SEEDS = (20240229, 20240301)  # the two integrations' generators (never numpy's global one)
+MASS_POINTS = 100_000             # lattice points per bounded column and seed, in MASS_SHIFTS randomly shifted copies
+MASS_SHIFTS = 8
+MASS_ABSEPS, MASS_RELEPS = 1e-9, 1e-7     # scipy's tolerances where scipy integrates (two bounded columns: its exact form)
+MAX_RVS_DRAWS = 1e8               # rvs refuses when size / mass, the draws it expects to make, exceeds this
+
+
+def _genz_box_mass(mean, cov, lo, hi, seed, points=None, shifts=None, chunk=1 << 16):
+    """The mass of the box ``[lo, hi]`` under ``N(mean, cov)`` by Genz's separation of variables (A. Genz, "Numerical
+    computation of multivariate normal probabilities", J. Comp. Graph. Stat. 1, 1992): the integral becomes one over the unit
+    cube of d - 1 dimensions, taken with ``shifts`` randomly shifted Richtmyer lattices (generators sqrt(prime), the tent
+    transform) of ``points / shifts`` points each; the narrowest columns are integrated first.  The shifts come from a
+    generator of their own, seeded with ``seed``: the same arguments give the same bits, and numpy's global generator is not
+    touched.  An interval beyond the mean is measured in the tail it lies in, so that its mass is a difference of small
+    numbers and not of numbers next to 1.  numpy and scipy.special only."""
+    from scipy.special import ndtr, ndtri
+    d = len(mean)
+    points = MASS_POINTS * d if points is None else int(points)
+    shifts = MASS_SHIFTS if shifts is None else int(shifts)
+    sd = np.sqrt(np.diag(cov))
+    a, b = lo - mean, hi - mean
+    order = np.argsort(ndtr(b / sd) - ndtr(a / sd), kind="stable")
+    a, b = a[order], b[order]
+    L = np.linalg.cholesky(cov[np.ix_(order, order)])
+    rng = np.random.Generator(np.random.PCG64(seed))
+    primes = [p for p in range(2, 64) if all(p % q for q in range(2, p))][:d - 1]
+    gen = np.sqrt(np.array(primes, dtype=np.float64))
+    n = -(-points // shifts)
+
+    def interval(ai, bi):
+        """(measured in the upper tail, the lower end's probability, the width) of [ai, bi] under the standard normal."""
+        flip = ai > 0
+        lo_, hi_ = np.where(flip, -bi, ai), np.where(flip, -ai, bi)
+        dd = ndtr(lo_)
+        return flip, dd, ndtr(hi_) - dd
+
+    total = 0.0
+    for _ in range(shifts):
+        shift = rng.random(d - 1)
+        acc = 0.0
+        for k0 in range(1, n + 1, chunk):
+            k = np.arange(k0, min(k0 + chunk, n + 1), dtype=np.float64)[:, None]
+            w = np.abs(2.0 * ((k * gen + shift) % 1.0) - 1.0)
+            y = np.empty((len(k), d - 1))
+            flip, dd, wd = interval(np.full(len(k), a[0] / L[0, 0]), np.full(len(k), b[0] / L[0, 0]))
+            f = wd.copy()
+            for i in range(1, d):
+                t = ndtri(np.clip(dd + w[:, i - 1] * wd, 1e-300, 1.0 - 2.0 ** -53))
+                y[:, i - 1] = np.where(flip, -t, t)
+                s = y[:, :i] @ L[i, :i]
+                flip, dd, wd = interval((a[i] - s) / L[i, i], (b[i] - s) / L[i, i])
+                f = f * wd
+            acc += float(f.sum())
+        total += acc / n
+    return total / shifts
+
+
+def _box_log_mass(mean, cov, bounds):
+    """``(log_mass, log_mass_spread)`` of the box ``bounds`` under ``N(mean, cov)``: see ``TruncatedGaussianPrior``."""
+    hint = "; log_mass= takes a value computed elsewhere"
+    S = np.flatnonzero(np.isfinite(bounds).any(axis=1))
+    if len(S) == 0:
+        return 0.0, 0.0
+    m, c, lo, hi = mean[S], cov[np.ix_(S, S)], bounds[S, 0], bounds[S, 1]           # the marginal on S: exact
+    if len(S) == 1 or not (c - np.diag(np.diag(c))).any():
+        sd = np.sqrt(np.diag(c))
+        log_mass, spread = float(sum(_log_gauss_mass((lo[j] - m[j]) / sd[j], (hi[j] - m[j]) / sd[j]) for j in range(len(S)))), 0.0
+    else:
+        if len(S) > MAX_CORRELATED_BOUNDS:
+            raise ValueError(f"TruncatedGaussianPrior: {len(S)} correlated bounded columns: the constructor integrates the box's "
+                             f"mass for at most MAX_CORRELATED_BOUNDS = {MAX_CORRELATED_BOUNDS}" + hint)
+        if len(S) == 2:
+            # scipy's routine takes two columns in closed form (no sampling: the same bits on every call)
+            from scipy.stats import multivariate_normal
+            masses = [float(multivariate_normal.cdf(hi, m, c, maxpts=1000000 * len(S), abseps=MASS_ABSEPS, releps=MASS_RELEPS,
+                                                    lower_limit=lo))] * 2
+        else:
+            masses = [_genz_box_mass(m, c, lo, hi, seed) for seed in MASS_SEEDS]
+        if not all(np.isfinite(v) and v > 0.0 for v in masses):
+            raise ValueError(f"TruncatedGaussianPrior: the box's mass under the normal is not positive and finite ({masses[0]!r}, "
+                             f"{masses[1]!r}): the box lies too far out in the tail for the integration" + hint)
+        log_mass = float(np.log(min(0.5 * (masses[0] + masses[1]), 1.0)))
+        spread = float(abs(np.log(masses[0]) - np.log(masses[1])))
+        if spread > MAX_LOG_MASS_SPREAD:
+            raise ValueError(f"TruncatedGaussianPrior: two integrations of the box's mass differ by {spread:.3g} in the log "
+                             f"(more than {MAX_LOG_MASS_SPREAD:g})" + hint)
+    if not (np.isfinite(log_mass) and log_mass <= 0.0):
+        raise ValueError(f"TruncatedGaussianPrior: the box's mass under the normal is not positive and finite (log mass "
+                         f"{log_mass!r})" + hint)
+    return log_mass, spread
+
+
+class TruncatedGaussianPrior(GaussianPrior):
+    """A correlated normal on a box: ``x ~ N(mean, cov)`` restricted to ``lo_j <= x_j <= hi_j`` and normalised,
+
+        ``log p(x) = -0.5 |Linv (x - mean)|^2 - logc - log_mass`` inside the closed box, ``-inf`` outside,
+
+    -- a published Gaussian constraint on parameters with hard limits (an amplitude above zero, a fraction in [0, 1]).
+
+    ``mean``, ``cov``  as for ``GaussianPrior`` (the same checks, the same texts, ``1 <= k <= 157``); ``mean`` need not lie in
+                       the box.
+    ``bounds``         ``(k, 2)`` floats, ``lo_j < hi_j``; -inf / +inf for a one-sided limit or an untouched column, no NaN.
+                       The value on a bound is finite and the first float beyond it is -inf (scipy's ``truncnorm``).
+    ``log_mass``       None: the constructor computes the log of the box's mass under the normal (numpy and scipy, no torch,
+                       no GPU).  With S the columns that have a finite limit, the marginal ``N(mean[S], cov[S, S])`` carries
+                       all of it: 0.0 for an empty S; the sum of scipy's ``truncnorm`` masses for one column or a diagonal
+                       ``cov[S, S]``; scipy's closed form for two correlated columns; otherwise two integrations by Genz's
+                       method with two fixed seeds (``MASS_SEEDS``, ``MASS_POINTS`` per column), ``log_mass`` the log of
+                       their mean and ``log_mass_spread`` the difference of their logs.  The same arguments give the same
+                       bits, and numpy's global generator is not touched.  ``ValueError`` -- each says that ``log_mass=``
+                       takes a value computed elsewhere -- for a spread above 1e-3, for a mass that is not positive and
+                       finite, and for more than ``MAX_CORRELATED_BOUNDS`` = 12 correlated bounded columns.
+                       A float: finite and <= 0, taken as given; ``log_mass_spread`` is then None.
+
+    ``logc_box = logc + log_mass`` (one float64 addition) is what the device subtracts; ``device_block()`` gives ``mean``,
+    ``linv_packed``, ``logc`` (= ``logc_box``), ``lo`` and ``hi``.  ``logpdf_device`` and ``logpdf`` follow ``GaussianPrior``'s
+    contract -- one launch, no host synchronisation, no copy for the two coalesced layouts, never NaN, never +inf -- through
+    ``pmc_gauss_box_logpdf``: the same kernel with the box test compiled in; a row inside has ``pmc_gauss_blocks_logpdf``'s bits
+    for ``logc_box``, and with all-infinite bounds ``GaussianPrior``'s.  ``rvs(size)`` is rejection from ``mean + z @ L.T``
+    (numpy's global generator, blocks of ``ceil(1.2 missing / mass) + 16`` rows, kept in draw order); ``RuntimeError`` before
+    anything is drawn when ``size / mass > 1e8``.  ``bounds`` is the box, ``dim`` k.  The state is ``GaussianPrior``'s plus
+    ``bounds``, ``log_mass`` and ``log_mass_spread``.  No ``device_descriptor``, no ``step_stage``; ``JointPrior`` takes it as a
+    Gaussian block.  Out of scope: boxes that are not axis-aligned, and singular covariances."""
+
+    def __init__(self, mean, cov, bounds, log_mass=None):
+        st = self._constants(mean, cov)
+        k = len(st["mean"])
+        try:
+            b = np.array(bounds, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"TruncatedGaussianPrior: bounds must be a ({k}, 2) array of floats") from None
+        if b.shape != (k, 2):
+            raise ValueError(f"TruncatedGaussianPrior: bounds must have shape ({k}, 2), got {b.shape}")
+        if np.isnan(b).any():
+            raise ValueError(f"TruncatedGaussianPrior: bounds of column {int(np.argwhere(np.isnan(b))[0][0])} hold a NaN")
+        if not (b[:, 0] < b[:, 1]).all():
+            j = int(np.argmin(b[:, 0] < b[:, 1]))
+            raise ValueError(f"TruncatedGaussianPrior: column {j}: lo = {float(b[j, 0])!r} is not below hi = {float(b[j, 1])!r}")
+        if log_mass is None:
+            log_mass, spread = _box_log_mass(st["mean"], st["cov"], b)
+        else:
+            try:
+                log_mass = float(log_mass)
+            except (TypeError, ValueError):
+                raise ValueError(f"TruncatedGaussianPrior: log_mass must be a finite float <= 0, got {log_mass!r}") from None
+            if not (np.isfinite(log_mass) and log_mass <= 0.0):
+                raise ValueError(f"TruncatedGaussianPrior: log_mass must be a finite float <= 0, got {log_mass!r}")
+            spread = None
+        self.__setstate__(dict(st, bounds=b, log_mass=log_mass, log_mass_spread=spread))
+
+    # ----------------------------------------------------------------- state
+    def __getstate__(self):
+        return dict(GaussianPrior.__getstate__(self), bounds=self._bounds.copy(), log_mass=self.log_mass,
+                    log_mass_spread=self.log_mass_spread)
+
+    def __setstate__(self, st):
+        GaussianPrior.__setstate__(self, st)
+        self._bounds = np.array(st["bounds"], dtype=np.float64)
+        self.log_mass = float(st["log_mass"])
+        self.log_mass_spread = None if st["log_mass_spread"] is None else float(st["log_mass_spread"])
+        self.logc_box = self.logc + self.log_mass
+
+    _logc_device = property(lambda self: self.logc_box)
+
+    def device_block(self):
+        """``GaussianPrior.device_block`` with ``logc`` = ``logc_box`` and the box: ``lo``, ``hi`` (k,)."""
+        return dict(mean=self.mean.copy(), linv_packed=self.linv_packed.copy(), logc=np.array(self.logc_box, dtype=np.float64),
+                    lo=self._bounds[:, 0].copy(), hi=self._bounds[:, 1].copy())
+
+    def _device(self, device):
+        if self._dev is None:
+            import torch
+            from . import _lib
+            d = GaussianPrior._device(self, device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d["device"])
+            d["lo"], d["hi"] = up(self._bounds[:, 0]), up(self._bounds[:, 1])
+            box = _lib.pmc_gauss_box_t()
+            box.lo[0], box.hi[0] = d["lo"].data_ptr(), d["hi"].data_ptr()
+            d["box"] = box
+        return self._dev
+
+    def _launch(self, d, x_ptr, strides, n, out_ptr):
+        import ctypes as C
+        from . import _lib
+        _lib.check(_lib.load().pmc_gauss_box_logpdf(C.byref(d["desc"]), C.byref(d["box"]), x_ptr, strides[0], strides[1], n,
+                                                    None, out_ptr, _lib.stream_handle()), "pmc_gauss_box_logpdf")
+
+    # ----------------------------------------------------------------- draws
+    def rvs(self, size=1):
+        size = int(size)
+        mass = float(np.exp(self.log_mass))
+        if size / mass > MAX_RVS_DRAWS:
+            raise RuntimeError(f"TruncatedGaussianPrior.rvs: {size} rows at a box mass of {mass:.3g} need about {size / mass:.3g} "
+                               f"draws of the untruncated normal (more than {MAX_RVS_DRAWS:g})")
+        lo, hi = self._bounds[:, 0], self._bounds[:, 1]
+        out, missing = [], size
+        while missing > 0:
+            m = int(np.ceil(1.2 * missing / mass)) + 16
+            x = GaussianPrior.rvs(self, m)
+            x = x[((x >= lo) & (x <= hi)).all(axis=1)][:missing]          # (in draw order)
+            out.append(x)
+            missing -= len(x)
+        return np.concatenate(out) if out else np.empty((0, self.dim))
+
+    @property
+    def bounds(self):
+        return self._bounds.copy()
 
 
 class JointPrior:
@@ -796,8 +1022,14 @@ class JointPrior:
     pass over ``x``).  ``rvs`` and ``bounds`` go by list order.  ``step_stage`` raises ``ValueError``: a prior with a Gaussian
     block is for ``logpdf`` and for ``device_prior=True``, not for the step of a host likelihood.
 
-    Out of scope: more than 8 blocks, non-diagonal scalers, the stage on sharded walkers, truncated or singular Gaussian
-    blocks, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
+    A ``TruncatedGaussianPrior`` is a Gaussian block as well (a block kind of its own in the state, ``"gauss_box"``): it is
+    listed in ``gaussian_priors``, added after the flow blocks and the table in list order, and refused by ``step_stage`` in
+    the same words.  As soon as one block has a box the Gaussian launch is ``pmc_gauss_box_logpdf`` (plain Gaussian blocks go
+    along without a box); without one it is ``pmc_gauss_blocks_logpdf`` as before.  The whole row is -inf as soon as any
+    block's box is violated, ``bounds`` reports the box on those columns and ``rvs`` stays inside it.
+
+    Out of scope: more than 8 blocks, non-diagonal scalers, the stage on sharded walkers, singular Gaussian blocks, boxes that
+    are not axis-aligned, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
 
     MAX_DIM = FlowPrior.MAX_DIM
     MAX_BLOCKS = 8           # PMC_JOINT_BLOCKS_MAX
@@ -933,9 +1165,10 @@ class JointPrior:
             if not isinstance(fp, (FlowPrior, GaussianPrior)):
                 raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior or GaussianPrior, got "
                                  f"{type(fp).__name__}")
-        kinds = ["flow" if isinstance(fp, FlowPrior) else "gauss" for fp in flow_priors]
+        kinds = ["flow" if isinstance(fp, FlowPrior) else "gauss_box" if isinstance(fp, TruncatedGaussianPrior) else "gauss"
+                 for fp in flow_priors]
         if not 1 <= B <= self.MAX_BLOCKS:
-            raise ValueError(f"JointPrior: {B} blocks ({kinds.count('flow')} flow blocks, {kinds.count('gauss')} Gaussian "
+            raise ValueError(f"JointPrior: {B} blocks ({kinds.count('flow')} flow blocks, {B - kinds.count('flow')} Gaussian "
                              f"blocks; 1 <= blocks <= {self.MAX_BLOCKS})")
         import torch
         # (a Gaussian block that has not been on a device yet goes where the others are)
@@ -961,7 +1194,8 @@ class JointPrior:
                              devs[known[0]] if known else None, kinds)
 
     def _restore_blocks(self, states, columns, rest, device=None, kinds=None):
-        """``states``, ``columns``, ``kinds`` (``"flow"`` / ``"gauss"``; None: every block a flow): the blocks in list order."""
+        """``states``, ``columns``, ``kinds`` (``"flow"`` / ``"gauss"`` / ``"gauss_box"``, a truncated Gaussian; None: every
+        block a flow): the blocks in list order."""
         import copy
         import ctypes as C
         import torch
@@ -974,11 +1208,12 @@ class JointPrior:
                 fp._restore(st["flow"], st["scaler"], device)
                 device = fp.flow.device                            # (an unpickled prior: every block where the first one went)
             else:
-                fp = GaussianPrior.__new__(GaussianPrior)
+                cls = TruncatedGaussianPrior if kind == "gauss_box" else GaussianPrior
+                fp = cls.__new__(cls)
                 fp.__setstate__(copy.deepcopy(st))
             parts.append(fp)
         fps = [p for k, p in zip(kinds, parts) if k == "flow"]
-        gps = [p for k, p in zip(kinds, parts) if k == "gauss"]
+        gps = [p for k, p in zip(kinds, parts) if k != "flow"]                # (both Gaussian kinds, in list order)
         self._kinds, self._parts = tuple(kinds), tuple(parts)
         self.flow_priors, self.gaussian_priors = tuple(fps), tuple(gps)
         self.blocks = len(parts)
@@ -990,7 +1225,7 @@ class JointPrior:
         self._device = dev
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         flow_cols = [c for k, c in zip(kinds, self._block_cols) if k == "flow"]
-        gauss_cols = [c for k, c in zip(kinds, self._block_cols) if k == "gauss"]
+        gauss_cols = [c for k, c in zip(kinds, self._block_cols) if k != "flow"]
         # (the descriptors point into these tensors: they live as long as the descriptors do)
         self._dev = dict(cols=[up(c) for c in flow_cols], gauss_cols=[up(c) for c in gauss_cols],
                          rest_cols=up(self._rest_cols) if Dr else None)
@@ -1013,17 +1248,25 @@ class JointPrior:
                 j.scaler[b] = C.cast(C.pointer(fp._sdesc), C.c_void_p)
                 j.cols[b] = self._dev["cols"][b].data_ptr()
             self._jdesc = j
-        self._gdesc = None
+        self._gdesc = self._gbox = None
         if gps:
             # (the table goes through this launch only where no flow launch has taken it)
             g = _lib.pmc_gauss_blocks_t(n_blocks=len(gps), D=self._dim, rest=None if fps else rest_ptr,
                                         rest_cols=None if fps else rest_cols_ptr)
             for b, gp in enumerate(gps):
                 d = gp._device(dev)
-                g.dim[b], g.logc[b] = gp.dim, gp.logc
+                g.dim[b], g.logc[b] = gp.dim, gp._logc_device
                 g.cols[b] = self._dev["gauss_cols"][b].data_ptr()
                 g.mean[b], g.linv[b] = d["mean"].data_ptr(), d["linv"].data_ptr()
             self._gdesc = g
+            if "gauss_box" in kinds:
+                # (one truncated block sends the launch through pmc_gauss_box_logpdf; a plain block is a NULL pair)
+                box = _lib.pmc_gauss_box_t()
+                for b, gp in enumerate(gps):
+                    if isinstance(gp, TruncatedGaussianPrior):
+                        d = gp._device(dev)
+                        box.lo[b], box.hi[b] = d["lo"].data_ptr(), d["hi"].data_ptr()
+                self._gbox = box
         self._offsets = np.concatenate([[0], np.cumsum([fp.dim for fp in fps])]).astype(np.int64)
         self._ws = {}
 
@@ -1170,10 +1413,16 @@ class JointPrior:
         else:
             x, strides = x.contiguous(), (D, 1)
         out = self._logpdf_device_blocks(x) if self.flow_priors else torch.empty(n, dtype=torch.float64, device=dev)
+        base = _lib.ptr(out) if self.flow_priors else None
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().pmc_gauss_blocks_logpdf(C.byref(self._gdesc), C.c_void_p(x.data_ptr()), strides[0],
-                                                           strides[1], n, _lib.ptr(out) if self.flow_priors else None,
-                                                           _lib.ptr(out), _lib.stream_handle()), "pmc_gauss_blocks_logpdf")
+            if self._gbox is not None:
+                _lib.check(_lib.load().pmc_gauss_box_logpdf(C.byref(self._gdesc), C.byref(self._gbox), C.c_void_p(x.data_ptr()),
+                                                            strides[0], strides[1], n, base, _lib.ptr(out),
+                                                            _lib.stream_handle()), "pmc_gauss_box_logpdf")
+            else:
+                _lib.check(_lib.load().pmc_gauss_blocks_logpdf(C.byref(self._gdesc), C.c_void_p(x.data_ptr()), strides[0],
+                                                               strides[1], n, base, _lib.ptr(out), _lib.stream_handle()),
+                           "pmc_gauss_blocks_logpdf")
         return out
 
     gaussian_priors = ()          # the owned copies of the Gaussian blocks, in list order (the blocks form)
