@@ -1271,6 +1271,62 @@ typedef struct pmc_gauss_box {            /* per block of the pmc_gauss_blocks_t
 int pmc_gauss_box_logpdf(const pmc_gauss_blocks_t* g, const pmc_gauss_box_t* box, const double* x, int64_t row_stride,
                          int64_t col_stride, int64_t n, const double* base, double* logp, void* stream);
 
+/* ----------------------------------------------------------------- a mixture of correlated normals */
+
+/* A mixture of C correlated normals on one block of dim columns of x (pocomc_amd.GaussianMixturePrior; the mixture blocks
+ * of pocomc_amd.JointPrior), on top of a value that is already there (base), of a table of scipy factors (rest) or of
+ * nothing:
+ *   log p(x) = start + log sum_c w_c N(x[cols]; mean_c, cov_c).
+ * ONE launch, float64, one pass over x.  Appended within ABI 9: a new entry and a new struct only.
+ *
+ * 1 <= n_comp <= 32 components (PMC_GAUSS_MIX_MAX_COMPONENTS) on the same 1 <= dim <= 64 columns (PMC_GAUSS_MIX_MAX_DIM);
+ * cols int32 [dim]; logw f64 [C], the logs of the normalised weights; mean f64 [C][dim]; linv f64 [C][dim (dim + 1) / 2], each
+ * component's inverse Cholesky factor packed by rows as in pmc_gauss_blocks_t; logc f64 [C] (its formula there); all device
+ * memory.  D: the columns of x.  rest / rest_cols: a table and its columns as in pmc_gauss_blocks_t, or both NULL.  The map
+ * is the caller's to check: distinct entries of [0, D); an entry outside [0, D) is not followed, every row of its launch
+ * block of 64 rows then gets -inf.
+ *
+ * The arithmetic of a row, every product and every sum rounded to float64 (no FMA):
+ *   g_c = pmc_gauss_blocks_logpdf's g for (mean_c, Linv_c, logc_c): d_j, y_i, q in i order, g = -0.5 q - logc_c
+ *   t_c = g_c + logw_c                          (-inf where g_c is NaN or -inf)
+ *   m   = max_c t_c
+ *   s   = ((0.0 + exp(t_0 - m)) + exp(t_1 - m)) + ...      in c order
+ *   v   = m + log(s);   logp[r] = start + v
+ * start = base[r] with base (f64 [n]; may be logp itself: in place), else lp = 0.0; lp += term_m, m = 0 .. rest->D - 1 with
+ * rest (the bits of pmc_prior_logpdf on the gathered rest columns), else nothing: logp[r] = v.  base and rest exclude each
+ * other.  The t_c are the bits of the numpy statement (tests/gauss_mix_model.py); exp and log are the device library's, so
+ * v lies within (C + 8) 2^-52 + 2^-52 |v| of that statement's.  With one component and logw_0 = 0.0 the value has
+ * pmc_gauss_blocks_logpdf's bits (exp(0) = 1, log(1) = 0).
+ * -inf where an x_j of a block or rest column is not finite, a rest term is NaN, every t_c is -inf (m = -inf: the
+ * differences are never formed) or the result is not finite: never NaN, never +inf.
+ * x: f64, element (r, j) at x[r * row_stride + j * col_stride], with the two coalesced layouts (D, 1) and (1, n); other
+ * strides are read correctly, slowly.  A row's bits depend on its values alone -- not on the layout, on n or on the row's
+ * place in the call.
+ * Refused before anything is launched or written, each with a text of its own: a NULL descriptor; a NULL array inside it;
+ * n_comp outside 1 .. 32; dim outside 1 .. 64; D > 157 ("n_dim too large"; a launch block keeps 64 rows of x, a work tile
+ * and every component's t in LDS: 64 * ((D | 1) + (dim | 1) + n_comp) * 8 + 256 bytes, 130304 at the three limits, under
+ * the 163840 of a workgroup); dim + rest->D > D; rest without rest_cols or the reverse; a rest without its arrays;
+ * rest->n_extended > 0 without rest->par; base and rest together; a NULL x or logp; a negative count or stride; more than
+ * 2^31 - 1 blocks of 64 rows.  n == 0 returns 0 and reads no array. */
+#define PMC_GAUSS_MIX_MAX_COMPONENTS 32
+#define PMC_GAUSS_MIX_MAX_DIM 64
+typedef struct pmc_gauss_mix {
+    int32_t n_comp;               /* 1 .. PMC_GAUSS_MIX_MAX_COMPONENTS */
+    int32_t dim;                  /* 1 .. PMC_GAUSS_MIX_MAX_DIM */
+    int32_t D;                    /* columns of x */
+    int32_t reserved;             /* 0 */
+    const int32_t* cols;          /* [dim] */
+    const double* logw;           /* [n_comp] */
+    const double* mean;           /* [n_comp][dim] */
+    const double* linv;           /* [n_comp][dim (dim + 1) / 2] */
+    const double* logc;           /* [n_comp] */
+    const pmc_prior_t* rest;      /* or NULL */
+    const int32_t* rest_cols;     /* or NULL (with rest) */
+} pmc_gauss_mix_t;
+
+int pmc_gauss_mix_logpdf(const pmc_gauss_mix_t* g, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
+                         const double* base, double* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

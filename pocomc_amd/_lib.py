@@ -169,6 +169,16 @@ class pmc_gauss_box_t(C.Structure):
     _fields_ = [("lo", c_p * PMC_GAUSS_BLOCKS_MAX), ("hi", c_p * PMC_GAUSS_BLOCKS_MAX)]
 
 
+PMC_GAUSS_MIX_MAX_COMPONENTS = 32
+PMC_GAUSS_MIX_MAX_DIM = 64
+
+
+class pmc_gauss_mix_t(C.Structure):
+    _fields_ = [("n_comp", C.c_int32), ("dim", C.c_int32), ("D", C.c_int32), ("reserved", C.c_int32),
+                ("cols", c_p), ("logw", c_p), ("mean", c_p), ("linv", c_p), ("logc", c_p),
+                ("rest", c_p), ("rest_cols", c_p)]
+
+
 # name -> (restype, argtypes); every symbol include/pocomc_amd.h declares
 i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
 P = C.POINTER
@@ -289,6 +299,7 @@ SIGNATURES = {
     "pmc_joint_blocks_post": (C.c_int, [i32, c_p, c_p, c_p, c_p, c_p, i64, c_p]),
     "pmc_gauss_blocks_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
     "pmc_gauss_box_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), P(pmc_gauss_box_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
+    "pmc_gauss_mix_logpdf": (C.c_int, [P(pmc_gauss_mix_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
 }
 
 _lib = None

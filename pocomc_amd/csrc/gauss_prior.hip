@@ -6,14 +6,10 @@
 // contracted into an FMA: a row's bits are those of the numpy model.
 // With a box (TruncatedGaussianPrior, pmc_gauss_box_logpdf) a block's columns are also held to lo_j <= x_j <= hi_j: a row
 // outside gets -inf, every other row keeps its bits (the caller has put the box's log mass into logc).
-#include "pmc_internal.h"
-#include "flow_prior_body.h"
+#include "gauss_body.h"
 #include "prior_body.h"
 
 #pragma clang fp contract(off)
-
-#define GP_WAVES (FP_THREADS / FP_ROWS)            // 8: a wavefront's lane is a row of the tile, its number picks i
-#define GP_ACC 4                                   // rows of Linv a lane carries through one walk over d
 
 // What the kernel takes of the host's pmc_gauss_blocks_t: everything by value.
 struct GaussBlocksArgs {
@@ -38,14 +34,8 @@ static inline size_t gauss_blocks_lds_bytes(int D) {
     return (size_t)FP_ROWS * (D | 1) * sizeof(double) + FP_ROWS * sizeof(int);
 }
 
-// The blocks' constants live in the constant address space for the kernel: nobody writes them during the launch, and a load
-// at an address the wavefront shares is then a scalar load (through the scalar cache, into SGPRs) where a generic pointer
-// makes it a vector load of 64 equal addresses.
-typedef const double __attribute__((address_space(4))) * gp_f64;
-typedef const int32_t __attribute__((address_space(4))) * gp_i32;
-
-// Block bb's constants, picked in a chain of selects over constant indices (the kernel arguments are never indexed with
-// a run-time value); bb is the same in every lane, so these stay scalars.
+// Block bb's constants (read through the constant address space, gauss_body.h), picked in a chain of selects over constant
+// indices (the kernel arguments are never indexed with a run-time value); bb is the same in every lane, so these stay scalars.
 struct GaussBlock {
     gp_i32 cols;
     gp_f64 mean;
@@ -81,12 +71,6 @@ __device__ __forceinline__ GaussBlock gauss_block(const GaussBlocksArgs& a, int 
         }
     }
     return g;
-}
-
-// a column of the caller's map, never followed outside the tile
-__device__ __forceinline__ int gauss_col(gp_i32 cols, int j, int D) {
-    const int c = cols[j];
-    return (unsigned)c < (unsigned)D ? c : 0;
 }
 
 // joint_prior_pre_kernel's tile and stride contract (64 rows of all D columns through LDS, row length D | 1, the same two
@@ -125,23 +109,7 @@ __global__ __launch_bounds__(FP_THREADS) void gauss_blocks_kernel(GaussBlocksArg
     const int64_t row0 = (int64_t)blockIdx.x * FP_ROWS;
     const int rows = (int)min((int64_t)FP_ROWS, n - row0);
     if (tid < FP_ROWS) rowin[tid] = 1;
-    if (col_stride == 1) {
-        int rr = tid / D, cc = tid - rr * D;                              // element e = rr * D + cc, stepped without a division
-        const int dr = FP_THREADS / D, dc = FP_THREADS - dr * D;
-        for (int e = tid; e < rows * D; e += FP_THREADS) {
-            T[rr * LD + cc] = x[(row0 + rr) * row_stride + cc];
-            rr += dr; cc += dc;
-            if (cc >= D) { cc -= D; ++rr; }
-        }
-    } else {
-        int cc = tid / rows, rr = tid - cc * rows;                        // element e = cc * rows + rr
-        const int dc = FP_THREADS / rows, dr = FP_THREADS - dc * rows;
-        for (int e = tid; e < rows * D; e += FP_THREADS) {
-            T[rr * LD + cc] = x[(row0 + rr) * row_stride + (int64_t)cc * col_stride];
-            cc += dc; rr += dr;
-            if (rr >= rows) { rr -= rows; ++cc; }
-        }
-    }
+    gauss_load_tile(T, x, row_stride, col_stride, row0, rows, D, LD, tid);
     __syncthreads();
     double* Tr = T + r * LD;
     const bool live = r < rows;

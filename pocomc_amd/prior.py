@@ -24,6 +24,9 @@ a ``JointPrior`` next to flow blocks and a table.
 ``TruncatedGaussianPrior`` is that normal restricted to a box and normalised: the box's mass is one number, computed once on
 the host, and the same launch tests the box (``pmc_gauss_box_logpdf``); alone or as a block of a ``JointPrior``.
 
+``GaussianMixturePrior`` is a weighted sum of up to 32 such normals on up to 64 columns, closed by a log-sum-exp: one float64
+launch (``csrc/gauss_mix_prior.hip``), alone or as a block of a ``JointPrior``; ``from_samples`` fits it by EM in numpy.
+
 Next to a HOST likelihood ``FlowPrior`` and ``JointPrior`` (without Gaussian blocks) can be evaluated by the MCMC step
 itself (``step_stage``, kernel option ``step_prior``): the same
 three launches on the step's stream, on the device's copy of x', while the host evaluates the likelihood."""
@@ -966,6 +969,266 @@ class TruncatedGaussianPrior(GaussianPrior):
         return self._bounds.copy()
 
 
+class GaussianMixturePrior:
+    """A mixture of correlated normals, ``p(x) = sum_c w_c N(x; mean_c, cov_c)``, with ``1 <= C <= 32`` components
+    (``MAX_COMPONENTS``) on the same ``1 <= k <= 64`` columns (``MAX_DIM``): the earlier result that is not Gaussian and not
+    worth a flow -- a bimodal or banana-shaped posterior on a few shared parameters, a published "sum of N Gaussians", two
+    competing predictions.  Exactly normalised, exactly sampled, float64 throughout.  The two limits (and ``D <= 157`` in a
+    ``JointPrior``) are what the kernel's LDS plan holds (``csrc/gauss_mix_prior.hip``); wider mixtures are out of scope.
+
+    ``weights``  ``(C,)`` finite and strictly positive; the constructor divides by their sum and keeps
+                 ``logw = log(weights / weights.sum())`` (exactly 0.0 for C = 1).
+    ``means``    ``(C, k)``;  ``covs``  ``(C, k, k)``.  Every ``(means[c], covs[c])`` passes ``GaussianPrior``'s checks (finite,
+                 exactly symmetric, positive definite); each ``ValueError`` is prefixed ``GaussianMixturePrior: component c: ``.
+    The constructor is numpy and scipy alone; ``device_block()`` gives ``logw`` (C,), ``mean`` (C, k), ``linv_packed``
+    (C, k (k + 1) / 2) in ``GaussianPrior``'s packing and ``logc`` (C,).  The state carries the inputs and these constants; the
+    device's copies are made at the first device call and dropped on pickling.
+
+    ``logpdf_device(x)``  the ``DevicePrior`` contract, as ``GaussianPrior.logpdf_device``: an ``(n, k)`` float64 tensor on the
+                          device in, an ``(n,)`` float64 tensor out, on the current stream, in ONE launch
+                          (``pmc_gauss_mix_logpdf``) and no host synchronisation; no copy of ``x`` when it is C-contiguous or
+                          the MCMC step's column-major view (any other layout is made contiguous once); ``n == 0`` gives an
+                          empty tensor.  The value is ``m + log(sum_c exp(t_c - m))``, ``t_c = g_c + logw_c`` with
+                          ``GaussianPrior``'s ``g_c`` bit for bit and ``m = max_c t_c``, in the order ``include/pocomc_amd.h``
+                          fixes (``tests/gauss_mix_model.py``).  -inf for a row with a NaN or an inf and for a row every
+                          component gives -inf; never NaN, never +inf.  With one component: ``GaussianPrior``'s bits.
+    ``logpdf(x)``         numpy in, numpy out, through the same function.
+    ``rvs(size)``         two draws from numpy's GLOBAL generator (``Sampler(random_state=...)`` reaches it), in this order:
+                          first the ``size`` component indices by the weights (``choice``), then ONE standard-normal
+                          ``(size, k)`` block; row r is ``mean_c + z_r @ L_c.T`` for its component c.
+    ``bounds``, ``dim``   ``(k, 2)`` of -inf / +inf, and k.
+
+    ``from_samples(x, weights, n_components)`` fits the mixture to weighted samples by EM, ``from_sampler(s, columns=...)`` to
+    a finished run's posterior.  There is no ``device_descriptor`` and no ``step_stage``: the step calls the function
+    (``Sampler(device_likelihood=True, device_prior=True)``).  ``JointPrior`` takes it as a block.  Out of scope: more than 32
+    components or 64 columns, a box around the mixture (``TruncatedGaussianPrior`` has one component), choosing C."""
+
+    MAX_COMPONENTS = 32      # PMC_GAUSS_MIX_MAX_COMPONENTS
+    MAX_DIM = 64             # PMC_GAUSS_MIX_MAX_DIM
+
+    def __init__(self, weights, means, covs):
+        self.__setstate__(self._constants(weights, means, covs))
+
+    @classmethod
+    def _constants(cls, weights, means, covs):
+        """The checks and the host-side constants: the state of a ``GaussianMixturePrior(weights, means, covs)``."""
+        who = "GaussianMixturePrior"
+        arrays = []
+        for name, a, what in (("weights", weights, "(C,)"), ("means", means, "(C, k)"), ("covs", covs, "(C, k, k)")):
+            try:
+                arrays.append(np.array(a, dtype=np.float64))
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: {name} must be a {what} array of floats") from None
+        w, m, c = arrays
+        if w.ndim != 1 or len(w) < 1:
+            raise ValueError(f"{who}: weights must have shape (C,) with C >= 1, got {w.shape}")
+        C = len(w)
+        if C > cls.MAX_COMPONENTS:
+            raise ValueError(f"{who}: {C} components (1 <= C <= {cls.MAX_COMPONENTS})")
+        if m.ndim != 2 or m.shape[0] != C or m.shape[1] < 1:
+            raise ValueError(f"{who}: means must have shape ({C}, k) with k >= 1, got {m.shape}")
+        k = m.shape[1]
+        if k > cls.MAX_DIM:
+            raise ValueError(f"{who}: means have {k} dimensions (1 <= k <= {cls.MAX_DIM})")
+        if c.shape != (C, k, k):
+            raise ValueError(f"{who}: covs must have shape ({C}, {k}, {k}), got {c.shape}")
+        if not (np.isfinite(w) & (w > 0)).all():
+            j = int(np.argmin(np.isfinite(w) & (w > 0)))
+            raise ValueError(f"{who}: weights[{j}] = {float(w[j])!r} is not finite and strictly positive")
+        parts = []
+        for j in range(C):
+            try:
+                parts.append(GaussianPrior._constants(m[j], c[j]))
+            except ValueError as e:
+                text = str(e)
+                text = text[len("GaussianPrior: "):] if text.startswith("GaussianPrior: ") else text
+                raise ValueError(f"{who}: component {j}: {text}") from None
+        with np.errstate(all="ignore"):
+            logw = np.log(w / w.sum())
+        if not np.isfinite(logw).all():
+            raise ValueError(f"{who}: weights[{int(np.argmin(np.isfinite(logw)))}] vanishes next to the weights' sum")
+        return dict(weights=w, means=m, covs=c, logw=logw, L=np.stack([p["L"] for p in parts]),
+                    linv_packed=np.stack([p["linv_packed"] for p in parts]), logc=np.array([p["logc"] for p in parts]),
+                    fit_info=None)
+
+    # ----------------------------------------------------------------- fits
+    @classmethod
+    def from_samples(cls, x, weights=None, n_components=2, seed=0, max_iter=500, tol=1e-8, cov_floor=1e-6):
+        """The mixture fitted to weighted samples by EM, numpy and scipy alone.  ``x`` ``(n, k)`` finite rows, ``weights``
+        ``(n,)`` finite, not negative, not all zero (None: uniform; normalised here), ``n_components`` = C.
+
+        Seeding is k-means++ on the weighted rows (the first centre drawn by the weights, every next one by weight times
+        squared distance to the nearest centre) from ``np.random.Generator(np.random.PCG64(seed))``: numpy's global generator
+        is never touched and the same arguments give the same bits.  Start: ``w_c = 1 / C``, every ``cov_c`` the weighted
+        sample covariance ``S0``.  Every M-step adds ``cov_floor * trace(S0) / k * I`` to every covariance and symmetrises it,
+        ``0.5 (S + S.T)``.  The fit stops when the weighted mean log-density improves by less than ``tol``, or after
+        ``max_iter`` E-steps.  ``ValueError`` when a component's responsibility mass falls below ``k + 1`` rows of the Kish
+        effective sample size ``1 / sum(w^2)`` (a collapsed component: use fewer components), and for a covariance that is
+        not positive definite.  ``prior.fit_info``: ``iterations`` (E-steps), ``converged`` and ``loglik``, the weighted mean
+        log-density at every E-step (the last one is the returned mixture's).  Out of scope: choosing C, diagonal or tied
+        covariances, bounded parameters."""
+        from scipy.linalg import solve_triangular
+        from scipy.special import logsumexp
+        who = "GaussianMixturePrior.from_samples"
+        try:
+            x = np.array(x, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: x must be an (n, k) array of floats") from None
+        if x.ndim != 2 or x.shape[0] < 2 or x.shape[1] < 1:
+            raise ValueError(f"{who}: x must have shape (n, k) with n >= 2 and k >= 1, got {x.shape}")
+        n, k = x.shape
+        if k > cls.MAX_DIM:
+            raise ValueError(f"{who}: x has {k} columns (1 <= k <= {cls.MAX_DIM})")
+        if not np.isfinite(x).all():
+            r, j = np.argwhere(~np.isfinite(x))[0]
+            raise ValueError(f"{who}: x[{r}, {j}] is not finite")
+        if weights is None:
+            w = np.full(n, 1.0 / n)
+        else:
+            w = np.array(weights, dtype=np.float64)
+            if w.shape != (n,):
+                raise ValueError(f"{who}: weights must have shape ({n},), got {w.shape}")
+            if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+                raise ValueError(f"{who}: weights must be finite, not negative and not all zero")
+            w = w / w.sum()
+        C = int(n_components)
+        if C != n_components or not 1 <= C <= cls.MAX_COMPONENTS:
+            raise ValueError(f"{who}: n_components = {n_components!r} (1 <= C <= {cls.MAX_COMPONENTS})")
+        max_iter = int(max_iter)
+        if max_iter < 1:
+            raise ValueError(f"{who}: max_iter must be at least 1, got {max_iter}")
+        rng = np.random.Generator(np.random.PCG64(seed))
+        n_eff = 1.0 / np.sum(w * w)                                       # Kish
+        xc = x - w @ x
+        S0 = (w * xc.T) @ xc
+        S0 = 0.5 * (S0 + S0.T)
+        floor = cov_floor * np.trace(S0) / k * np.eye(k)
+        # k-means++ on the weighted rows
+        centres = [x[rng.choice(n, p=w)]]
+        d2 = np.sum((x - centres[0]) ** 2, axis=1)
+        for c in range(1, C):
+            p = w * d2
+            if not p.sum() > 0:
+                raise ValueError(f"{who}: the rows with weight hold fewer than {C} distinct points; use fewer components")
+            centres.append(x[rng.choice(n, p=p / p.sum())])
+            d2 = np.minimum(d2, np.sum((x - centres[-1]) ** 2, axis=1))
+        pi, means, covs = np.full(C, 1.0 / C), np.array(centres), np.stack([S0] * C)
+        loglik, converged = [], False
+        for it in range(max_iter):
+            lr = np.empty((C, n))
+            for c in range(C):
+                try:
+                    L = np.linalg.cholesky(covs[c])
+                except np.linalg.LinAlgError:
+                    raise ValueError(f"{who}: component {c}: its covariance is not positive definite at E-step {it}; use "
+                                     "fewer components or a larger cov_floor") from None
+                y = solve_triangular(L, (x - means[c]).T, lower=True)
+                lr[c] = (np.log(pi[c]) - 0.5 * np.sum(y * y, axis=0)) - (np.sum(np.log(np.diag(L))) + 0.5 * k * np.log(2 * np.pi))
+            lse = logsumexp(lr, axis=0)
+            loglik.append(float(w @ lse))
+            if it > 0 and loglik[-1] - loglik[-2] < tol:
+                converged = True
+                break
+            if it == max_iter - 1:
+                break                                                     # (the parameters stay those of the last E-step)
+            resp = w * np.exp(lr - lse)                                   # (C, n): weight times responsibility
+            mass = resp.sum(axis=1)
+            for c in range(C):
+                if mass[c] * n_eff < k + 1:
+                    raise ValueError(f"{who}: component {c} has collapsed: its responsibility mass is {mass[c] * n_eff:.3g} "
+                                     f"of {n_eff:.3g} effective rows (below k + 1 = {k + 1}); use fewer components")
+                means[c] = (resp[c] @ x) / mass[c]
+                xm = x - means[c]
+                S = (resp[c] * xm.T) @ xm / mass[c] + floor
+                covs[c] = 0.5 * (S + S.T)
+            pi = mass / mass.sum()
+        prior = cls(pi, means, covs)
+        prior.fit_info = dict(iterations=len(loglik), converged=converged, loglik=np.array(loglik))
+        return prior
+
+    @classmethod
+    def from_sampler(cls, sampler, columns=None, n_components=2, **fit):
+        """The mixture fitted to a finished ``Sampler`` run's weighted posterior samples (``sampler.posterior()``), on
+        ``columns`` of its parameters in that order (None: all of them), taken as ``FlowPrior.from_sampler(columns=...)``
+        takes them; ``fit``: ``from_samples``'s other arguments.  ``ValueError`` unless the sampler has run to beta = 1."""
+        FlowPrior._finished(sampler)
+        ndim = sampler.scaler.ndim
+        if columns is None:
+            cols = np.arange(ndim)
+        else:
+            k = len(columns) if hasattr(columns, "__len__") else 1
+            cols, _ = JointPrior.layout(columns, k, ndim - k)            # (checks them: distinct integers in [0, ndim))
+        samples, weights = sampler.posterior()[:2]
+        return cls.from_samples(np.asarray(samples)[:, cols], weights, n_components=n_components, **fit)
+
+    # ----------------------------------------------------------------- state
+    def __getstate__(self):
+        fit = None if self.fit_info is None else dict(self.fit_info, loglik=np.array(self.fit_info["loglik"]))
+        return dict(weights=self.weights.copy(), means=self.means.copy(), covs=self.covs.copy(), logw=self.logw.copy(),
+                    L=self.L.copy(), linv_packed=self.linv_packed.copy(), logc=self.logc.copy(), fit_info=fit)
+
+    def __setstate__(self, st):
+        for key in ("weights", "means", "covs", "logw", "L", "linv_packed", "logc"):
+            setattr(self, key, np.array(st[key], dtype=np.float64))
+        self.fit_info = st.get("fit_info")
+        self._dev = None
+
+    def device_block(self):
+        """The device's constants as numpy arrays: ``logw`` (C,), ``mean`` (C, k), ``linv_packed`` (C, k (k + 1) / 2): row i of
+        component c's inverse Cholesky factor at ``[c, i (i + 1) / 2]``, and ``logc`` (C,).  No torch, no GPU."""
+        return dict(logw=self.logw.copy(), mean=self.means.copy(), linv_packed=self.linv_packed.copy(), logc=self.logc.copy())
+
+    def _device(self, device):
+        """The device's copies and the descriptor of the mixture alone, made once, on ``device``."""
+        if self._dev is None:
+            import torch
+            k = self.dim
+            dev = torch.device(device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d = dict(device=dev, logw=up(self.logw), mean=up(self.means), linv=up(self.linv_packed), logc=up(self.logc),
+                     cols=up(np.arange(k, dtype=np.int32)))
+            d["desc"] = self._descriptor(d, d["cols"], k)           # (it points into the tensors next to it)
+            self._dev = d
+        return self._dev
+
+    def _descriptor(self, d, cols, D, rest=None, rest_cols=None):
+        """``pmc_gauss_mix_t`` of this mixture on the columns ``cols`` (a device tensor) of a ``D``-column x."""
+        from . import _lib
+        return _lib.pmc_gauss_mix_t(n_comp=self.components, dim=self.dim, D=D, reserved=0, cols=cols.data_ptr(),
+                                    logw=d["logw"].data_ptr(), mean=d["mean"].data_ptr(), linv=d["linv"].data_ptr(),
+                                    logc=d["logc"].data_ptr(), rest=rest, rest_cols=rest_cols)
+
+    # ----------------------------------------------------------------- density
+    logpdf_device = GaussianPrior.logpdf_device      # the same checks and layouts around _device and _launch
+    logpdf = GaussianPrior.logpdf
+
+    def _launch(self, d, x_ptr, strides, n, out_ptr):
+        import ctypes as C
+        from . import _lib
+        _lib.check(_lib.load().pmc_gauss_mix_logpdf(C.byref(d["desc"]), x_ptr, strides[0], strides[1], n, None, out_ptr,
+                                                    _lib.stream_handle()), "pmc_gauss_mix_logpdf")
+
+    # ----------------------------------------------------------------- draws
+    def rvs(self, size=1):
+        size = int(size)
+        glob = np.random.mtrand._rand                                     # (numpy's global generator, named: JointPrior.rvs)
+        comp = glob.choice(self.components, size=size, p=np.exp(self.logw))      # first the components ...
+        z = glob.standard_normal((size, self.dim))                               # ... then one block of normals
+        return self.means[comp] + np.einsum("rj,rij->ri", z, self.L[comp])
+
+    @property
+    def components(self):
+        return len(self.logw)
+
+    @property
+    def bounds(self):
+        return np.stack([np.full(self.dim, -np.inf), np.full(self.dim, np.inf)], axis=1)
+
+    @property
+    def dim(self):
+        return self.means.shape[1]
+
+
 class JointPrior:
     """A flow prior on some of the parameters and scipy factors on the others:
 
@@ -1028,7 +1291,19 @@ class JointPrior:
     along without a box); without one it is ``pmc_gauss_blocks_logpdf`` as before.  The whole row is -inf as soon as any
     block's box is violated, ``bounds`` reports the box on those columns and ``rvs`` stays inside it.
 
-    Out of scope: more than 8 blocks, non-diagonal scalers, the stage on sharded walkers, singular Gaussian blocks, boxes that
+    Mixture blocks: the list takes a ``GaussianMixturePrior`` wherever it takes a ``FlowPrior`` or a ``GaussianPrior`` (block
+    kind ``"gmix"`` in the state; states without the kind still load), at most 8 blocks of all kinds, distinct columns, 157
+    dimensions.  ``mixture_priors`` are the owned copies in list order, copied through their state.  The value is that of the
+    same prior without its mixture blocks -- flow blocks in list order, the table, Gaussian blocks in list order -- THEN
+    ``+ v`` for every mixture block in list order, ``v`` the block's own ``logpdf_device`` on its gathered columns: bit for bit
+    that left-to-right float64 sum, -inf outside any part's support, never NaN.  Each mixture block is one
+    ``pmc_gauss_mix_logpdf`` launch that adds in place behind the launches that exist; where no flow block and no Gaussian
+    block precedes, the first mixture launch evaluates the table as well (one pass over ``x`` for that launch).  ``rvs`` and
+    ``bounds`` go by list order; ``step_stage`` raises ``ValueError`` as for a Gaussian block.  A prior without a mixture block
+    takes the path and the launches it took before.
+
+    Out of scope: more than 8 blocks, a box around a mixture, mixture blocks folded into the Gaussian launch, non-diagonal
+    scalers, the stage on sharded walkers, singular Gaussian blocks, boxes that
     are not axis-aligned, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
 
     MAX_DIM = FlowPrior.MAX_DIM
@@ -1145,8 +1420,8 @@ class JointPrior:
         if self.blocks:
             st = {"flow_priors": [p.__getstate__() for p in self._parts],
                   "columns": [c.tolist() for c in self._block_cols], "rest": self.rest}
-            if self.gaussian_priors:
-                st["kinds"] = list(self._kinds)               # (the blocks in list order: a flow's state or a Gaussian's)
+            if self.gaussian_priors or self.mixture_priors:
+                st["kinds"] = list(self._kinds)               # (the blocks in list order: a flow's state, a Gaussian's, a mixture's)
             return st
         return {"flow_prior": self.flow_prior.__getstate__(), "columns": self._flow_cols.tolist(), "rest": self.rest}
 
@@ -1162,14 +1437,15 @@ class JointPrior:
     def _init_blocks(self, flow_priors, columns, rest):
         B = len(flow_priors)
         for b, fp in enumerate(flow_priors):
-            if not isinstance(fp, (FlowPrior, GaussianPrior)):
-                raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior or GaussianPrior, got "
-                                 f"{type(fp).__name__}")
-        kinds = ["flow" if isinstance(fp, FlowPrior) else "gauss_box" if isinstance(fp, TruncatedGaussianPrior) else "gauss"
-                 for fp in flow_priors]
+            if not isinstance(fp, (FlowPrior, GaussianPrior, GaussianMixturePrior)):
+                raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior or GaussianPrior or "
+                                 f"GaussianMixturePrior, got {type(fp).__name__}")
+        kinds = ["flow" if isinstance(fp, FlowPrior) else "gmix" if isinstance(fp, GaussianMixturePrior) else
+                 "gauss_box" if isinstance(fp, TruncatedGaussianPrior) else "gauss" for fp in flow_priors]
         if not 1 <= B <= self.MAX_BLOCKS:
-            raise ValueError(f"JointPrior: {B} blocks ({kinds.count('flow')} flow blocks, {B - kinds.count('flow')} Gaussian "
-                             f"blocks; 1 <= blocks <= {self.MAX_BLOCKS})")
+            n_flow, n_mix = kinds.count("flow"), kinds.count("gmix")
+            raise ValueError(f"JointPrior: {B} blocks ({n_flow} flow blocks, {B - n_flow - n_mix} Gaussian blocks"
+                             + (f", {n_mix} mixture blocks" if n_mix else "") + f"; 1 <= blocks <= {self.MAX_BLOCKS})")
         import torch
         # (a Gaussian block that has not been on a device yet goes where the others are)
         devs = [torch.device(fp.flow.device) if k == "flow" else None if fp._dev is None else fp._dev["device"]
@@ -1194,8 +1470,8 @@ class JointPrior:
                              devs[known[0]] if known else None, kinds)
 
     def _restore_blocks(self, states, columns, rest, device=None, kinds=None):
-        """``states``, ``columns``, ``kinds`` (``"flow"`` / ``"gauss"`` / ``"gauss_box"``, a truncated Gaussian; None: every
-        block a flow): the blocks in list order."""
+        """``states``, ``columns``, ``kinds`` (``"flow"`` / ``"gauss"`` / ``"gauss_box"``, a truncated Gaussian / ``"gmix"``, a
+        mixture; None: every block a flow): the blocks in list order."""
         import copy
         import ctypes as C
         import torch
@@ -1208,14 +1484,15 @@ class JointPrior:
                 fp._restore(st["flow"], st["scaler"], device)
                 device = fp.flow.device                            # (an unpickled prior: every block where the first one went)
             else:
-                cls = TruncatedGaussianPrior if kind == "gauss_box" else GaussianPrior
+                cls = {"gauss": GaussianPrior, "gauss_box": TruncatedGaussianPrior, "gmix": GaussianMixturePrior}[kind]
                 fp = cls.__new__(cls)
                 fp.__setstate__(copy.deepcopy(st))
             parts.append(fp)
         fps = [p for k, p in zip(kinds, parts) if k == "flow"]
-        gps = [p for k, p in zip(kinds, parts) if k != "flow"]                # (both Gaussian kinds, in list order)
+        gps = [p for k, p in zip(kinds, parts) if k in ("gauss", "gauss_box")]      # (both Gaussian kinds, in list order)
+        mps = [p for k, p in zip(kinds, parts) if k == "gmix"]
         self._kinds, self._parts = tuple(kinds), tuple(parts)
-        self.flow_priors, self.gaussian_priors = tuple(fps), tuple(gps)
+        self.flow_priors, self.gaussian_priors, self.mixture_priors = tuple(fps), tuple(gps), tuple(mps)
         self.blocks = len(parts)
         self.rest = copy.deepcopy(rest)
         Dr = 0 if self.rest is None else self.rest.dim
@@ -1225,10 +1502,11 @@ class JointPrior:
         self._device = dev
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         flow_cols = [c for k, c in zip(kinds, self._block_cols) if k == "flow"]
-        gauss_cols = [c for k, c in zip(kinds, self._block_cols) if k != "flow"]
+        gauss_cols = [c for k, c in zip(kinds, self._block_cols) if k in ("gauss", "gauss_box")]
+        mix_cols = [c for k, c in zip(kinds, self._block_cols) if k == "gmix"]
         # (the descriptors point into these tensors: they live as long as the descriptors do)
         self._dev = dict(cols=[up(c) for c in flow_cols], gauss_cols=[up(c) for c in gauss_cols],
-                         rest_cols=up(self._rest_cols) if Dr else None)
+                         mix_cols=[up(c) for c in mix_cols], rest_cols=up(self._rest_cols) if Dr else None)
         self._rdesc = None
         if Dr:
             tab = self.rest.device_table()
@@ -1242,8 +1520,10 @@ class JointPrior:
         rest_cols_ptr = self._dev["rest_cols"].data_ptr() if Dr else None
         self._jdesc = None
         if fps:
-            # (D: x has the Gaussian blocks' columns as well; 0 where the flow blocks and the table cover every column)
-            j = _lib.pmc_joint_blocks_t(n_blocks=len(fps), D=self._dim if gps else 0, rest=rest_ptr, rest_cols=rest_cols_ptr)
+            # (D: x has the Gaussian and mixture blocks' columns as well; 0 where the flow blocks and the table cover every
+            # column)
+            j = _lib.pmc_joint_blocks_t(n_blocks=len(fps), D=self._dim if gps or mps else 0, rest=rest_ptr,
+                                        rest_cols=rest_cols_ptr)
             for b, fp in enumerate(fps):
                 j.scaler[b] = C.cast(C.pointer(fp._sdesc), C.c_void_p)
                 j.cols[b] = self._dev["cols"][b].data_ptr()
@@ -1267,6 +1547,13 @@ class JointPrior:
                         d = gp._device(dev)
                         box.lo[b], box.hi[b] = d["lo"].data_ptr(), d["hi"].data_ptr()
                 self._gbox = box
+        # one descriptor per mixture block, in list order; the table goes through the first one only where neither a flow
+        # launch nor the Gaussian launch has taken it
+        self._mdescs = []
+        for b, mp in enumerate(mps):
+            first = b == 0 and not fps and not gps
+            self._mdescs.append(mp._descriptor(mp._device(dev), self._dev["mix_cols"][b], self._dim,
+                                               rest_ptr if first else None, rest_cols_ptr if first else None))
         self._offsets = np.concatenate([[0], np.cumsum([fp.dim for fp in fps])]).astype(np.int64)
         self._ws = {}
 
@@ -1425,9 +1712,51 @@ class JointPrior:
                            "pmc_gauss_blocks_logpdf")
         return out
 
+    def _logpdf_device_mix(self, x):
+        """The blocks form with mixture blocks: the launches of the same prior without them (``_logpdf_device_gauss`` or
+        ``_logpdf_device_blocks``), then one ``pmc_gauss_mix_logpdf`` launch per mixture block in list order, each adding its
+        block in place; where nothing precedes, the first launch starts the value, with the table in it."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        D, dev = self.dim, self._device
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"JointPrior.logpdf_device: expected an (n, {D}) float64 tensor, got {what}")
+        _on_device(x, dev, "JointPrior.logpdf_device")
+        n = x.shape[0]
+        if n == 0:
+            return torch.empty(0, dtype=torch.float64, device=dev)
+        # the two layouts the kernels read with coalesced loads; everything else is copied once, for all of them
+        if x.is_contiguous():
+            strides = (D, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (D, 1)
+        if self.gaussian_priors:
+            out = self._logpdf_device_gauss(x)
+        elif self.flow_priors:
+            out = self._logpdf_device_blocks(x)
+        else:
+            out = None
+        base = None if out is None else _lib.ptr(out)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            for desc in self._mdescs:
+                _lib.check(_lib.load().pmc_gauss_mix_logpdf(C.byref(desc), C.c_void_p(x.data_ptr()), strides[0], strides[1], n,
+                                                            base, _lib.ptr(out), _lib.stream_handle()), "pmc_gauss_mix_logpdf")
+                base = _lib.ptr(out)
+        return out
+
     gaussian_priors = ()          # the owned copies of the Gaussian blocks, in list order (the blocks form)
+    mixture_priors = ()           # the owned copies of the mixture blocks, in list order (the blocks form)
 
     def logpdf_device(self, x):
+        if self.mixture_priors:
+            return self._logpdf_device_mix(x)
         if self.gaussian_priors:
             return self._logpdf_device_gauss(x)
         if self.blocks:
@@ -1475,6 +1804,9 @@ class JointPrior:
 
     def step_stage(self, n, device=None):
         """``FlowPrior.step_stage`` for the joint prior: the descriptor carries the column maps and the table as well."""
+        if self.mixture_priors:
+            raise ValueError("JointPrior.step_stage: a prior with a mixture block is not evaluated inside the step of a host "
+                             "likelihood (step_prior); use logpdf, or device_prior=True with a device likelihood")
         if self.gaussian_priors:
             raise ValueError("JointPrior.step_stage: a prior with a Gaussian block is not evaluated inside the step of a host "
                              "likelihood (step_prior); use logpdf, or device_prior=True with a device likelihood")
