@@ -1327,6 +1327,68 @@ typedef struct pmc_gauss_mix {
 int pmc_gauss_mix_logpdf(const pmc_gauss_mix_t* g, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
                          const double* base, double* logp, void* stream);
 
+/* ----------------------------------------------------------------- a weighted Gaussian KDE of samples */
+
+/* A kernel density estimate of M weighted samples with one shared bandwidth matrix H on one block of dim columns of x
+ * (pocomc_amd.KDEPrior; the KDE blocks of pocomc_amd.JointPrior), on top of a value that is already there (base), of a
+ * table of scipy factors (rest) or of nothing:
+ *   log p(x) = start + log sum_m w_m N(x[cols]; s_m, H).
+ * ONE launch, float64, one pass over x.  Appended within ABI 9: a new entry and a new struct only.
+ *
+ * 1 <= n_samples <= 65536 samples (PMC_KDE_MAX_SAMPLES) on 1 <= dim <= 16 columns (PMC_KDE_MAX_DIM); cols int32 [dim];
+ * center f64 [dim], the weighted mean of the samples; linv f64 [dim (dim + 1) / 2], the inverse of H's lower Cholesky factor
+ * packed by rows as in pmc_gauss_blocks_t; t f64 [n_samples][dim], the whitened samples t_m = Linv (s_m - center); logw f64
+ * [n_samples], the logs of the normalised weights; all device memory.  logc = dim / 2 log(2 pi) + 1/2 log|H|, by value.
+ * D: the columns of x.  rest / rest_cols: a table and its columns as in pmc_gauss_blocks_t, or both NULL.  The map is the
+ * caller's to check: distinct entries of [0, D); an entry outside [0, D) is not followed, every row of its launch block of
+ * 64 rows then gets -inf.
+ *
+ * The statement of a row (tests/kde_model.py), every product and every sum rounded to float64 (no FMA):
+ *   d_j = x[cols[j]] - center_j
+ *   y_i = (((0.0 + Linv[i,0] d_0) + Linv[i,1] d_1) + ...) + Linv[i,i] d_i          (pmc_gauss_blocks_logpdf's y)
+ *   q_m = ((0.0 + (y_0 - t_m0)^2) + (y_1 - t_m1)^2) + ...                         in j order
+ *   e_m = -0.5 q_m + logw_m
+ *   mx  = max_m e_m                              (-inf: the row is -inf)
+ *   s   = sum_m exp(e_m - mx)
+ *   v   = (mx + log(s)) - logc;   logp[r] = start + v
+ * start = base[r] with base (f64 [n]; may be logp itself: in place), else lp = 0.0; lp += term_m, m = 0 .. rest->D - 1 with
+ * rest (the bits of pmc_prior_logpdf on the gathered rest columns), else nothing: logp[r] = v.  base and rest exclude each
+ * other.  The y_i and every e_m have the statement's bits.  The kernel cuts the samples in eight contiguous slices of
+ * ceil(M / 8) -- a cut that depends on M alone -- adds each slice's exps in m order and the eight partial sums in slice
+ * order; exp and log are the device library's.  v lies within (M + 8) 2^-52 + 2^-50 (|v| + |logc|) of the statement
+ * evaluated with a sequential sum.  With one sample and logw_0 = 0.0 the value has pmc_gauss_blocks_logpdf's bits for
+ * (mean = s_0, H): t_0 = 0, exp(0) = 1, log(1) = 0.
+ * -inf where an x_j of a block or rest column is not finite, a rest term is NaN, every e_m is -inf or NaN (mx = -inf) or
+ * the result is not finite: never NaN, never +inf.
+ * x: f64, element (r, j) at x[r * row_stride + j * col_stride], with the two coalesced layouts (D, 1) and (1, n); other
+ * strides are read correctly, slowly.  A row's bits depend on its values and the descriptor alone -- not on the layout, on
+ * n or on the row's place in the call.
+ * Refused before anything is launched or written, each with a text of its own: a NULL descriptor; a NULL array inside it;
+ * n_samples outside 1 .. 65536; dim outside 1 .. 16; D > 157 ("n_dim too large"; a launch block keeps 64 rows of x and the
+ * eight wavefronts' partial maxima and sums in LDS: 64 * ((D | 1) + 16) * 8 + 256 bytes, 88832 at D = 157); dim + rest->D
+ * > D; rest without rest_cols or the reverse; a rest without its arrays; rest->n_extended > 0 without rest->par; base and
+ * rest together; a NULL x or logp; a negative count or stride; more than 2^31 - 1 blocks of 64 rows.  n == 0 returns 0 and
+ * reads no array. */
+#define PMC_KDE_MAX_DIM 16
+#define PMC_KDE_MAX_SAMPLES 65536
+typedef struct pmc_kde {
+    int32_t n_samples;            /* 1 .. PMC_KDE_MAX_SAMPLES */
+    int32_t dim;                  /* 1 .. PMC_KDE_MAX_DIM */
+    int32_t D;                    /* columns of x */
+    int32_t reserved;             /* 0 */
+    const int32_t* cols;          /* [dim] */
+    const double* center;         /* [dim] */
+    const double* linv;           /* [dim (dim + 1) / 2] */
+    const double* t;              /* [n_samples][dim] */
+    const double* logw;           /* [n_samples] */
+    double logc;
+    const pmc_prior_t* rest;      /* or NULL */
+    const int32_t* rest_cols;     /* or NULL (with rest) */
+} pmc_kde_t;
+
+int pmc_kde_logpdf(const pmc_kde_t* g, const double* x, int64_t row_stride, int64_t col_stride, int64_t n,
+                   const double* base, double* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ gfx950 kernels behind the C ABI of ``include/pocomc_amd.h``.
 """
 from .maf_spec import MAFSpec  # noqa: F401
 
-__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "GaussianPrior", "TruncatedGaussianPrior", "GaussianMixturePrior", "JointPrior", "mcmc", "tools"]
+__all__ = ["Flow", "MAFSpec", "Reparameterize", "Sampler", "Prior", "DevicePrior", "FlowPrior", "GaussianPrior", "TruncatedGaussianPrior", "GaussianMixturePrior", "KDEPrior", "JointPrior", "mcmc", "tools"]
 
 
 def __getattr__(name):
@@ -41,6 +41,9 @@ def __getattr__(name):
     if name == "GaussianMixturePrior":
         from .prior import GaussianMixturePrior
         return GaussianMixturePrior
+    if name == "KDEPrior":
+        from .prior import KDEPrior
+        return KDEPrior
     if name == "JointPrior":
         from .prior import JointPrior
         return JointPrior

@@ -179,6 +179,16 @@ class pmc_gauss_mix_t(C.Structure):
                 ("rest", c_p), ("rest_cols", c_p)]
 
 
+PMC_KDE_MAX_DIM = 16
+PMC_KDE_MAX_SAMPLES = 65536
+
+
+class pmc_kde_t(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("dim", C.c_int32), ("D", C.c_int32), ("reserved", C.c_int32),
+                ("cols", c_p), ("center", c_p), ("linv", c_p), ("t", c_p), ("logw", c_p), ("logc", C.c_double),
+                ("rest", c_p), ("rest_cols", c_p)]
+
+
 # name -> (restype, argtypes); every symbol include/pocomc_amd.h declares
 i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
 P = C.POINTER
@@ -300,6 +310,7 @@ SIGNATURES = {
     "pmc_gauss_blocks_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
     "pmc_gauss_box_logpdf": (C.c_int, [P(pmc_gauss_blocks_t), P(pmc_gauss_box_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
     "pmc_gauss_mix_logpdf": (C.c_int, [P(pmc_gauss_mix_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
+    "pmc_kde_logpdf": (C.c_int, [P(pmc_kde_t), c_p, i64, i64, i64, c_p, c_p, c_p]),
 }
 
 _lib = None

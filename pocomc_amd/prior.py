@@ -27,6 +27,10 @@ the host, and the same launch tests the box (``pmc_gauss_box_logpdf``); alone or
 ``GaussianMixturePrior`` is a weighted sum of up to 32 such normals on up to 64 columns, closed by a log-sum-exp: one float64
 launch (``csrc/gauss_mix_prior.hip``), alone or as a block of a ``JointPrior``; ``from_samples`` fits it by EM in numpy.
 
+``KDEPrior`` is a weighted Gaussian kernel density estimate of up to 65536 samples on up to 16 columns with one shared
+bandwidth matrix: a row is whitened once and the kernels are an n x M streaming log-sum-exp, one float64 launch
+(``csrc/kde_prior.hip``), alone or as a block of a ``JointPrior``; nothing is fitted.
+
 Next to a HOST likelihood ``FlowPrior`` and ``JointPrior`` (without Gaussian blocks) can be evaluated by the MCMC step
 itself (``step_stage``, kernel option ``step_prior``): the same
 three launches on the step's stream, on the device's copy of x', while the host evaluates the likelihood."""
@@ -1229,6 +1233,253 @@ class GaussianMixturePrior:
         return self.means.shape[1]
 
 
+class KDEPrior:
+    """A weighted Gaussian kernel density estimate of samples, ``p(x) = sum_m w_m N(x; s_m, H)`` with ONE shared bandwidth
+    matrix ``H``: the earlier result that arrives as a chain -- a published MCMC chain, another run's weighted posterior on a
+    few shared parameters -- when nothing is to be fitted to it.  No fit, no random number, exactly normalised, exactly
+    sampled, float64 throughout.  ``1 <= M <= 65536`` samples (``MAX_SAMPLES``) on ``1 <= k <= 16`` columns (``MAX_DIM``).
+
+    The estimate has NO support restriction: around samples of a bounded parameter it puts mass outside the bounds (about
+    half a kernel's for a sample on a bound).  Bounded parameters leak mass; a box around the estimate is out of scope.
+
+    ``samples``    ``(M, k)`` floats;  ``weights``  ``(M,)`` finite, not negative, not all zero (None: equal).  Rows of weight
+                   zero are dropped before anything else (their values are not looked at); what remains must be finite.
+                   More than 65536 rows: thin the chain; more than 16 columns: choose fewer.
+    ``bandwidth``  ``"scott"``, ``"silverman"``, a positive float ``f``, or a ``(k, k)`` symmetric positive definite matrix
+                   taken as ``H`` itself.  For the first three ``H = f^2 C`` with ``C`` the weighted sample covariance as
+                   ``scipy.stats.gaussian_kde`` forms it (divided by ``1 - sum w^2``, ``w`` the normalised weights),
+                   ``neff = 1 / sum w^2``, Scott's ``f = neff^(-1 / (k + 4))`` and Silverman's
+                   ``f = (neff (k + 2) / 4)^(-1 / (k + 4))``.  A ``C`` that is not positive definite (too few distinct rows)
+                   is refused: a matrix ``bandwidth=`` takes an ``H`` from elsewhere.
+    The constructor is numpy and scipy alone.  ``center`` is the weighted mean of the samples; ``linv_packed`` and
+    ``logc = k / 2 log(2 pi) + 1/2 log|H|`` are ``GaussianPrior._constants(center, H)``'s (its checks and texts apply, behind
+    ``KDEPrior: ``); ``t = (samples - center) @ Linv.T`` are the whitened samples and ``logw = log(w / sum w)`` (exactly 0.0
+    for M = 1); ``device_block()`` gives them.  The state carries the inputs kept (the samples and weights after the drop,
+    ``H``) and these constants; the device's copies are made at the first device call and dropped on pickling.
+
+    ``logpdf_device(x)``  the ``DevicePrior`` contract, as ``GaussianPrior.logpdf_device``: an ``(n, k)`` float64 tensor on the
+                          device in, an ``(n,)`` float64 tensor out, on the current stream, in ONE launch
+                          (``pmc_kde_logpdf``, ``csrc/kde_prior.hip``) and no host synchronisation; no copy of ``x`` when it
+                          is C-contiguous or the MCMC step's column-major view (any other layout is made contiguous once);
+                          ``n == 0`` gives an empty tensor.  A row is whitened once, ``y = Linv (x - center)``, and the value
+                          is ``(mx + log sum_m exp(e_m - mx)) - logc`` with ``e_m = -0.5 |y - t_m|^2 + logw_m`` and
+                          ``mx = max_m e_m`` (``include/pocomc_amd.h``, ``tests/kde_model.py``): within
+                          ``(M + 8) 2^-52 + 2^-50 (|v| + |logc|)`` of that statement.  -inf for a row with a NaN or an inf
+                          and for a row every kernel gives -inf; never NaN, never +inf.  With one sample:
+                          ``GaussianPrior(samples[0], H)``'s bits.
+    ``logpdf(x)``         numpy in, numpy out, through the same function.
+    ``rvs(size)``         two draws from numpy's GLOBAL generator (``Sampler(random_state=...)`` reaches it), in this order:
+                          first the ``size`` sample indices by the weights (``choice``), then ONE standard-normal
+                          ``(size, k)`` block; row r is ``samples[m_r] + z_r @ L.T``.
+    ``bounds``, ``dim``   ``(k, 2)`` of -inf / +inf, and k.
+
+    ``from_samples(x, weights, columns=...)`` selects columns first; ``from_sampler(s, columns=...)`` takes a finished run's
+    weighted posterior.  There is no ``device_descriptor`` and no ``step_stage``: the step calls the function
+    (``Sampler(device_likelihood=True, device_prior=True)``).  ``JointPrior`` takes it as a block.  Out of scope: a box or any
+    other support restriction, per-sample bandwidths, thinning, more than 16 columns or 65536 samples."""
+
+    MAX_DIM = 16             # PMC_KDE_MAX_DIM
+    MAX_SAMPLES = 65536      # PMC_KDE_MAX_SAMPLES
+
+    def __init__(self, samples, weights=None, bandwidth="scott"):
+        self.__setstate__(self._constants(samples, weights, bandwidth))
+
+    @classmethod
+    def _constants(cls, samples, weights, bandwidth):
+        """The checks and the host-side constants: the state of a ``KDEPrior(samples, weights, bandwidth)``."""
+        who = "KDEPrior"
+        try:
+            s = np.array(samples, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: samples must be an (M, k) array of floats") from None
+        if s.ndim != 2 or s.shape[0] < 1 or s.shape[1] < 1:
+            raise ValueError(f"{who}: samples must have shape (M, k) with M >= 1 and k >= 1, got {s.shape}")
+        k = s.shape[1]
+        if k > cls.MAX_DIM:
+            raise ValueError(f"{who}: samples have {k} columns (1 <= k <= {cls.MAX_DIM}): choose fewer columns "
+                             "(from_samples(..., columns=...)); the other parameters take other priors in a JointPrior")
+        if weights is None:
+            w = np.ones(len(s), dtype=np.float64)
+        else:
+            try:
+                w = np.array(weights, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: weights must be an (M,) array of floats") from None
+            if w.shape != (len(s),):
+                raise ValueError(f"{who}: weights must have shape ({len(s)},), got {w.shape}")
+            if not (np.isfinite(w) & (w >= 0)).all():
+                j = int(np.argmin(np.isfinite(w) & (w >= 0)))
+                raise ValueError(f"{who}: weights[{j}] = {float(w[j])!r} is not finite and non-negative")
+            if not (w > 0).any():
+                raise ValueError(f"{who}: every weight is zero")
+            s, w = s[w > 0], w[w > 0]                                        # (before anything else)
+        M = len(s)
+        if M > cls.MAX_SAMPLES:
+            raise ValueError(f"{who}: {M} samples of weight above zero (1 <= M <= {cls.MAX_SAMPLES}): thin the chain "
+                             "(every j-th row, or a resample by the weights)")
+        if not np.isfinite(s).all():
+            i, j = np.argwhere(~np.isfinite(s))[0]
+            raise ValueError(f"{who}: samples[{i}, {j}] is not finite (row {i} of the rows of weight above zero)")
+        with np.errstate(all="ignore"):
+            wn = w / w.sum()
+            logw = np.log(wn)
+        if not np.isfinite(logw).all():
+            raise ValueError(f"{who}: a weight vanishes next to the weights' sum (or the sum overflows): rescale the weights")
+        center = (wn[:, None] * s).sum(axis=0)
+        xm = s - center
+        factor = None
+        matrix = not isinstance(bandwidth, str) and np.ndim(bandwidth) == 2
+        if matrix:
+            try:
+                H = np.array(bandwidth, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: a matrix bandwidth must be a ({k}, {k}) array of floats") from None
+            if H.shape != (k, k):
+                raise ValueError(f"{who}: a matrix bandwidth must have shape ({k}, {k}), got {H.shape}")
+        else:
+            neff = 1.0 / float(np.sum(wn ** 2))
+            if isinstance(bandwidth, str):
+                if bandwidth == "scott":
+                    factor = float(np.power(neff, -1.0 / (k + 4)))
+                elif bandwidth == "silverman":
+                    factor = float(np.power(neff * (k + 2.0) / 4.0, -1.0 / (k + 4)))
+                else:
+                    raise ValueError(f"{who}: bandwidth must be 'scott', 'silverman', a positive float or a ({k}, {k}) matrix, "
+                                     f"got {bandwidth!r}")
+            else:
+                try:
+                    factor = float(bandwidth)
+                except (TypeError, ValueError):
+                    raise ValueError(f"{who}: bandwidth must be 'scott', 'silverman', a positive float or a ({k}, {k}) "
+                                     f"matrix, got {bandwidth!r}") from None
+                if not (np.isfinite(factor) and factor > 0):
+                    raise ValueError(f"{who}: the bandwidth factor must be finite and positive, got {factor!r}")
+            # scipy.stats.gaussian_kde's covariance: np.cov(samples.T, aweights=wn), that is divided by 1 - sum wn^2
+            with np.errstate(all="ignore"):
+                Cw = (xm.T * wn) @ xm / (1.0 - float(np.sum(wn ** 2)))
+            Cw = 0.5 * (Cw + Cw.T)
+            # (k or fewer distinct rows span no k-dimensional volume, whatever rounding leaves on the diagonal)
+            ok = bool(np.isfinite(Cw).all()) and len(np.unique(s, axis=0)) > k
+            if ok:
+                try:
+                    np.linalg.cholesky(Cw)
+                except np.linalg.LinAlgError:
+                    ok = False
+            if not ok:
+                raise ValueError(f"{who}: the weighted covariance of the {M} samples is not positive definite (too few "
+                                 "distinct rows): a matrix bandwidth=H takes an H from elsewhere")
+            H = factor ** 2 * Cw
+        try:
+            g = GaussianPrior._constants(center, H)
+        except ValueError as e:
+            text = str(e)
+            text = text[len("GaussianPrior: "):] if text.startswith("GaussianPrior: ") else text
+            raise ValueError(f"{who}: {text} (mean: the samples' weighted mean, cov: the bandwidth matrix H)") from None
+        k_idx = np.tril_indices(k)
+        Linv = np.zeros((k, k), dtype=np.float64)
+        Linv[k_idx] = g["linv_packed"]
+        with np.errstate(all="ignore"):
+            t = np.ascontiguousarray(xm @ Linv.T)
+        if not np.isfinite(t).all():
+            raise ValueError(f"{who}: the samples are too far apart for the bandwidth: a whitened sample is not finite")
+        return dict(samples=s, weights=w, H=g["cov"], factor=factor, center=g["mean"], L=g["L"],
+                    linv_packed=g["linv_packed"], logc=g["logc"], t=t, logw=logw)
+
+    # ----------------------------------------------------------------- other sources
+    @classmethod
+    def from_samples(cls, x, weights=None, columns=None, bandwidth="scott"):
+        """The estimate of the ``columns`` of ``x`` ``(n, d)`` in that order (None: all of them; distinct integers in
+        ``[0, d)``), with the constructor's ``weights`` and ``bandwidth``."""
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise ValueError(f"KDEPrior.from_samples: x must have shape (n, d), got {x.shape}")
+        if columns is not None:
+            k = len(columns) if hasattr(columns, "__len__") else 1
+            cols, _ = JointPrior.layout(columns, k, x.shape[1] - k)          # (checks them: distinct integers in [0, d))
+            x = x[:, cols]
+        return cls(x, weights, bandwidth)
+
+    @classmethod
+    def from_sampler(cls, sampler, columns=None, bandwidth="scott"):
+        """The estimate of a finished ``Sampler`` run's weighted posterior samples (``sampler.posterior()``), on ``columns``
+        of its parameters in that order (None: all of them), taken as ``FlowPrior.from_sampler(columns=...)`` takes them.
+        ``ValueError`` unless the sampler has run to beta = 1."""
+        FlowPrior._finished(sampler)
+        samples, weights = sampler.posterior()[:2]
+        return cls.from_samples(np.asarray(samples), weights, columns=columns, bandwidth=bandwidth)
+
+    # ----------------------------------------------------------------- state
+    _ARRAYS = ("samples", "weights", "H", "center", "L", "linv_packed", "t", "logw")
+
+    def __getstate__(self):
+        st = {key: getattr(self, key).copy() for key in self._ARRAYS}
+        st.update(logc=self.logc, factor=self.factor)
+        return st
+
+    def __setstate__(self, st):
+        for key in self._ARRAYS:
+            setattr(self, key, np.array(st[key], dtype=np.float64))
+        self.logc = float(st["logc"])
+        self.factor = None if st.get("factor") is None else float(st["factor"])      # (None: H was given as a matrix)
+        self._dev = None
+
+    def device_block(self):
+        """The device's constants as numpy arrays: ``center`` (k,), ``linv_packed`` (k (k + 1) / 2,) in ``GaussianPrior``'s
+        packing, ``t`` (M, k) the whitened samples, ``logw`` (M,) and ``logc`` (a 0-d array).  No torch, no GPU."""
+        return dict(center=self.center.copy(), linv_packed=self.linv_packed.copy(), t=self.t.copy(), logw=self.logw.copy(),
+                    logc=np.array(self.logc, dtype=np.float64))
+
+    def _device(self, device):
+        """The device's copies and the descriptor of the estimate alone, made once, on ``device``."""
+        if self._dev is None:
+            import torch
+            k = self.dim
+            dev = torch.device(device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d = dict(device=dev, center=up(self.center), linv=up(self.linv_packed), t=up(self.t), logw=up(self.logw),
+                     cols=up(np.arange(k, dtype=np.int32)))
+            d["desc"] = self._descriptor(d, d["cols"], k)           # (it points into the tensors next to it)
+            self._dev = d
+        return self._dev
+
+    def _descriptor(self, d, cols, D, rest=None, rest_cols=None):
+        """``pmc_kde_t`` of this estimate on the columns ``cols`` (a device tensor) of a ``D``-column x."""
+        from . import _lib
+        return _lib.pmc_kde_t(n_samples=self.n_samples, dim=self.dim, D=D, reserved=0, cols=cols.data_ptr(),
+                              center=d["center"].data_ptr(), linv=d["linv"].data_ptr(), t=d["t"].data_ptr(),
+                              logw=d["logw"].data_ptr(), logc=self.logc, rest=rest, rest_cols=rest_cols)
+
+    # ----------------------------------------------------------------- density
+    logpdf_device = GaussianPrior.logpdf_device      # the same checks and layouts around _device and _launch
+    logpdf = GaussianPrior.logpdf
+
+    def _launch(self, d, x_ptr, strides, n, out_ptr):
+        import ctypes as C
+        from . import _lib
+        _lib.check(_lib.load().pmc_kde_logpdf(C.byref(d["desc"]), x_ptr, strides[0], strides[1], n, None, out_ptr,
+                                              _lib.stream_handle()), "pmc_kde_logpdf")
+
+    # ----------------------------------------------------------------- draws
+    def rvs(self, size=1):
+        size = int(size)
+        glob = np.random.mtrand._rand                                     # (numpy's global generator, named: JointPrior.rvs)
+        idx = glob.choice(self.n_samples, size=size, p=self.weights / self.weights.sum())     # first the samples ...
+        z = glob.standard_normal((size, self.dim))                                            # ... then one block of normals
+        return self.samples[idx] + z @ self.L.T
+
+    @property
+    def n_samples(self):
+        return len(self.logw)
+
+    @property
+    def bounds(self):
+        return np.stack([np.full(self.dim, -np.inf), np.full(self.dim, np.inf)], axis=1)
+
+    @property
+    def dim(self):
+        return self.samples.shape[1]
+
+
 class JointPrior:
     """A flow prior on some of the parameters and scipy factors on the others:
 
@@ -1302,7 +1553,16 @@ class JointPrior:
     ``bounds`` go by list order; ``step_stage`` raises ``ValueError`` as for a Gaussian block.  A prior without a mixture block
     takes the path and the launches it took before.
 
-    Out of scope: more than 8 blocks, a box around a mixture, mixture blocks folded into the Gaussian launch, non-diagonal
+    KDE blocks: the list takes a ``KDEPrior`` wherever it takes a ``GaussianMixturePrior`` (block kind ``"kde"`` in the state;
+    states without the kind still load), with the same limits: at most 8 blocks of all kinds, distinct columns, 157
+    dimensions, one device.  ``kde_priors`` are the owned copies in list order, copied through their state.  The value is that
+    of the same prior without its KDE blocks -- flow blocks, the table, Gaussian blocks, mixture blocks, in the order above
+    -- THEN ``+ v`` for every KDE block in list order, ``v`` the block's own ``logpdf_device`` on its gathered columns: bit
+    for bit that left-to-right float64 sum.  Each KDE block is one ``pmc_kde_logpdf`` launch that adds in place behind the
+    launches that exist; where nothing precedes, the first KDE launch evaluates the table as well.  ``step_stage`` raises
+    ``ValueError``.  A prior without a KDE block takes the path and the launches it took before.
+
+    Out of scope: more than 8 blocks, a box around a mixture or a KDE, mixture blocks folded into the Gaussian launch, non-diagonal
     scalers, the stage on sharded walkers, singular Gaussian blocks, boxes that
     are not axis-aligned, and -- as for every ``DevicePrior`` -- lanes and graph capture."""
 
@@ -1420,8 +1680,9 @@ class JointPrior:
         if self.blocks:
             st = {"flow_priors": [p.__getstate__() for p in self._parts],
                   "columns": [c.tolist() for c in self._block_cols], "rest": self.rest}
-            if self.gaussian_priors or self.mixture_priors:
-                st["kinds"] = list(self._kinds)               # (the blocks in list order: a flow's state, a Gaussian's, a mixture's)
+            if self.gaussian_priors or self.mixture_priors or self.kde_priors:
+                # (the blocks in list order: a flow's state, a Gaussian's, a mixture's, a KDE's)
+                st["kinds"] = list(self._kinds)
             return st
         return {"flow_prior": self.flow_prior.__getstate__(), "columns": self._flow_cols.tolist(), "rest": self.rest}
 
@@ -1437,15 +1698,17 @@ class JointPrior:
     def _init_blocks(self, flow_priors, columns, rest):
         B = len(flow_priors)
         for b, fp in enumerate(flow_priors):
-            if not isinstance(fp, (FlowPrior, GaussianPrior, GaussianMixturePrior)):
+            if not isinstance(fp, (FlowPrior, GaussianPrior, GaussianMixturePrior, KDEPrior)):
                 raise ValueError(f"JointPrior: block {b} must be a pocomc_amd.FlowPrior or GaussianPrior or "
-                                 f"GaussianMixturePrior, got {type(fp).__name__}")
+                                 f"GaussianMixturePrior, got {type(fp).__name__} (a KDEPrior is taken as well)")
         kinds = ["flow" if isinstance(fp, FlowPrior) else "gmix" if isinstance(fp, GaussianMixturePrior) else
+                 "kde" if isinstance(fp, KDEPrior) else
                  "gauss_box" if isinstance(fp, TruncatedGaussianPrior) else "gauss" for fp in flow_priors]
         if not 1 <= B <= self.MAX_BLOCKS:
-            n_flow, n_mix = kinds.count("flow"), kinds.count("gmix")
-            raise ValueError(f"JointPrior: {B} blocks ({n_flow} flow blocks, {B - n_flow - n_mix} Gaussian blocks"
-                             + (f", {n_mix} mixture blocks" if n_mix else "") + f"; 1 <= blocks <= {self.MAX_BLOCKS})")
+            n_flow, n_mix, n_kde = kinds.count("flow"), kinds.count("gmix"), kinds.count("kde")
+            raise ValueError(f"JointPrior: {B} blocks ({n_flow} flow blocks, {B - n_flow - n_mix - n_kde} Gaussian blocks"
+                             + (f", {n_mix} mixture blocks" if n_mix else "") + (f", {n_kde} KDE blocks" if n_kde else "")
+                             + f"; 1 <= blocks <= {self.MAX_BLOCKS})")
         import torch
         # (a Gaussian block that has not been on a device yet goes where the others are)
         devs = [torch.device(fp.flow.device) if k == "flow" else None if fp._dev is None else fp._dev["device"]
@@ -1471,7 +1734,7 @@ class JointPrior:
 
     def _restore_blocks(self, states, columns, rest, device=None, kinds=None):
         """``states``, ``columns``, ``kinds`` (``"flow"`` / ``"gauss"`` / ``"gauss_box"``, a truncated Gaussian / ``"gmix"``, a
-        mixture; None: every block a flow): the blocks in list order."""
+        mixture / ``"kde"``, a kernel density estimate; None: every block a flow): the blocks in list order."""
         import copy
         import ctypes as C
         import torch
@@ -1484,15 +1747,18 @@ class JointPrior:
                 fp._restore(st["flow"], st["scaler"], device)
                 device = fp.flow.device                            # (an unpickled prior: every block where the first one went)
             else:
-                cls = {"gauss": GaussianPrior, "gauss_box": TruncatedGaussianPrior, "gmix": GaussianMixturePrior}[kind]
+                cls = {"gauss": GaussianPrior, "gauss_box": TruncatedGaussianPrior, "gmix": GaussianMixturePrior,
+                       "kde": KDEPrior}[kind]
                 fp = cls.__new__(cls)
                 fp.__setstate__(copy.deepcopy(st))
             parts.append(fp)
         fps = [p for k, p in zip(kinds, parts) if k == "flow"]
         gps = [p for k, p in zip(kinds, parts) if k in ("gauss", "gauss_box")]      # (both Gaussian kinds, in list order)
         mps = [p for k, p in zip(kinds, parts) if k == "gmix"]
+        kps = [p for k, p in zip(kinds, parts) if k == "kde"]
         self._kinds, self._parts = tuple(kinds), tuple(parts)
         self.flow_priors, self.gaussian_priors, self.mixture_priors = tuple(fps), tuple(gps), tuple(mps)
+        self.kde_priors = tuple(kps)
         self.blocks = len(parts)
         self.rest = copy.deepcopy(rest)
         Dr = 0 if self.rest is None else self.rest.dim
@@ -1504,9 +1770,11 @@ class JointPrior:
         flow_cols = [c for k, c in zip(kinds, self._block_cols) if k == "flow"]
         gauss_cols = [c for k, c in zip(kinds, self._block_cols) if k in ("gauss", "gauss_box")]
         mix_cols = [c for k, c in zip(kinds, self._block_cols) if k == "gmix"]
+        kde_cols = [c for k, c in zip(kinds, self._block_cols) if k == "kde"]
         # (the descriptors point into these tensors: they live as long as the descriptors do)
         self._dev = dict(cols=[up(c) for c in flow_cols], gauss_cols=[up(c) for c in gauss_cols],
-                         mix_cols=[up(c) for c in mix_cols], rest_cols=up(self._rest_cols) if Dr else None)
+                         mix_cols=[up(c) for c in mix_cols], kde_cols=[up(c) for c in kde_cols],
+                         rest_cols=up(self._rest_cols) if Dr else None)
         self._rdesc = None
         if Dr:
             tab = self.rest.device_table()
@@ -1520,9 +1788,9 @@ class JointPrior:
         rest_cols_ptr = self._dev["rest_cols"].data_ptr() if Dr else None
         self._jdesc = None
         if fps:
-            # (D: x has the Gaussian and mixture blocks' columns as well; 0 where the flow blocks and the table cover every
-            # column)
-            j = _lib.pmc_joint_blocks_t(n_blocks=len(fps), D=self._dim if gps or mps else 0, rest=rest_ptr,
+            # (D: x has the Gaussian, mixture and KDE blocks' columns as well; 0 where the flow blocks and the table cover
+            # every column)
+            j = _lib.pmc_joint_blocks_t(n_blocks=len(fps), D=self._dim if gps or mps or kps else 0, rest=rest_ptr,
                                         rest_cols=rest_cols_ptr)
             for b, fp in enumerate(fps):
                 j.scaler[b] = C.cast(C.pointer(fp._sdesc), C.c_void_p)
@@ -1553,6 +1821,12 @@ class JointPrior:
         for b, mp in enumerate(mps):
             first = b == 0 and not fps and not gps
             self._mdescs.append(mp._descriptor(mp._device(dev), self._dev["mix_cols"][b], self._dim,
+                                               rest_ptr if first else None, rest_cols_ptr if first else None))
+        # and one per KDE block, likewise: the table goes through the first one only where nothing at all precedes
+        self._kdescs = []
+        for b, kp in enumerate(kps):
+            first = b == 0 and not fps and not gps and not mps
+            self._kdescs.append(kp._descriptor(kp._device(dev), self._dev["kde_cols"][b], self._dim,
                                                rest_ptr if first else None, rest_cols_ptr if first else None))
         self._offsets = np.concatenate([[0], np.cumsum([fp.dim for fp in fps])]).astype(np.int64)
         self._ws = {}
@@ -1751,10 +2025,55 @@ class JointPrior:
                 base = _lib.ptr(out)
         return out
 
+    def _logpdf_device_kde(self, x):
+        """The blocks form with KDE blocks: the launches of the same prior without them (``_logpdf_device_mix``,
+        ``_logpdf_device_gauss`` or ``_logpdf_device_blocks``), then one ``pmc_kde_logpdf`` launch per KDE block in list
+        order, each adding its block in place; where nothing precedes, the first launch starts the value, with the table in
+        it."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .mcmc import _on_device
+        D, dev = self.dim, self._device
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != D:
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"JointPrior.logpdf_device: expected an (n, {D}) float64 tensor, got {what}")
+        _on_device(x, dev, "JointPrior.logpdf_device")
+        n = x.shape[0]
+        if n == 0:
+            return torch.empty(0, dtype=torch.float64, device=dev)
+        # the two layouts the kernels read with coalesced loads; everything else is copied once, for all of them
+        if x.is_contiguous():
+            strides = (D, 1)
+        elif x.t().is_contiguous():
+            strides = (1, n)
+        else:
+            x, strides = x.contiguous(), (D, 1)
+        if self.mixture_priors:
+            out = self._logpdf_device_mix(x)
+        elif self.gaussian_priors:
+            out = self._logpdf_device_gauss(x)
+        elif self.flow_priors:
+            out = self._logpdf_device_blocks(x)
+        else:
+            out = None
+        base = None if out is None else _lib.ptr(out)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            for desc in self._kdescs:
+                _lib.check(_lib.load().pmc_kde_logpdf(C.byref(desc), C.c_void_p(x.data_ptr()), strides[0], strides[1], n,
+                                                      base, _lib.ptr(out), _lib.stream_handle()), "pmc_kde_logpdf")
+                base = _lib.ptr(out)
+        return out
+
     gaussian_priors = ()          # the owned copies of the Gaussian blocks, in list order (the blocks form)
     mixture_priors = ()           # the owned copies of the mixture blocks, in list order (the blocks form)
+    kde_priors = ()               # the owned copies of the KDE blocks, in list order (the blocks form)
 
     def logpdf_device(self, x):
+        if self.kde_priors:
+            return self._logpdf_device_kde(x)
         if self.mixture_priors:
             return self._logpdf_device_mix(x)
         if self.gaussian_priors:
@@ -1804,6 +2123,9 @@ class JointPrior:
 
     def step_stage(self, n, device=None):
         """``FlowPrior.step_stage`` for the joint prior: the descriptor carries the column maps and the table as well."""
+        if self.kde_priors:
+            raise ValueError("JointPrior.step_stage: a prior with a KDE block is not evaluated inside the step of a host "
+                             "likelihood (step_prior); use logpdf, or device_prior=True with a device likelihood")
         if self.mixture_priors:
             raise ValueError("JointPrior.step_stage: a prior with a mixture block is not evaluated inside the step of a host "
                              "likelihood (step_prior); use logpdf, or device_prior=True with a device likelihood")

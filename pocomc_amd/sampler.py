@@ -269,6 +269,9 @@ class Sampler:
         if self.step_prior and getattr(prior, "mixture_priors", ()):
             raise ValueError("step_prior=True does not take a JointPrior with a mixture block (its step_stage refuses): use "
                              "device_prior=True with a device likelihood")
+        if self.step_prior and getattr(prior, "kde_priors", ()):
+            raise ValueError("step_prior=True does not take a JointPrior with a KDE block (its step_stage refuses): use "
+                             "device_prior=True with a device likelihood")
         if self.step_prior and self.ranks.world > 1:
             raise ValueError("step_prior=True does not run on sharded walkers (a process group)")
         # (blob_shape, dtype name) of the device blobs, or blob_shape of a vectorised host likelihood's: fixed by the first call
